@@ -1,7 +1,14 @@
 """bench.py -- refined SV loci/sec on MI355X (BASELINE.json metric), driver contract.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: it generates the workload, loads it, warms up,
+times the K steps, writes the last step's records with --dump-outputs DIR (DIR/records.npy, see
+dump_outputs) and prints the result line (metric, value, unit, ms_per_step, config, engine
+identity).  --full adds, after the timed steps and untimed: the records checks against the CPU
+oracle, the phase and cold-cache timings, the roofline / traffic / per-kernel figures, the exact
+work count and the CPU baseline described below.
 
 Workload: BASELINE config 4 by default (cfg4_1m_delins_30x_hifi: 1M DEL+INS calls over 22
 contigs, 30x HiFi-like pileup) -- the configuration the >= 100k loci/s target is quoted on.
@@ -183,6 +190,31 @@ def parity_sample(parts, res, first_rows, n_random: int = 10000, seed: int = 0, 
     return out
 
 
+DUMP_MAX_ROWS = 2_000_000   # x 3 float64 columns = 48 MB, under the 64 MB a dump may take
+
+
+def dump_outputs(out_dir: str, parts, seed: int = 0) -> dict:
+    """--dump-outputs DIR: what the timed path computed in its last step, as a caller receives
+    it -- the gathered {vcf_index, start, end, pad} record buffers `parts` -- written as
+    DIR/records.npy: float64 [rows, 3] = (vcf_index, start, end) in the order the records hold
+    (rank by rank, genomic order within a rank), gather pads dropped; NA stays 4294967295 (every
+    uint32 is exact in float64).  More than DUMP_MAX_ROWS rows: a seeded sample of them (sorted
+    positions, the same rows in every run).  The workload is seeded, so two builds run with the
+    same arguments write comparable files."""
+    import numpy as np
+    from svtrek_amd.distributed import PAD_INDEX
+    rec = np.concatenate([np.asarray(p).reshape(-1, 4) for p in parts]).view(np.uint32)
+    rec = rec[rec[:, 0] != PAD_INDEX]
+    n_rows = len(rec)
+    if n_rows > DUMP_MAX_ROWS:
+        rec = rec[np.sort(np.random.default_rng(seed).choice(n_rows, size=DUMP_MAX_ROWS, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, "records.npy")
+    np.save(path, np.ascontiguousarray(rec[:, :3], dtype=np.float64))
+    return {"records.npy": {"rows": int(len(rec)), "of": int(n_rows), "columns": ["vcf_index", "start", "end"],
+                            "dtype": "float64"}}
+
+
 STEP_KERNELS = ("ix2_census_kernel", "ix2_emit_kernel", "refine_lane_kernel", "refine_redo_kernel")
 STREAM_INDEX_KERNELS = ("index_kernel", "ix_copy_kernel")   # the long-read index build (svt_index.inc)
 BUCKET_INDEX_KERNELS = ("ixb_lane_kernel",)                  # the value buckets filed from the stream (short reads)
@@ -310,6 +342,8 @@ def dry_run(args, world: int, rank: int) -> int:
         parts = [p.numpy().view(np.uint32).reshape(-1, 4) for p in pg.gathered(args.steps - 1)]
         unpack_records(np.concatenate(parts), n_total)
         ranks_seen = sum(int((p[:, 0] != 0xFFFFFFFF).any()) for p in parts)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, parts)
         ps = parity_sample(parts, res, np.arange(min(n_total, 200)), n_random=500, threads=2)
         rc = 1 if ps["mismatches"] else 0
         print(json.dumps({
@@ -345,6 +379,13 @@ def main() -> int:
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=DEFAULT_WORKLOAD)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also: the records checks against the CPU oracle, phase and "
+                         "cold-cache timings, roofline / traffic figures, the work count and the CPU baseline "
+                         "(--no-cpu-baseline, --no-cold, --no-verify and --parity-full trim or widen these)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's records to DIR/records.npy (float64 [rows, 3]: vcf_index, "
+                         "start, end)")
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cold", action="store_true")
@@ -370,6 +411,10 @@ def main() -> int:
     ap.add_argument("--scale", type=float, default=1.0,
                     help="diagnostic: scale the workload's locus count (and so its genome) by this factor")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.parity_full and not (args.full or args.dry_run):
+        ap.error("--parity-full is one of --full's checks: give --full as well")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -437,7 +482,7 @@ def main() -> int:
     load_s = (time.perf_counter() - t0) / K
     eng = engs[0]
     load_stats = eng.load_stats()
-    work = eng.count_work(sl)   # exact algorithmic work (counting kernel, untimed)
+    work = eng.count_work(sl) if args.full else None   # exact algorithmic work (counting kernel, untimed)
 
     d_loci = torch.from_numpy(np.ascontiguousarray(sl).view(np.uint8).copy()).to(dev)
     d_index = torch.from_numpy(rows.astype(np.uint32).view(np.int32)).to(dev)
@@ -501,15 +546,73 @@ def main() -> int:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         t_max = float(tt.item())
 
-    # ---- untimed: every VCF row arrives exactly once at rank 0 (last step's records), and the
-    # records agree with the CPU oracle on a sample (the whole set with --parity-full)
+    # ---- untimed: the last step's records as rank 0 holds them, written out on request
     last = args.steps - 1
+    parts = None
+    dumped = None
+    if rank == 0 and (gather or world == 1) and (args.dump_outputs or (args.full and not args.no_verify)):
+        parts = [p.cpu().numpy().view(np.uint32).reshape(-1, 4) for p in pg.gathered(last)]
+    if args.dump_outputs and parts is not None:
+        dumped = dump_outputs(args.dump_outputs, parts)
+    elif args.dump_outputs and rank == 0:
+        print("bench.py: --dump-outputs wrote nothing: --no-gather leaves rank 0 without the other ranks' records",
+              file=sys.stderr, flush=True)
+
+    total_loci = (n if args.emulate_shard else n_total) * args.steps
+    value = total_loci / t_max
+    head = {
+        "metric": "refined SV loci/sec (whole node)",
+        "value": round(value, 1),
+        "unit": "loci/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(t_max / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "int32",
+        "data": "synthetic (seeded simpileup: HiFi/ONT-like pileup + SV loci; no real BAM)",
+        "full": args.full,
+        "config": {"workload": args.workload, "loci_total": n_total, "loci_per_gpu": n,
+                   "reads_per_gpu": spile.n_reads, "cigar_ops_per_gpu": spile.n_ops,
+                   "coverage": cfg.coverage, "read_len_mean": cfg.read_len_mean,
+                   "parallelism": f"genomic row shard x{world}",
+                   "gather": ("16-B records, RCCL gather to rank 0, overlapped with the next launch"
+                              if backend == "nccl" else "16-B records, gloo gather to rank 0 through host memory")
+                   if gather else None,
+                   **({"loci_scale": args.scale} if args.scale != 1.0 else {}),
+                   **({"emulated_shard": args.emulate_shard} if args.emulate_shard else {})},
+    }
+    tail = {
+        **({"outputs": dumped} if dumped else {}),
+        "engine_lib": engine_lib_identity(),
+        **({"emulation": f"one-device emulation: {world} ranks on {ndev} GPU(s), gather through host memory "
+                         "(gloo) -- the N-rank path with the engine, not a scaling number"} if emulated else {}),
+        "setup_s": {"generate": round(gen_s, 2), "shard": round(shard_s, 2), "load_pileup": round(load_s, 2)},
+        "pileup_device_bytes": eng.device_bytes,
+        "engine_version": _engine_version(),
+    }
+
+    def finish() -> None:
+        for e_ in engs:
+            e_.close()
+        if world > 1:
+            dist.destroy_process_group()
+
+    if not args.full:   # the plain run ends here: the headline, the step timing and the identity of what ran
+        if rank == 0:
+            print(json.dumps({**head, "step_ms_mean": round(step_ms, 5), "steps_in_flight": K, **tail}), flush=True)
+        finish()
+        return 0
+
+    # ---- untimed, --full: every VCF row arrives exactly once at rank 0 (last step's records), and
+    # the records agree with the CPU oracle on a sample (the whole set with --parity-full)
     verified = None
     gather_ranks = None
     parity = None
     rc = 0
-    if rank == 0 and (gather or world == 1) and not args.no_verify:
-        parts = [p.cpu().numpy().view(np.uint32).reshape(-1, 4) for p in pg.gathered(last)]
+    if args.full and parts is not None and not args.no_verify:
         if not args.emulate_shard:
             unpack_records(np.concatenate(parts), n_total)
         gather_ranks = sum(int((p[:, 0] != 0xFFFFFFFF).any()) for p in parts)
@@ -542,8 +645,6 @@ def main() -> int:
         del flush
     eng.sync(sh)
 
-    total_loci = (n if args.emulate_shard else n_total) * args.steps
-    value = total_loci / t_max
     ref_bytes = 24 * n + 12 * work["reads"] + 4 * work["ops_walked"]
     ev_bytes = int(work["event_bytes"]) + 12 * n   # records: 16-B result record (not 8) + 4-B row index
     idx_bytes = int(load_stats.get("bucket_bytes" if load_stats.get("bucket_index") else "index_bytes", 0))
@@ -574,27 +675,7 @@ def main() -> int:
 
     if rank == 0:
         out = {
-            "metric": "refined SV loci/sec (whole node)",
-            "value": round(value, 1),
-            "unit": "loci/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(t_max / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "int32",
-            "data": "synthetic (seeded simpileup: HiFi/ONT-like pileup + SV loci; no real BAM)",
-            "config": {"workload": args.workload, "loci_total": n_total, "loci_per_gpu": n,
-                       "reads_per_gpu": spile.n_reads, "cigar_ops_per_gpu": spile.n_ops,
-                       "coverage": cfg.coverage, "read_len_mean": cfg.read_len_mean,
-                       "parallelism": f"genomic row shard x{world}",
-                       "gather": ("16-B records, RCCL gather to rank 0, overlapped with the next launch"
-                                  if backend == "nccl" else "16-B records, gloo gather to rank 0 through host memory")
-                       if gather else None,
-                       **({"loci_scale": args.scale} if args.scale != 1.0 else {}),
-                       **({"emulated_shard": args.emulate_shard} if args.emulate_shard else {})},
+            **head,
             "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
                          "frac_hbm": round(traffic / step_s / 1e9 / HBM_PEAK_GBS, 4) if traffic else None,
@@ -658,21 +739,13 @@ def main() -> int:
             "records_verified": verified,
             "parity_sample": parity,
             "gather_ranks": gather_ranks,
-            "engine_lib": engine_lib_identity(),
-            **({"emulation": f"one-device emulation: {world} ranks on {ndev} GPU(s), gather through host memory "
-                             "(gloo) -- the N-rank path with the engine, not a scaling number"} if emulated else {}),
-            "setup_s": {"generate": round(gen_s, 2), "shard": round(shard_s, 2), "load_pileup": round(load_s, 2)},
-            "pileup_device_bytes": eng.device_bytes,
-            "engine_version": _engine_version(),
+            **tail,
         }
         print(json.dumps(out), flush=True)
         if rc:
             print(f"bench.py: parity self-check failed: {parity['mismatches']} of {parity['loci']} sampled loci "
                   f"differ from the oracle (first: {parity.get('first')})", file=sys.stderr, flush=True)
-    for e_ in engs:
-        e_.close()
-    if world > 1:
-        dist.destroy_process_group()
+    finish()
     return rc
 
 

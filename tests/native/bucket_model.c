@@ -11,7 +11,7 @@
 #include <stdlib.h>
 #include <stdint.h>
 #include <string.h>
-#include "/root/repo/oracle/svtrek_oracle.h"
+#include "svtrek_oracle.h"   /* oracle/ (tests/test_bucket_model.py passes -I) */
 
 #define SAT (1u << 30)
 #define TRAIL 0xEu

@@ -25,7 +25,7 @@ PARAMS = [[20000, 10000, 2000, 500, 5, 3], [3000, 1500, 700, 400, 10, 2], [20000
 def model(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("bkm") / "bucket_model")
     lib = os.path.join(ROOT, "oracle")
-    subprocess.run(["gcc", "-O2", "-o", out, os.path.join(ROOT, "tests", "native", "bucket_model.c"), "-L" + lib,
+    subprocess.run(["gcc", "-O2", "-I" + lib, "-o", out, os.path.join(ROOT, "tests", "native", "bucket_model.c"), "-L" + lib,
                     "-loracle", "-Wl,-rpath," + lib, "-lpthread"], check=True)
     return out
 

@@ -298,6 +298,51 @@ def test_parity_sample_counts_mismatches():
     assert ps["mismatches"] == 1 and ps["first"]["vcf_row"] == int(parts[1][5, 0])
 
 
+def test_bench_dump_outputs_records(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs DIR): the gathered record buffers as DIR/records.npy,
+    float64 [rows, 3] = (vcf_index, start, end) with the gather pads dropped and NA exact; above
+    DUMP_MAX_ROWS rows the same seeded sample of the rows in every run."""
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    sys.path.insert(0, os.path.dirname(here))
+    import bench
+    import oracle_ffi as O
+    from svtrek_amd import sim
+    from svtrek_amd.distributed import padded_rows
+    r = sim.generate(sim.SimConfig(seed=31, n_targets=2, n_loci=301, del_frac=0.5, coverage=8.0))
+    want = O.refine_batch(r.pileup, r.loci)
+    per = padded_rows(len(r.loci), 2)   # 151 rows per rank: the second rank's buffer ends in a pad
+    parts = [pack_records(shard_rows(r.loci, 2, g), want[shard_rows(r.loci, 2, g)], per) for g in range(2)]
+    info = bench.dump_outputs(str(tmp_path / "a"), [p.view(np.int32) for p in parts])   # (as torch hands them over)
+    a = np.load(tmp_path / "a" / "records.npy")
+    assert a.dtype == np.float64 and a.shape == (301, 3) and info["records.npy"]["rows"] == 301
+    idx = a[:, 0].astype(np.int64)
+    assert sorted(idx) == list(range(301))
+    np.testing.assert_array_equal(a[:, 1], want["start"][idx].astype(np.float64))
+    np.testing.assert_array_equal(a[:, 2], want["end"][idx].astype(np.float64))
+    assert (a[:, 1:] == float(0xFFFFFFFF)).any()   # an unrefined breakpoint stays NA, exactly
+    monkeypatch.setattr(bench, "DUMP_MAX_ROWS", 100)
+    info = bench.dump_outputs(str(tmp_path / "b"), parts)
+    bench.dump_outputs(str(tmp_path / "c"), parts)
+    b, c = np.load(tmp_path / "b" / "records.npy"), np.load(tmp_path / "c" / "records.npy")
+    assert b.shape == (100, 3) and info["records.npy"] == {"rows": 100, "of": 301, "dtype": "float64",
+                                                           "columns": ["vcf_index", "start", "end"]}
+    np.testing.assert_array_equal(b, c)
+    full = {int(x[0]): (x[1], x[2]) for x in a}
+    assert len(set(b[:, 0])) == 100 and all(full[int(x[0])] == (x[1], x[2]) for x in b)
+
+
+def test_bench_parity_full_needs_full():
+    """--parity-full widens one of --full's checks; a plain run that names it is refused, not
+    run without the check."""
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    bench = os.path.join(os.path.dirname(here), "bench.py")
+    r = subprocess.run([sys.executable, bench, "--parity-full"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--full" in r.stderr
+
+
 def test_bench_refuses_world_size_mismatch():
     import subprocess
     import sys

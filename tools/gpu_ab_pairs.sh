@@ -17,7 +17,7 @@ for spec in "$@"; do
   v=${spec%%|*}; rest=${spec#*|}; wl=${rest%%|*}; extra=${rest#*|}; [ "$extra" = "$rest" ] && extra=""
   lib=$PWD/svtrek_amd/libsvtrek_hip.so; [ "$v" != default ] && lib=$PWD/variants/$v.so
   n="${v}_${wl}$(echo "$extra" | tr -c 'a-zA-Z0-9' '_')"
-  SVTREK_ENGINE_LIB=$lib timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-cold \
+  SVTREK_ENGINE_LIB=$lib timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-cold \
     --workload "$wl" $extra > "$OUT/$n.log" 2>&1 || { echo "$n failed rc=$?"; tail -5 "$OUT/$n.log"; exit 1; }
   python - "$n" "$OUT/$n.log" <<'PY'
 import json, sys

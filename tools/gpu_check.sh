@@ -19,6 +19,6 @@ run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $?
 run pytest 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread; rc=$?
 tail -5 "$OUT/pytest.log"
 if [ $rc -gt 1 ]; then echo "pytest crashed rc=$rc"; exit $rc; fi
-run bench 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline || exit $?
+run bench 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline || exit $?
 tail -1 "$OUT/bench.log"
 exit $rc

@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 run() {  # name, timeout, args...
   local name=$1 t=$2; shift 2
   echo "[$(date +%T)] $name" >> "$OUT/steps.log"
-  timeout -k 10 "$t" python -u bench.py "$@" > "$OUT/$name.log" 2>&1
+  timeout -k 10 "$t" python -u bench.py --full "$@" > "$OUT/$name.log" 2>&1
   local rc=$?
   echo "[$(date +%T)] $name rc=$rc" >> "$OUT/steps.log"
   [ $rc -eq 0 ] || { tail -20 "$OUT/$name.log"; exit $rc; }

@@ -13,7 +13,7 @@ for pass in "$@"; do
   i=$((i+1))
   echo "[$(date +%T)] pass $i: $pass" >> "$OUT/steps.log"
   timeout -k 10 300 rocprofv3 --pmc $pass --output-format csv -d "$OUT/p$i" -o run -- \
-    python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/p$i.log" 2>&1
+    python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/p$i.log" 2>&1
   rc=$?
   echo "[$(date +%T)] pass $i rc=$rc" >> "$OUT/steps.log"
   if [ $rc -ne 0 ]; then tail -20 "$OUT/p$i.log"; exit $rc; fi

@@ -12,7 +12,7 @@ for lib in svtrek_amd/libsvtrek_hip.so svtrek_amd/diag/*.so; do
   name=$(basename "$lib" .so)
   for args in "$@"; do
     i=$((i+1))
-    SVTREK_ENGINE_LIB=$PWD/$lib timeout -k 10 300 python bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-verify $args > "$OUT/$i.log" 2>&1 || { echo "fail $name $args"; tail -5 "$OUT/$i.log"; exit 1; }
+    SVTREK_ENGINE_LIB=$PWD/$lib timeout -k 10 300 python bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --no-verify $args > "$OUT/$i.log" 2>&1 || { echo "fail $name $args"; tail -5 "$OUT/$i.log"; exit 1; }
     echo "$name [$args] $(python3 -c "import json;d=json.loads(open('$OUT/$i.log').read().strip().splitlines()[-1]);r=d['roofline'];print(round(d['value']), r['kernel_ms_mean'], r['frac'])")" | tee -a "$OUT/summary.txt"
   done
 done

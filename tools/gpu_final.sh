@@ -12,12 +12,12 @@ export TMPDIR=/tmp
 bash tools/gpu_profile.sh "${TAG}_cfg4" || exit $?
 bash tools/gpu_profile.sh "${TAG}_cfg5" --workload cfg5_100k_60x_ul_ont || exit $?
 echo "[$(date +%T)] bench" >> "$OUT/steps.log"
-timeout -k 10 400 python3 bench.py > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -20 "$OUT/bench.log"; exit 1; }
+timeout -k 10 400 python3 bench.py --full > "$OUT/bench.log" 2>&1 || { echo "bench failed"; tail -20 "$OUT/bench.log"; exit 1; }
 echo "[$(date +%T)] bench done" >> "$OUT/steps.log"
 tail -1 "$OUT/bench.log" | cut -c1-300
 for spec in "shard8_r0|--emulate-shard 8:0" "shard8_r7|--emulate-shard 8:7" "scale0125|--scale 0.125"; do
   n=${spec%%|*}; a=${spec#*|}
-  timeout -k 10 300 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-cold $a > "$OUT/cfg4_$n.log" 2>&1 \
+  timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-cold $a > "$OUT/cfg4_$n.log" 2>&1 \
     || { echo "$n failed"; tail -5 "$OUT/cfg4_$n.log"; exit 1; }
   echo "[$(date +%T)] cfg4_$n done" >> "$OUT/steps.log"
 done

@@ -18,7 +18,7 @@ for lib in "${LIBS[@]}"; do
   for pass in "$P1" "$P2"; do
     i=$((i+1))
     SVTREK_ENGINE_LIB=$PWD/$lib timeout -s KILL 200 rocprofv3 --pmc $pass --output-format csv -d "$OUT/${name}_p$i" -o run -- \
-      python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-cold --no-verify "$@" > "$OUT/${name}_p$i.log" 2>&1 \
+      python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-cold --no-verify "$@" > "$OUT/${name}_p$i.log" 2>&1 \
       || { echo "fail $name p$i"; tail -5 "$OUT/${name}_p$i.log"; exit 1; }
   done
   echo "done $name"

@@ -19,10 +19,10 @@ run() {  # name, timeout, cmd...
 run pytest 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread -k "$K"; rc=$?
 tail -3 "$OUT/pytest.log"
 if [ $rc -gt 1 ]; then echo "pytest crashed rc=$rc"; exit $rc; fi
-run bench 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline "$@" || exit $?
+run bench 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline "$@" || exit $?
 tail -1 "$OUT/bench.log"
 export TMPDIR=/tmp
 run trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- \
-  python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-cold "$@" || exit $?
+  python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-cold "$@" || exit $?
 head -8 "$OUT/trace/run_kernel_stats.csv" | cut -c1-150
 exit $rc

@@ -12,7 +12,7 @@ exec_steps() { bash tools/gpu_steps.sh "$TAG" "$@"; }
 exec_steps \
   "pytest|700|python -u -m pytest -x -q --timeout 240 --timeout-method thread -m gpu tests" \
   "smoke|120|python -c 'import __graft_entry__ as g; g.smoke()'" \
-  "bench|300|python bench.py" \
-  "bench_rank3|300|python bench.py --emulate-shard 8:3 --no-cpu-baseline" \
-  "trace|400|rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-cold" \
+  "bench|300|python bench.py --full" \
+  "bench_rank3|300|python bench.py --full --emulate-shard 8:3 --no-cpu-baseline" \
+  "trace|400|rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-cold" \
   "$@"

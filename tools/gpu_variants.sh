@@ -10,7 +10,7 @@ WL=${VARIANT_WORKLOADS:-cfg4_1m_delins_30x_hifi}
 for wl in $WL; do
 for so in variants/*.so; do
   n=$(basename "$so" .so)_$wl
-  SVTREK_ENGINE_LIB=$PWD/$so timeout -k 10 240 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-cold --workload $wl "$@" \
+  SVTREK_ENGINE_LIB=$PWD/$so timeout -k 10 240 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-cold --workload $wl "$@" \
     > "$OUT/$n.log" 2>&1 || { echo "$n failed rc=$?"; tail -5 "$OUT/$n.log"; exit 1; }
   python - "$n" "$OUT/$n.log" <<'PY'
 import json, sys
