@@ -30,6 +30,7 @@ SW_QUERY_DTYPE = np.dtype([("chrom", "<i4"), ("start", "<u4"), ("end", "<u4")]) 
 SW_WINDOW_DTYPE = np.dtype([("candidate", "<i4"), ("support", "<i4")])               # svt_sw_window
 BGZF_BLOCK_DTYPE = np.dtype([("coff", "<u8"), ("uoff", "<u8"), ("clen", "<u4"), ("ulen", "<u4")])   # svt_bgzf_block
 RECORD_DTYPE = np.dtype([("index", "<u4"), ("start", "<u4"), ("end", "<u4"), ("pad", "<u4")])   # svt_record
+EVIDENCE_DTYPE = np.dtype([("support", "<u4"), ("depth", "<u4"), ("lo", "<u4"), ("hi", "<u4")])   # svt_evidence
 
 
 class SvtParams(C.Structure):
@@ -125,6 +126,9 @@ ENGINE_SYMBOLS = (
     "svt_host_alloc", "svt_host_free",
     "svt_bam_dec_open", "svt_bam_dec_feed", "svt_bam_dec_load", "svt_bam_dec_stats_get", "svt_bam_dec_close",
 )
+# include/svtrek_evidence.h: an extension the HIP engine exports; a backend without it (the CPU
+# restatement) still binds, and Engine.evidence raises on it
+EVIDENCE_SYMBOLS = ("svt_evidence_batch", "svt_evidence_device")
 
 _engine = None
 
@@ -210,7 +214,17 @@ def bind_abi(lib: C.CDLL) -> C.CDLL:
                  "svt_open", "svt_open_multi", "svt_refine_device_records", "svt_load_pileup", "svt_refine_batch", "svt_refine_device", "svt_sync",
                  "svt_reindex", "svt_count_work", "svt_sliding_window_ins", "svt_load_insseq", "svt_poa_consensus"):
         getattr(lib, name).restype = C.c_int32
+    if has_evidence(lib):
+        lib.svt_evidence_batch.argtypes = [P, P, P, C.c_size_t, P]
+        lib.svt_evidence_device.argtypes = [P, P, P, C.c_size_t, P, P]
+        for name in EVIDENCE_SYMBOLS:
+            getattr(lib, name).restype = C.c_int32
     return lib
+
+
+def has_evidence(lib: C.CDLL) -> bool:
+    """Does the library export include/svtrek_evidence.h's entry points?"""
+    return all(hasattr(lib, name) for name in EVIDENCE_SYMBOLS)
 
 
 _sim = None

@@ -42,7 +42,8 @@ def build_engine(force: bool = False) -> str:
     deps = [os.path.join(CSRC, "svt_engine.hip"), os.path.join(INC, "svtrek_gpu.h"), os.path.join(CSRC, "svt_poa.inc"),
             os.path.join(CSRC, "svt_index.inc"), os.path.join(CSRC, "svt_index2.inc"),
             os.path.join(CSRC, "svt_inflate.inc"), os.path.join(CSRC, "svt_bamrec.h"), os.path.join(CSRC, "svt_bam.inc"),
-            os.path.join(CSRC, "svt_bucket.inc"), os.path.join(CSRC, "svt_bucket_build.inc")]
+            os.path.join(CSRC, "svt_bucket.inc"), os.path.join(CSRC, "svt_bucket_build.inc"),
+            os.path.join(CSRC, "svt_evidence.inc"), os.path.join(INC, "svtrek_evidence.h")]
     if force or _stale(out, deps):
         _run([HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared",
               "-Wall", "-I", INC, "-o", out, deps[0]])
@@ -56,7 +57,8 @@ def build_test_engine(force: bool = False) -> str:
     deps = [os.path.join(CSRC, "svt_engine.hip"), os.path.join(INC, "svtrek_gpu.h"), os.path.join(CSRC, "svt_poa.inc"),
             os.path.join(CSRC, "svt_index.inc"), os.path.join(CSRC, "svt_index2.inc"),
             os.path.join(CSRC, "svt_inflate.inc"), os.path.join(CSRC, "svt_bamrec.h"), os.path.join(CSRC, "svt_bam.inc"),
-            os.path.join(CSRC, "svt_bucket.inc"), os.path.join(CSRC, "svt_bucket_build.inc")]
+            os.path.join(CSRC, "svt_bucket.inc"), os.path.join(CSRC, "svt_bucket_build.inc"),
+            os.path.join(CSRC, "svt_evidence.inc"), os.path.join(INC, "svtrek_evidence.h")]
     if force or _stale(out, deps):
         os.makedirs(os.path.dirname(out), exist_ok=True)
         _run([HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-DSVT_POA_RING=2",
@@ -67,7 +69,8 @@ def build_test_engine(force: bool = False) -> str:
 def build_host(force: bool = False) -> str:
     out = os.path.join(PKG, "libsvtrek_host.so")
     srcs = [os.path.join(CSRC, f) for f in ("bam_ingest.cpp", "vcf_audit.cpp")]
-    hdrs = [os.path.join(CSRC, "svtrek_host.h"), os.path.join(INC, "svtrek_gpu.h"), os.path.join(CSRC, "svt_bamrec.h")]
+    hdrs = [os.path.join(CSRC, "svtrek_host.h"), os.path.join(INC, "svtrek_gpu.h"), os.path.join(INC, "svtrek_evidence.h"),
+            os.path.join(CSRC, "svt_bamrec.h")]
     if all(os.path.exists(s) for s in srcs) and (force or _stale(out, srcs + hdrs)):
         _run(["g++", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-pthread",
               "-I", INC, "-o", out] + srcs + ["-lz", "-ldl"])
@@ -78,7 +81,8 @@ def build_cli(force: bool = False) -> str:
     out = os.path.join(PKG, "svtrek")
     main = os.path.join(CSRC, "svtrek_main.cpp")
     srcs = [main] + [os.path.join(CSRC, f) for f in ("bam_ingest.cpp", "vcf_audit.cpp")]
-    hdrs = [os.path.join(CSRC, "svtrek_host.h"), os.path.join(INC, "svtrek_gpu.h"), os.path.join(CSRC, "svt_bamrec.h")]
+    hdrs = [os.path.join(CSRC, "svtrek_host.h"), os.path.join(INC, "svtrek_gpu.h"), os.path.join(INC, "svtrek_evidence.h"),
+            os.path.join(CSRC, "svt_bamrec.h")]
     eng = os.path.join(PKG, "libsvtrek_hip.so")
     if all(os.path.exists(s) for s in srcs) and (force or _stale(out, srcs + hdrs + [eng])):
         _run(["g++", "-O3", "-std=c++17", "-Wall", "-Wextra", "-pthread", "-I", INC, "-o", out] + srcs +

@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "../../include/svtrek_gpu.h"
+#include "../../include/svtrek_evidence.h"
 #include "svt_bamrec.h"
 
 #define SVT_VERSION "svtrek_amd 0.25.0 (gfx950, value-bucketed event index filed by a lane-per-read walk with a 9-B LDS stage, band + prefix-max facts, packed span walk fed by readlane, lane vote, BGZF inflate + BAM decode)"
@@ -260,9 +261,10 @@ __device__ __forceinline__ bool is_candidate_op(uint32_t op, uint32_t len) {
 // Per-read walk, 64 ops per step, replaying the reference's uint32 position arithmetic
 // exactly (refinement.c:118-159 / :184-221 / :295-318).  Used for reads whose walk could
 // wrap 2^32 (never in practice) and by the per-read gather variant.
-template <int KIND, bool COUNT>
+// SinkT: the LDS candidate sink, or svt_evidence.inc's counting sink (push(pred, val) per lane).
+template <int KIND, bool COUNT, typename SinkT>
 __device__ __forceinline__ void walk_read(const uint32_t *__restrict__ cigar, uint64_t off, uint32_t n, uint32_t rpos,
-                          uint32_t clip, uint32_t s, uint32_t e, Sink &sink, WinStats &st) {
+                          uint32_t clip, uint32_t s, uint32_t e, SinkT &sink, WinStats &st) {
     const int ln = lane_id();
     uint32_t carry = rpos;
     bool broke = false;
@@ -345,8 +347,8 @@ __device__ __forceinline__ bool read_range(const DevPileup &P, int tid, int64_t 
 }
 
 // ------------------------------------------------------------------ per-read gather (v1)
-template <int KIND, bool COUNT>
-__device__ __forceinline__ void gather_perread(const DevPileup &P, int tid, uint32_t s, uint32_t e, Sink &sink, WinStats &st) {
+template <int KIND, bool COUNT, typename SinkT>
+__device__ __forceinline__ void gather_perread(const DevPileup &P, int tid, uint32_t s, uint32_t e, SinkT &sink, WinStats &st) {
     const int64_t beg = (int64_t)(uint32_t)(s - 1u), end = (int64_t)(uint32_t)(e - 1u);
     int64_t lo, hi;
     if (!read_range(P, tid, beg, end, lo, hi)) return;
@@ -2087,6 +2089,7 @@ __global__ void sw_reduce_kernel(const int2 *sub, const uint64_t *off, uint32_t 
     best[q] = b;
 }
 
+#include "svt_evidence.inc"
 #include "svt_index.inc"
 #include "svt_index2.inc"
 #include "svt_bucket_build.inc"
@@ -2168,6 +2171,8 @@ struct svt_ctx {
     svt_locus *d_loci = nullptr;
     svt_result *d_out = nullptr;
     size_t batch_cap = 0;
+    svt_evidence *d_evid = nullptr;   // svt_evidence_batch's records [2 * evid_cap]
+    size_t evid_cap = 0;
     // spill pool + status + work counters
     int32_t *d_pool = nullptr;
     unsigned long long pool_words = 0;
@@ -3422,6 +3427,58 @@ svt_status svt_poa_consensus(svt_ctx *c, const svt_poa_params *p, const svt_locu
     return poa_run(c, p, loci, refined, n, cap, bases, res);
 }
 
+// ---- include/svtrek_evidence.h
+static svt_status evidence_launch(svt_ctx *c, const svt_locus *d_loci, const svt_result *d_refined, size_t n,
+                                  svt_evidence *d_out, hipStream_t st) {
+    if (n > 0x3fffffffull) return fail(c, SVT_EINVAL, "batch too large (%s)", "n > 2^30-1");
+    const svt_status s = order_on(c, st);   // after every launch already issued (svt_reindex rebuilds the buckets)
+    if (s) return s;
+    const KArgs a = make_args(c, d_loci, nullptr, (uint32_t)n, false);
+    hipLaunchKernelGGL(evidence_kernel, dim3((unsigned)((2 * n + WPB - 1) / WPB)), dim3(64 * WPB), 0, st, a, d_refined,
+                       d_out);
+    HIP_TRY(c, hipGetLastError());
+    return SVT_OK;
+}
+
+svt_status svt_evidence_device(svt_ctx *c, const svt_locus *d_loci, const svt_result *d_refined, size_t n,
+                               svt_evidence *d_out, void *stream) {
+    if (!c) return SVT_EINVAL;
+    if (!c->loaded) return fail(c, SVT_ESTATE, "%s", "svt_load_pileup not called");
+    if (n == 0) return SVT_OK;
+    if (!d_loci || !d_refined || !d_out) return fail(c, SVT_EINVAL, "%s", "null loci/refined/out");
+    DEV_GUARD(c);
+    return evidence_launch(c, d_loci, d_refined, n, d_out, (hipStream_t)stream);
+}
+
+static svt_status evidence_1(svt_ctx *c, const svt_locus *loci, const svt_result *refined, size_t n, svt_evidence *out) {
+    if (n == 0) return SVT_OK;
+    DEV_GUARD(c);
+    svt_status s = ensure_batch(c, n);   // d_out holds the refined results here
+    if (s) return s;
+    if (n > c->evid_cap) {
+        hfree(c->d_evid);
+        c->evid_cap = 0;
+        HIP_TRY(c, hipMalloc(&c->d_evid, 2 * n * sizeof(svt_evidence)));
+        c->evid_cap = n;
+    }
+    HIP_TRY(c, hipMemcpy(c->d_loci, loci, n * sizeof(svt_locus), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_out, refined, n * sizeof(svt_result), hipMemcpyHostToDevice));
+    if ((s = evidence_launch(c, c->d_loci, c->d_out, n, c->d_evid, nullptr))) return s;
+    HIP_TRY(c, hipStreamSynchronize(nullptr));
+    HIP_TRY(c, hipMemcpy(out, c->d_evid, 2 * n * sizeof(svt_evidence), hipMemcpyDeviceToHost));
+    return SVT_OK;
+}
+
+svt_status svt_evidence_batch(svt_ctx *c, const svt_locus *loci, const svt_result *refined, size_t n, svt_evidence *out) {
+    if (!c) return SVT_EINVAL;
+    if (!c->loaded) return fail(c, SVT_ESTATE, "%s", "svt_load_pileup not called");
+    if (n == 0) return SVT_OK;
+    if (!loci || !refined || !out) return fail(c, SVT_EINVAL, "%s", "null loci/refined/out");
+    return for_devices(c, n, [&](svt_ctx *x, size_t lo, size_t hi) {
+        return evidence_1(x, loci + lo, refined + lo, hi - lo, out + 2 * lo);
+    });
+}
+
 uint64_t svt_pileup_device_bytes(const svt_ctx *c) { return c ? c->dev_bytes : 0; }
 
 uint64_t svt_poa_deferred(const svt_ctx *c) { return c ? c->poa_deferred : 0; }
@@ -3905,7 +3962,7 @@ void svt_close(svt_ctx *c) {
     if (c->order_ev) (void)hipEventDestroy(c->order_ev);
     free_pileup(c);
     hfree(c->d_infc); hfree(c->d_info); hfree(c->d_infb); hfree(c->d_inferr);
-    hfree(c->d_loci); hfree(c->d_out); hfree(c->d_pool); hfree(c->d_ctl); hfree(c->d_redo); hfree(c->poa_small.d); hfree(c->poa_big.d);
+    hfree(c->d_loci); hfree(c->d_out); hfree(c->d_evid); hfree(c->d_pool); hfree(c->d_ctl); hfree(c->d_redo); hfree(c->poa_small.d); hfree(c->poa_big.d);
     delete c;
 }
 

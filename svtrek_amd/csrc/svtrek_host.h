@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "svtrek_gpu.h"
+#include "svtrek_evidence.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -99,6 +100,13 @@ void             svth_vcf_free(svth_vcf *v);
 /* A11 over a batch: the concatenated stdout text of n records in order, formatted by
  * `threads` threads; malloc'ed (free with svth_free), *len = its length. */
 char *svth_format_batch(const svt_locus *l, const svt_result *r, size_t n, int threads, size_t *len);
+/* The `--evidence FILE` table (include/svtrek_evidence.h): one tab-separated line per record,
+ *   row type chrom pos end ref_pos ref_end sup_pos depth_pos lo_pos hi_pos sup_end depth_end lo_end hi_end
+ * row = the record's index (0 .. n-1), type its numeric code, chrom the index stdout prints, ev[2k] /
+ * ev[2k + 1] record k's two breakpoints; NA stands for 0xFFFFFFFF in ref_* / lo_* / hi_*.  header != 0:
+ * the "#row ..." column line first.  malloc'ed (free with svth_free), *len = its length. */
+char *svth_format_evidence(const svt_locus *l, const svt_result *r, const svt_evidence *ev, size_t n, int header,
+                           int threads, size_t *len);
 void  svth_free(void *p);
 
 /* A11: stdout text for one refined record; returns bytes written (0 = prints nothing:

@@ -28,6 +28,10 @@
 #include "svtrek_gpu.h"
 #include "svtrek_host.h"
 
+// include/svtrek_evidence.h is an extension: this file is also linked against backends that do
+// not export it, so the entry point is referenced weakly and tested before use.
+extern "C" __typeof__(svt_evidence_batch) svt_evidence_batch __attribute__((weak));
+
 namespace {
 
 // params.h:27-36
@@ -60,10 +64,12 @@ void audt_usage() {
     printf("    --spill-bytes <num>               Initial candidate spill pool per GPU; grown on demand [Default: 67108864]\n");
     printf("    --inflate <auto|gpu|cpu>          BGZF decompression of the BAM: first GPU or -t host threads;\n");
     printf("                                      auto: the GPU from 1 GiB of BAM on [Default: auto]\n");
+    printf("    --evidence <filename>             Write per-breakpoint evidence (read support, depth, value range),\n");
+    printf("                                      one tab-separated line per record in VCF order [Default: off]\n");
 }
 
 struct Args {
-    const char *bam = nullptr, *vcf = nullptr, *out = "svtrek.out";
+    const char *bam = nullptr, *vcf = nullptr, *out = "svtrek.out", *evidence = nullptr;
     int threads = THREADS, verbose = 0, gpus = 1, device = 0, gpu_inflate = -1;   // -1: by BAM size
     size_t batch = 1u << 20;
     std::vector<int> devices;   // device of shard g
@@ -100,6 +106,7 @@ Args parse_audt(int argc, char **argv) {
         {"gpus", required_argument, nullptr, 20}, {"device", required_argument, nullptr, 21},
         {"batch", required_argument, nullptr, 22}, {"devices", required_argument, nullptr, 23},
         {"spill-bytes", required_argument, nullptr, 24}, {"inflate", required_argument, nullptr, 25},
+        {"evidence", required_argument, nullptr, 26},
         {nullptr, 0, nullptr, 0}};
     int opt, li;
     while ((opt = getopt_long(argc, argv, "b:v:o:t:h", opts, &li)) != -1) {
@@ -127,6 +134,7 @@ Args parse_audt(int argc, char **argv) {
             }
             a.gpu_inflate = strcmp(optarg, "gpu") == 0 ? 1 : strcmp(optarg, "cpu") == 0 ? 0 : -1;
             break;
+        case 26: a.evidence = optarg; break;
         case 23: {
             a.devices.clear();
             for (const char *p = optarg; *p;) {
@@ -150,6 +158,10 @@ Args parse_audt(int argc, char **argv) {
     // The reference deadlocks on -t 0 and reads locations[-1] for min-count <= 0.
     if (a.threads < 1) { fprintf(stderr, "[ERROR] -t must be >= 1\n"); exit(EXIT_FAILURE); }
     if (a.prm.consensus_min_count < 1) { fprintf(stderr, "[ERROR] --consensus-min-count must be >= 1\n"); exit(EXIT_FAILURE); }
+    if (a.evidence && !svt_evidence_batch) {
+        fprintf(stderr, "[ERROR] --evidence: not supported by this backend\n");
+        exit(EXIT_FAILURE);
+    }
     if (a.gpu_inflate < 0) {   // auto: small BAMs inflate faster on the host than the HIP start-up takes
         struct stat st;
         a.gpu_inflate = stat(a.bam, &st) == 0 && st.st_size >= (off_t)(1ll << 30) ? 1 : 0;
@@ -181,10 +193,13 @@ double now_s() {
 // (audit.c:178,191-192), sam_itr_queryi(start-1, end-1) (refinement.c:114), empty when
 // end <= beg; INV collects nothing (A7).  A read is kept when pos < hull.end and
 // endpos > hull.beg -- a superset of every query's yield, so results are unchanged.
+// evidence: the hull also covers [imp - range - |ci|, imp + range + |ci|] of every breakpoint,
+// where its refined position lies, so that the shard holds the reads covering it (depth).
 struct Shard {
     std::vector<size_t> rows;
     std::vector<svt_locus> loci;
     std::vector<svt_result> res;
+    std::vector<svt_evidence> ev;   // --evidence: two per locus
     std::vector<int64_t> tid_off;
     std::vector<int32_t> pos, endpos;
     std::vector<uint64_t> cig_off;
@@ -194,7 +209,7 @@ struct Shard {
 };
 
 void build_shard(const svt_pileup_view &full, const std::vector<svt_locus> &loci, const std::vector<size_t> &rows,
-                 const svt_params &prm, Shard &sh) {
+                 const svt_params &prm, bool evidence, Shard &sh) {
     sh.rows = rows;
     sh.loci.resize(rows.size());
     for (size_t k = 0; k < rows.size(); k++) sh.loci[k] = loci[rows[k]];
@@ -208,11 +223,23 @@ void build_shard(const svt_pileup_view &full, const std::vector<svt_locus> &loci
         lo[tid] = std::min(lo[tid], b);
         hi[tid] = std::max(hi[tid], q);
     };
+    const int64_t reach = (int64_t)prm.consensus_interval_range + std::abs((int64_t)prm.consensus_interval);
+    auto cover = [&](const svt_locus &l, uint32_t imp) {   // one-base queries at imp - reach .. imp + reach
+        int tid = l.chrom - 1;
+        if (!evidence || reach < 0 || tid < 0 || tid >= nt) return;
+        lo[tid] = std::min(lo[tid], std::max<int64_t>((int64_t)imp - reach, 0));
+        hi[tid] = std::max(hi[tid], std::min<int64_t>((int64_t)imp + reach + 1, (int64_t)UINT32_MAX + 1));
+    };
     for (const svt_locus &l : sh.loci) {
-        if (l.type == 1) add(l, l.pos - (uint32_t)prm.median_interval, l.pos + (uint32_t)prm.median_interval);
+        if (l.type == 1) {
+            add(l, l.pos - (uint32_t)prm.median_interval, l.pos + (uint32_t)prm.median_interval);
+            cover(l, l.pos);
+        }
         if (l.type == 2) {
             add(l, l.pos - (uint32_t)prm.wider_interval, l.pos + (uint32_t)prm.narrow_interval);
             add(l, l.end - (uint32_t)prm.narrow_interval, l.end + (uint32_t)prm.narrow_interval);
+            cover(l, l.pos);
+            cover(l, l.end);
         }
     }
     sh.tid_off.assign(1, 0);
@@ -401,6 +428,7 @@ int audit(int argc, char **argv) {
 
     const double t_parse = now_s();
     std::vector<svt_result> res(loci.size());
+    std::vector<svt_evidence> evid(a.evidence ? 2 * loci.size() : 0);
     std::vector<int> rc(G, 0);
     std::vector<std::string> gerr(G);
     std::vector<double> load_s(G, 0.0);
@@ -419,12 +447,16 @@ int audit(int argc, char **argv) {
         if (s || !ctx) { rc[g] = s ? s : SVT_EDEVICE; gerr[g] = "svt_open failed (HIP device?)"; return; }
         const svt_locus *in = loci.data();
         svt_result *out = res.data();
+        svt_evidence *ev = evid.data();
         size_t n = loci.size();
         Shard sh;
         const double tl = now_s();
         if (G > 1) {
             size_t per = (n + G - 1) / G, b0 = std::min(n, per * (size_t)g), b1 = std::min(n, b0 + per);
-            build_shard(view, loci, std::vector<size_t>(order.begin() + b0, order.begin() + b1), a.prm, sh);
+            build_shard(view, loci, std::vector<size_t>(order.begin() + b0, order.begin() + b1), a.prm, a.evidence != nullptr,
+                        sh);
+            if (a.evidence) sh.ev.resize(2 * sh.loci.size());
+            ev = sh.ev.data();
             s = svt_load_pileup(ctx, &sh.view);
             in = sh.loci.data();
             out = sh.res.data();
@@ -441,12 +473,16 @@ int audit(int argc, char **argv) {
         for (size_t k = 0; !s && k < n; k += a.batch) {
             size_t m = std::min(a.batch, n - k);
             s = svt_refine_batch(ctx, in + k, m, out + k);
+            if (!s && a.evidence) s = svt_evidence_batch(ctx, in + k, out + k, m, ev + 2 * k);
         }
         if (s) { rc[g] = s; gerr[g] = svt_last_error(ctx); }
         svt_close(ctx);
         ctxs[g] = nullptr;
         if (!s && G > 1)
-            for (size_t k = 0; k < sh.rows.size(); k++) res[sh.rows[k]] = sh.res[k];
+            for (size_t k = 0; k < sh.rows.size(); k++) {
+                res[sh.rows[k]] = sh.res[k];
+                if (a.evidence) { evid[2 * sh.rows[k]] = sh.ev[2 * k]; evid[2 * sh.rows[k] + 1] = sh.ev[2 * k + 1]; }
+            }
     };
     if (G == 1) worker(0);
     else {
@@ -465,6 +501,15 @@ int audit(int argc, char **argv) {
     if (!out) { fprintf(stderr, "[ERROR] out of host memory\n"); return 1; }
     fwrite(out, 1, olen, stdout);
     svth_free(out);
+    if (a.evidence) {   // the evidence table, beside stdout (which stays as it is)
+        size_t elen = 0;
+        char *et = svth_format_evidence(loci.data(), res.data(), evid.data(), loci.size(), 1, a.threads, &elen);
+        FILE *ef = et ? fopen(a.evidence, "wb") : nullptr;
+        const bool ok = ef && fwrite(et, 1, elen, ef) == elen;
+        if (ef && fclose(ef) != 0) { svth_free(et); fprintf(stderr, "[ERROR] --evidence: cannot write %s\n", a.evidence); return 1; }
+        svth_free(et);
+        if (!ok) { fprintf(stderr, "[ERROR] --evidence: cannot write %s\n", a.evidence); return 1; }
+    }
     printf("[INFO] Ended processing variation file\n");
     if (a.verbose)   // --verbose is parsed but unused by the reference; here: stage timings on stderr
         fprintf(stderr, "[svtrek_amd] ingest %.3fs (%s%s)  vcf-read+parse %.3fs (beside the ingest)  "

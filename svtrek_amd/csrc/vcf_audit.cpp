@@ -186,6 +186,48 @@ char *svth_format_batch(const svt_locus *l, const svt_result *r, size_t n, int t
     return out;
 }
 
+char *svth_format_evidence(const svt_locus *l, const svt_result *r, const svt_evidence *ev, size_t n, int header,
+                           int threads, size_t *len) {
+    const int T = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(threads, 1), n / 16384 + 1));
+    std::vector<std::string> part((size_t)T);
+    run_parts(T, [&](int t) {
+        std::string &o = part[(size_t)t];
+        const size_t b = n * (size_t)t / (size_t)T, e = n * (size_t)(t + 1) / (size_t)T;
+        o.reserve((e - b) * 96);
+        char buf[256];
+        auto na = [&](uint32_t v, char sep) {   // NA for 0xFFFFFFFF
+            const int m = v == SVT_NA ? snprintf(buf, sizeof buf, "NA%c", sep) : snprintf(buf, sizeof buf, "%u%c", v, sep);
+            o.append(buf, (size_t)m);
+        };
+        for (size_t k = b; k < e; k++) {
+            const int m = snprintf(buf, sizeof buf, "%zu\t%d\t%d\t%u\t%u\t", k, l[k].type, l[k].chrom, l[k].pos, l[k].end);
+            o.append(buf, (size_t)m);
+            na(r[k].start, '\t');
+            na(r[k].end, '\t');
+            for (int w = 0; w < 2; w++) {
+                const svt_evidence &x = ev[2 * k + (size_t)w];
+                const int q = snprintf(buf, sizeof buf, "%u\t%u\t", x.support, x.depth);
+                o.append(buf, (size_t)q);
+                na(x.lo, '\t');
+                na(x.hi, w ? '\n' : '\t');
+            }
+        }
+    });
+    static const char head[] = "#row\ttype\tchrom\tpos\tend\tref_pos\tref_end\tsup_pos\tdepth_pos\tlo_pos\thi_pos\t"
+                               "sup_end\tdepth_end\tlo_end\thi_end\n";
+    const size_t hl = header ? sizeof head - 1 : 0;
+    size_t tot = hl;
+    for (auto &p : part) tot += p.size();
+    char *out = (char *)malloc(tot + 1);
+    if (!out) return nullptr;
+    memcpy(out, head, hl);
+    size_t at = hl;
+    for (auto &p : part) { memcpy(out + at, p.data(), p.size()); at += p.size(); }
+    out[tot] = 0;
+    if (len) *len = tot;
+    return out;
+}
+
 void svth_free(void *p) { free(p); }
 
 int svth_parse_line(char *line, svt_locus *l, char *err, size_t errcap) {

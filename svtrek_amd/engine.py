@@ -13,8 +13,9 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import (LOCUS_DTYPE, POA_RESULT_DTYPE, RESULT_DTYPE, STATUS_NAMES, SW_QUERY_DTYPE, SW_WINDOW_DTYPE,
-                   SvtInsseqView, SvtLoadStats, SvtParams, SvtPoaParams, SvtWork, load_engine, ptr)
+from ._lib import (EVIDENCE_DTYPE, LOCUS_DTYPE, POA_RESULT_DTYPE, RESULT_DTYPE, STATUS_NAMES, SVT_EINVAL, SW_QUERY_DTYPE,
+                   SW_WINDOW_DTYPE, SvtInsseqView, SvtLoadStats, SvtParams, SvtPoaParams, SvtWork, has_evidence,
+                   load_engine, ptr)
 from .pileup import Pileup
 
 # params.h:27-32
@@ -102,6 +103,31 @@ class Engine:
         """As refine_device, writing RECORD_DTYPE gather records {index, start, end, 0}."""
         self._check(self.lib.svt_refine_device_records(self._h, C.c_void_p(d_loci), n, C.c_void_p(d_index or 0),
                                                        int(index_base), C.c_void_p(d_rec), C.c_void_p(stream or 0)))
+
+    def _need_evidence(self) -> None:
+        if not has_evidence(self.lib):
+            raise SvtError(SVT_EINVAL, "this backend does not export svt_evidence_batch / svt_evidence_device "
+                                       "(include/svtrek_evidence.h): evidence needs the HIP engine")
+
+    def evidence(self, loci: np.ndarray, refined: np.ndarray) -> np.ndarray:
+        """Per-breakpoint evidence of refined calls (svt_evidence_batch, include/svtrek_evidence.h):
+        EVIDENCE_DTYPE records {support, depth, lo, hi} of shape (n, 2) -- [:, 0] for
+        refined["start"], [:, 1] for refined["end"]; {0, 0, NA, NA} where the value is NA."""
+        self._need_evidence()
+        loci = np.ascontiguousarray(loci, dtype=LOCUS_DTYPE)
+        refined = np.ascontiguousarray(refined, dtype=RESULT_DTYPE)
+        if len(refined) != len(loci):
+            raise ValueError(f"evidence: {len(loci)} loci but {len(refined)} refined results")
+        out = np.empty((len(loci), 2), dtype=EVIDENCE_DTYPE)
+        if len(loci):
+            self._check(self.lib.svt_evidence_batch(self._h, ptr(loci), ptr(refined), len(loci), ptr(out)))
+        return out
+
+    def evidence_device(self, d_loci: int, d_refined: int, n: int, d_out: int, stream: int | None = None) -> None:
+        """svt_evidence_device on device pointers: d_out receives 2 * n EVIDENCE_DTYPE records."""
+        self._need_evidence()
+        self._check(self.lib.svt_evidence_device(self._h, C.c_void_p(d_loci), C.c_void_p(d_refined), n,
+                                                 C.c_void_p(d_out), C.c_void_p(stream or 0)))
 
     def reindex(self, stream: int | None = None) -> None:
         """Rebuild the device index of the loaded pileup on a hipStream_t handle (svt_reindex:

@@ -42,6 +42,8 @@ def load_host() -> C.CDLL:
         L.svth_vcf_free.restype = None
         L.svth_format_batch.argtypes = [P, P, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]
         L.svth_format_batch.restype = P
+        L.svth_format_evidence.argtypes = [P, P, P, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+        L.svth_format_evidence.restype = P
         L.svth_free.argtypes = [P]
         L.svth_free.restype = None
         L.svth_bam_free.argtypes = [P]
@@ -232,6 +234,26 @@ def format_batch(loci: np.ndarray, res: np.ndarray, threads: int = 4) -> str:
     p = L.svth_format_batch(loci.ctypes.data, res.ctypes.data, len(loci), threads, C.byref(n))
     if not p:
         raise MemoryError("svth_format_batch failed")
+    try:
+        return C.string_at(p, n.value).decode("latin-1")
+    finally:
+        L.svth_free(p)
+
+
+def format_evidence(loci: np.ndarray, res: np.ndarray, ev: np.ndarray, header: bool = True, threads: int = 4) -> str:
+    """The `--evidence` table of every record, in order (svth_format_evidence); ev: (n, 2) EVIDENCE_DTYPE."""
+    from ._lib import EVIDENCE_DTYPE, RESULT_DTYPE
+    L = load_host()
+    loci = np.ascontiguousarray(loci, dtype=LOCUS_DTYPE)
+    res = np.ascontiguousarray(res, dtype=RESULT_DTYPE)
+    ev = np.ascontiguousarray(ev, dtype=EVIDENCE_DTYPE)
+    if len(res) != len(loci) or ev.size != 2 * len(loci):
+        raise ValueError("format_evidence: loci, results and evidence records do not match")
+    n = C.c_size_t(0)
+    p = L.svth_format_evidence(loci.ctypes.data, res.ctypes.data, ev.ctypes.data, len(loci), int(header), threads,
+                               C.byref(n))
+    if not p:
+        raise MemoryError("svth_format_evidence failed")
     try:
         return C.string_at(p, n.value).decode("latin-1")
     finally:
