@@ -42,7 +42,7 @@
 #include "../../include/svtrek_evidence.h"
 #include "svt_bamrec.h"
 
-#define SVT_VERSION "svtrek_amd 0.25.0 (gfx950, value-bucketed event index filed by a lane-per-read walk with a 9-B LDS stage, band + prefix-max facts, packed span walk fed by readlane, lane vote, BGZF inflate + BAM decode)"
+#define SVT_VERSION "svtrek_amd 0.26.0 (gfx950, value-bucketed event index filed by a lane-per-read walk with a 9-B LDS stage, band + prefix-max facts, packed span walk fed by readlane, lane vote on 64 windows a wave, BGZF inflate + BAM decode)"
 
 namespace {
 
@@ -374,9 +374,6 @@ __device__ __forceinline__ uint32_t ref_adv(uint32_t w) {   // refinement.c:141:
     return (w >> 4) & (uint32_t)__builtin_amdgcn_sbfe((int)~0x12u, w & 0xfu, 1);
 }
 
-#ifndef SVT_VOTE2
-#define SVT_VOTE2 0              // 1: a window's two vote passes in two lanes (parity-green, no faster: profiles/r06_AA)
-#endif
 #ifndef SVT_DIAG
 #define SVT_DIAG 0               // diagnostic builds only (wrong results): 1 = region query only, 3 = no refine_end
                                  // stop search, 4 = no sort/vote, 5 = sort + prefix sums, no vote, ...,
@@ -1076,6 +1073,18 @@ constexpr int WPB = 4;
 #define SVT_REFINE_WAVES 8
 #endif
 #define SVT_OCC __attribute__((amdgpu_waves_per_eu(SVT_REFINE_WAVES, SVT_REFINE_WAVES)))
+// refine_lane_kernel at 64 windows per wave: the windows per round of its phases 0-1 and the waves
+// per SIMD its LDS allows (LaneLds<64, 32>: 5 632 B a wave, 7 workgroups a CU; <64, 64>: 6 400 B, 6).
+#ifndef SVT_WIDE_R
+#define SVT_WIDE_R 32
+#endif
+#ifndef SVT_WIDE_OCC
+#define SVT_WIDE_OCC (SVT_WIDE_R == 32 ? 7 : 6)
+#endif
+// Windows a launch needs for 64 per wave (svt_ctx::launch): the 250K-window launch of a 125K-locus
+// shard is the smallest measured, and 64 per wave wins there (0.118 vs 0.127 ms a step at 32,
+// profiles/e0260); smaller launches keep 32 per wave.
+constexpr size_t LANE_WIDE_MIN = 250000;
 template <bool COUNT, int G>
 __device__ __forceinline__ void refine_body(const KArgs &a);
 
@@ -1184,8 +1193,10 @@ __device__ __forceinline__ void refine_body(const KArgs &a) {
 // instead of a wave-wide network and per-lane searches for every window.  Phase 3: the
 // other windows (band off, > LV_CAP band elements, > CAP candidates) are re-gathered and
 // voted wave-wide (refine_window), as refine_span_kernel does.  Same results.
-// windows per wave (<= 64: one lane each in phase 2): 32, or 8 for batches too small to fill
-// the chip with 32 per wave (svt_ctx::launch)
+// Windows per wave (<= 64: one lane each in phase 2): 64, so that the sort network and the
+// vote's loops issue with every lane at work -- taken through phases 0-1 in two rounds of 32,
+// which keeps the win table and so the wave's LDS small (7 waves per SIMD) -- or 32 for
+// launches too small to fill the chip with 64 per wave (svt_ctx::launch).
 constexpr int LV_CAP = 32;   // band elements a lane votes on
 constexpr int LV_S = 34;     // u16 per staged row (17 words: odd -> no bank conflicts)
 static_assert(LV_S > LV_CAP, "a staged row needs a spare slot past LV_CAP");
@@ -1194,12 +1205,8 @@ static_assert(LV_S > LV_CAP, "a staged row needs a spare slot past LV_CAP");
 constexpr uint32_t LV_PENDING = 1u << 8, LV_BELOW = 1u << 9, LV_ABOVE = 1u << 10,
                    LV_REDO = 1u << 13;
 
-struct LvMeta {
-    int32_t lo;       // the band's low end (pos - w, w = range + max(ci, 0))
-    uint32_t liw;     // li << 1 | w
-    uint32_t flags;   // nb | LV_* bits
-    int32_t n;        // candidates (min_count test)
-};
+// A window's flags word (LaneLds::flags): nb | LV_* bits.  It is the only per-window fact another
+// lane writes in phase 1; the band's low end stays in the owning lane's registers.
 constexpr uint32_t LV_NONE = 1u << 14;   // no window (INV / other types): NA
 // diagnostic build 11: why a window left the lane path (bits 16+), reported as its result
 #if SVT_DIAG == 11
@@ -1211,20 +1218,29 @@ constexpr uint32_t LV_NONE = 1u << 14;   // no window (INV / other types): NA
 // Phase 1's packed walk: the windows with a span to walk, in wave order, one entry
 // each (written by their phase-0 lanes); consecutive windows of <= 64 events together share
 // one 64-event slot.
-struct alignas(16) LvWin {
+// (24 B: the band's low end is not kept -- lv_lo gives it back from s and the kind -- so that
+// the wide kernel's LDS leaves room for 6-7 waves per SIMD.)
+constexpr uint32_t LVW_BELOW = 1u << 16;
+struct alignas(8) LvWin {
     uint64_t e0;    // the span's first event
     uint32_t s, e;  // the window
-    int32_t lo;     // the band's low end
-    uint32_t kl;    // kind | the window's lane (row) << 8
+    uint32_t kl;    // kind | the window's row << 8 | LVW_BELOW (value buckets: the prefix maxima below
+                    // the band's buckets hold a candidate)
     uint32_t len;   // span events (> 0)
-    uint32_t pad;   // value buckets: LV_BELOW when the prefix maxima below the band's buckets hold a candidate
 };
+// The band's low end pos - (range + max(ci, 0)) from the window's start: s = pos - wider / median /
+// narrow in uint32 (window_of), so s + that width is pos again, bit for bit.
+__device__ __forceinline__ int32_t lv_lo(const KParams &k, uint32_t kind, uint32_t s, int32_t bw) {
+    const int32_t d = kind == (uint32_t)K_INS ? k.median : kind == (uint32_t)K_START ? k.wider : k.narrow;
+    return (int32_t)(s + (uint32_t)d) - bw;
+}
 
-template <int W>
+// W rows for phase 2 (one lane each), R windows per round of phases 0-1 (the win table is per round).
+template <int W, int R>
 struct LaneLds {
-    uint16_t stage[W * LV_S];   // parked queries (phase 0 -> 1), band offsets (1 -> 2)
-    LvMeta meta[W];
-    LvWin win[W];
+    uint16_t stage[W * LV_S];   // band offsets (phase 1 -> 2)
+    uint32_t flags[W];
+    LvWin win[R];
     uint32_t sink[WAVE];        // lane_walk: the store target of lanes without a band member
 };
 
@@ -1405,8 +1421,8 @@ __device__ __forceinline__ void lane_walk2(const LwOne &A, const LwOne &B, uint1
 // M marks the first lane of a window (bit 0 always), tot <= 64 events in all.  Lane j walks
 // event j - f of the window that starts at f = the highest mark <= j, with that window's own
 // s / e / band (the tests of span_cand_mask, per lane); members go to the window's row at
-// their rank among its members, and each window's first lane writes its meta row (band size,
-// candidates, below / above) -- everything lane_walk gives a window, for 1-64 events at once.
+// their rank among its members, and each window's first lane writes its flags word (band size,
+// below / above) -- everything lane_walk gives a window, for 1-64 events at once.
 // The event lane ln tests in the packed slot of windows win[c0..] with marks M (value buckets: one
 // event array) -- loaded ahead of the slot's tests so that a run of packed slots keeps the next
 // slot's loads in flight while the current one is tested.
@@ -1419,18 +1435,18 @@ __device__ __forceinline__ uint4 lane_packed_load(const BkIndex &B, const LvWin 
 }
 
 template <bool BK>
-__device__ __forceinline__ void lane_packed(const DevPileup &P, const BkIndex &B, const LvWin *win, LvMeta *meta,
-                                            uint16_t *stage, uint32_t c0, uint64_t M, uint32_t tot, int32_t bw2,
-                                            const uint4 *vpre = nullptr) {
+__device__ __forceinline__ void lane_packed(const DevPileup &P, const BkIndex &B, const KParams &prm, const LvWin *win,
+                                            uint32_t *flags, uint16_t *stage, uint32_t c0, uint64_t M, uint32_t tot,
+                                            int32_t bw2, const uint4 *vpre = nullptr) {
     const int ln = lane_id();
     const uint64_t upto = M & ((2ull << ln) - 1ull);   // marks at or below this lane (ln 63: all)
     const uint32_t r = (uint32_t)__popcll(upto) - 1u, f = 63u - (uint32_t)__clzll(upto);
     const LvWin w = win[c0 + r];
-    const uint32_t kind = w.kl & 0xffu, k = w.kl >> 8;
+    const uint32_t kind = w.kl & 0xffu, k = (w.kl >> 8) & 0xffu;
     const uint4 *evb = (BK ? B.ev : kind == (uint32_t)K_INS ? P.spI : P.spD) + w.e0;
     const uint4 v = vpre ? *vpre : evb[min((uint32_t)ln - f, w.len - 1u)];   // lanes past tot: their window's last event
     const uint32_t s = w.s, e = w.e, x = v.x, op = v.y & 0xfu;
-    const int32_t lo = w.lo;
+    const int32_t lo = lv_lo(prm, kind, s, bw2 >> 1);
     const uint64_t isI = ballot(kind == (uint32_t)K_INS), isE = ballot(kind == (uint32_t)K_END);
     const uint64_t oD = ballot(op == OP_DEL), sx = ballot(s <= x), oL = ballot(op == SP_LEAD);
     const uint64_t ovl = ballot((int32_t)v.z > (int32_t)(s - 1u));
@@ -1453,9 +1469,9 @@ __device__ __forceinline__ void lane_packed(const DevPileup &P, const BkIndex &B
         const uint64_t rm = (w.len >= 64u ? ~0ull : ((1ull << w.len) - 1ull)) << ln;
         const uint32_t nb = (uint32_t)__popcll(mb & rm);
         const bool below = (cm & ~gt & rm) != 0ull, above = ((brk | (cm & ~lt)) & rm) != 0ull;
-        meta[k].flags = nb > (uint32_t)LV_CAP ? (LV_REDO | LV_WHY(3))
-                                              : nb | LV_PENDING | (below ? LV_BELOW : 0u) | (above ? LV_ABOVE : 0u) | w.pad;
-        meta[k].n = 0;
+        flags[k] = nb > (uint32_t)LV_CAP ? (LV_REDO | LV_WHY(3))
+                                         : nb | LV_PENDING | (below || (w.kl & LVW_BELOW) ? LV_BELOW : 0u) |
+                                               (above ? LV_ABOVE : 0u);
     }
 }
 
@@ -1559,54 +1575,6 @@ __device__ __forceinline__ int32_t lane_vote(const uint16_t *B, int32_t nb, int3
         }
     }
     return distL < distR ? valL : valR;                                      // :100
-}
-
-// One of lane_vote's two passes (right: the pass above pos - 25, refinement.c:78-98; else the
-// pass below pos + 25, :56-76), written once for both directions so that the two passes of a
-// window run in two lanes of one wave at once: i walks from the pass's start in direction dir,
-// and the cluster's far end f moves the same way while its next element lies within ci of
-// B[i].  Returns whether the pass returned early (val = that value); otherwise val / dist are
-// the pass's best (-1 / INT_MAX: none).
-__device__ __forceinline__ bool lane_vote_half(const uint16_t *B, int32_t nb, int32_t w, int32_t lo, uint32_t fl,
-                                               const KParams &k, int32_t l0, bool right, int32_t &val, int32_t &dist) {
-    const int32_t ci = k.ci, range = k.range;
-    const bool below = fl & LV_BELOW, above = fl & LV_ABOVE;
-    int32_t start;
-    if (!right) {
-        const bool u0 = !below && l0 == 0;
-        start = nb == 0 ? -1 : u0 ? 0 : l0 == 0 ? -1 : l0 - 1;
-    } else {
-        const bool lt = below || (nb > 0 && (int32_t)B[0] < w - SV_MIN_LENGTH / 2);
-        start = lt ? (!below ? 0 : nb) : (!above ? nb - 1 : nb);
-    }
-    const int32_t dir = right ? 1 : -1;
-    int32_t mx = k.min_count - 1, f = start - dir, prev = 0;
-    uint32_t S = 0;
-    val = -1;
-    dist = 0x7fffffff;
-    for (int32_t i = start; i >= 0 && i < nb; i += dir) {
-        const int32_t a = B[i];
-        if (ref_abs(w - a) >= range) break;
-        if (i != start) S -= (uint32_t)prev;                     // the element behind i leaves
-        if ((f - i) * dir < 0) { f = i; S = (uint32_t)a; }
-        for (;;) {                                               // :61-64 / :83-86
-            const int32_t g = f + dir;
-            if (g < 0 || g >= nb) break;
-            const int32_t b = B[g];
-            if ((b - a) * dir > ci) break;
-            f = g;
-            S += (uint32_t)b;
-        }
-        prev = a;
-        const int32_t c = (f - i) * dir + 1;
-        if (c > mx) {                                            // :67-76 / :88-97
-            const int32_t co = (int32_t)div_small(S + (uint32_t)(c / 2), (uint32_t)c);
-            const int32_t d = ref_abs(w - co);
-            if (d < ci) { val = lo + co; return true; }
-            if (d < dist) { mx = c; val = lo + co; dist = d; }
-        }
-    }
-    return false;
 }
 
 // A2 (audit.c:176-225) for window g: kind (-1: none -> NA), s, e, pos of the vote.
@@ -1742,43 +1710,55 @@ __device__ unsigned long long ph_prof[16];
 #define PH(...)
 #define PH_T(t)
 #endif
-template <int LV_W, bool BK>
-__global__ __launch_bounds__(64 * WPB) SVT_OCC void refine_lane_kernel(KArgs a) {
-    __shared__ LaneLds<LV_W> lds_all[WPB];
+// LV_W windows per wave (phase 2: one lane each, so <= 64), taken through phases 0-1 LV_R at a
+// time (LV_R == LV_W: one round); OCC waves per SIMD (what the workgroup's LDS allows).
+template <int LV_W, int LV_R, int OCC, bool BK>
+__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void refine_lane_kernel(KArgs a) {
+    static_assert(LV_W <= WAVE && LV_W % LV_R == 0, "one lane per window in phase 2, whole rounds");
+    __shared__ LaneLds<LV_W, LV_R> lds_all[WPB];
     const uint32_t wid = threadIdx.x >> 6;
     const int ln = lane_id();
     const uint32_t g0 = (blockIdx.x * WPB + wid) * LV_W, nw = 2u * a.n;
     if (g0 >= nw) return;
-    LaneLds<LV_W> &L = lds_all[wid];
+    LaneLds<LV_W, LV_R> &L = lds_all[wid];
     const KParams &k = a.prm;
     const uint32_t cnt = min((uint32_t)LV_W, nw - g0);
     const int32_t bw = k.range + max(k.ci, 0);   // the band's half-width
-    PH_T(pt0);
+    PH(long long ph_t0 = 0, ph_t1 = 0;)
     const bool band_ok = k.range > SV_MIN_LENGTH / 2 && bw <= LV_WMAX && k.ci >= -LV_WMAX &&
                          SVT_DIAG != 7;
+    // Window g0 + l is lane l's in phase 2: its row, its flags word, and (in registers) its band's
+    // low end; in a round of phases 0-1 it is lane l - r0's.
+    uint32_t aflags = 0;   // phase 1: the flags of a window walked alone, in its phase-2 lane
+    int32_t mylo = 0;
+#pragma nounroll
+    for (uint32_t r0 = 0; r0 < cnt; r0 += (uint32_t)LV_R) {
+    PH_T(pt0);
     // ---- phase 0: every window's A2 + A3 at once, one lane each (the dependent loads of
-    // locus -> bucket words -> pos/emax searches -> span bounds run once per LV_W windows).
-    // The meta row gets its final flags here unless the window has a span to walk, and the
-    // walkable windows' table entries go to win[] in lane order.
+    // locus -> bucket words -> pos/emax searches -> span bounds run once per LV_R windows).
+    // The flags word is final here unless the window has a span to walk, and the walkable
+    // windows' table entries go to win[] in lane order.
     uint32_t nwin;
     {
-        const bool mine = (uint32_t)ln < cnt;
+        const bool mine = (uint32_t)ln < min((uint32_t)LV_R, cnt - r0);
+        const uint32_t row = r0 + (uint32_t)ln;
         LvQuery q{};
         if (mine) {
-            if (BK) lane_query_bk(a, g0 + (uint32_t)ln, q);
-            else lane_query(a, g0 + (uint32_t)ln, band_ok, q);
+            if (BK) lane_query_bk(a, g0 + row, q);
+            else lane_query(a, g0 + row, band_ok, q);
         }
         const bool walk = mine && q.kind >= 0 && !(q.kind & LQ_REDO) && q.len != 0u;
         if (mine) {
-            uint32_t *row32 = reinterpret_cast<uint32_t *>(L.stage + (uint32_t)ln * LV_S);
+            uint32_t *row32 = reinterpret_cast<uint32_t *>(L.stage + row * LV_S);
 #pragma unroll
             for (int j = 0; j < LV_CAP / 2; j++) row32[j] = 0xffffffffu;   // unused band slots read as 0xffff
-            LvMeta m;
-            m.lo = q.lo;
-            m.liw = q.liw;
-            m.flags = q.kind < 0 ? LV_NONE : (q.kind & LQ_REDO) ? (LV_REDO | LV_WHY(1)) : LV_PENDING;
-            m.n = 0;
-            L.meta[ln] = m;
+            L.flags[row] = q.kind < 0 ? LV_NONE : (q.kind & LQ_REDO) ? (LV_REDO | LV_WHY(1)) : LV_PENDING;
+        }
+        if constexpr (LV_R < LV_W) {   // the band's low end moves to the window's phase-2 lane
+            const int32_t t = __shfl(q.lo, ln & (LV_R - 1), WAVE);
+            if (((uint32_t)ln & ~(uint32_t)(LV_R - 1)) == r0) mylo = t;
+        } else {
+            mylo = q.lo;
         }
         const uint64_t wm = ballot(walk);
         if (walk) {
@@ -1786,36 +1766,36 @@ __global__ __launch_bounds__(64 * WPB) SVT_OCC void refine_lane_kernel(KArgs a) 
             wn.e0 = (uint64_t)q.e0[0] | (uint64_t)q.e0[1] << 32;
             wn.s = q.s;
             wn.e = q.e;
-            wn.lo = q.lo;
-            wn.kl = (uint32_t)q.kind | (uint32_t)ln << 8;
+            wn.kl = (uint32_t)q.kind | row << 8 | (q.fl ? LVW_BELOW : 0u);
             wn.len = q.len;
-            wn.pad = q.fl;
             L.win[mbcnt(wm)] = wn;
         }
         nwin = (uint32_t)__popcll(wm);
     }
     wave_sync();
     PH_T(pt1);
+    PH(ph_t0 += pt1 - pt0;)
     if (SVT_DIAG == 6) {   // diagnostic build: phase 0 only (its answers written out, so it is not dead code)
-        if ((uint32_t)ln < cnt) {
-            const LvMeta mt = L.meta[ln];
+        const uint32_t g = g0 + r0 + (uint32_t)ln;
+        if (g < g0 + cnt && (uint32_t)ln < (uint32_t)LV_R) {
             const LvWin wn = L.win[min((uint32_t)ln, nwin > 0 ? nwin - 1 : 0u)];
-            write_result(a, mt.liw >> 1, mt.liw & 1u, mt.flags ^ (uint32_t)wn.e0 ^ wn.len);
+            write_result(a, g >= a.n ? g - a.n : g, g >= a.n ? 1u : 0u, L.flags[r0 + (uint32_t)ln] ^ (uint32_t)wn.e0 ^ wn.len);
         }
-        return;
+        wave_sync();
+        continue;
     }
     // ---- phase 1 (packed): windows of <= 64 events share slots (lane_packed), longer ones are
     // walked alone (lane_walk).  Lane c holds walkable window c's walk constants, computed here
     // once for the wave; the scalar window loop reads them with v_readlane (no LDS round trip and
     // no scalar arithmetic per window), and a window walked alone leaves its flags in lane kw of
-    // aflags (a v_cndmask on the lane index) instead of a store to its meta row.
-    uint32_t aflags = 0;
+    // aflags (a v_cndmask on the lane index) instead of a store to its flags word.
     {
         const bool has = (uint32_t)ln < nwin;
         const LvWin wv = L.win[has ? (uint32_t)ln : 0u];   // (entry 0 unused when nwin == 0)
-        const uint32_t lenv = has ? wv.len : 0u, klv = wv.kl, ev = wv.e, flv = wv.pad;
+        const uint32_t lenv = has ? wv.len : 0u, klv = wv.kl & 0xffffu, ev = wv.e;
+        const uint32_t flv = wv.kl & LVW_BELOW ? LV_BELOW : 0u;
         const int32_t em2v = (int32_t)(wv.e - 2u);
-        const int32_t lov = wv.lo;
+        const int32_t lov = lv_lo(k, klv & 0xffu, wv.s, bw);
         const int32_t b1v = max((int32_t)(wv.s - 1u), -(1 << 30)) + 1;
         const int32_t scv = (int32_t)min(wv.s, 0x7fffffffu);
         const uint64_t addrv = reinterpret_cast<uint64_t>(
@@ -1877,7 +1857,7 @@ __global__ __launch_bounds__(64 * WPB) SVT_OCC void refine_lane_kernel(KArgs a) 
                 tot += l;
             }
             if (!BK) {
-                lane_packed<BK>(a.pile, a.bk, L.win, L.meta, L.stage, c, M, tot, bw2);
+                lane_packed<BK>(a.pile, a.bk, k, L.win, L.flags, L.stage, c, M, tot, bw2);
                 c = c1;
                 continue;
             }
@@ -1900,7 +1880,7 @@ __global__ __launch_bounds__(64 * WPB) SVT_OCC void refine_lane_kernel(KArgs a) 
                 }
                 // (unconditional: a load under a branch would be waited for at the join)
                 const uint4 vn = lane_packed_load(a.bk, L.win, more ? c1 : c, more ? Mn : M);
-                lane_packed<BK>(a.pile, a.bk, L.win, L.meta, L.stage, c, M, tot, bw2, &v);
+                lane_packed<BK>(a.pile, a.bk, k, L.win, L.flags, L.stage, c, M, tot, bw2, &v);
                 c = c1;
                 if (!more) break;
                 v = vn;
@@ -1911,9 +1891,18 @@ __global__ __launch_bounds__(64 * WPB) SVT_OCC void refine_lane_kernel(KArgs a) 
         }
         wave_sync();
     }
+    PH(ph_t1 += wall_clock64() - pt1;)
+    }   // (the round)
+    if (SVT_DIAG == 6) return;
     PH_T(pt2);
     const bool mine = (uint32_t)ln < cnt;
-    LvMeta mt = mine ? L.meta[ln] : LvMeta{0, 0, 0, 0};
+    struct { int32_t lo; uint32_t liw, flags; } mt;   // the window's facts, in its own lane
+    {
+        const uint32_t g = g0 + (uint32_t)ln, w = g >= a.n ? 1u : 0u;
+        mt.lo = mylo;
+        mt.liw = (g - w * a.n) << 1 | w;
+        mt.flags = mine ? L.flags[ln] : 0u;
+    }
     if (aflags) mt.flags = aflags;   // the window was walked alone
     if (SVT_DIAG == 8) {   // diagnostic build: phases 0-1 only (a checksum of their LDS output written out)
         if (mine) {
@@ -1925,7 +1914,7 @@ __global__ __launch_bounds__(64 * WPB) SVT_OCC void refine_lane_kernel(KArgs a) 
         return;
     }
     // ---- phase 2: one lane per staged window
-    uint64_t redo;   // phase 3's windows (the meta rows are overwritten by its gathers)
+    uint64_t redo;   // the windows left over for refine_redo_kernel
     {
         // decisions: no window or fewer than min_count band members -> NA (refinement.c:43-45,
         // LaneBand); the wave-wide path; or this lane's vote
@@ -1987,22 +1976,6 @@ __global__ __launch_bounds__(64 * WPB) SVT_OCC void refine_lane_kernel(KArgs a) 
             }
             if (SVT_DIAG == 42 || SVT_DIAG == 43) {   // diagnostic builds: no vote (42), no vote or ABOVE walks (43)
                 if (pend) write_result(a, mt.liw >> 1, mt.liw & 1u, x[0] + (uint32_t)l0 + (uint32_t)needA);
-            } else if (SVT_VOTE2 && LV_W <= 32) {
-                // the two passes of window j in lanes j (below pos + 25) and j + 32 (above pos - 25)
-                const int src = ln & 31;
-                const bool right = ln >= 32;
-                const bool pv = __shfl((int)pend, src, WAVE) != 0;
-                const int32_t nbv = __shfl(nb, src, WAVE), lov = __shfl(mt.lo, src, WAVE), l0v = __shfl(l0, src, WAVE);
-                const uint32_t flv = (uint32_t)__shfl((int)mt.flags, src, WAVE);
-                int32_t val = -1, dist = 0x7fffffff;
-                bool early = false;
-                if (pv) early = lane_vote_half(L.stage + (uint32_t)src * LV_S, nbv, bw, lov, flv, k, l0v, right, val, dist);
-                const int32_t valR = __shfl(val, src + 32, WAVE), distR = __shfl(dist, src + 32, WAVE);
-                const bool earlyR = __shfl((int)early, src + 32, WAVE) != 0;
-                if (pend) {   // :100 after an early return of neither pass
-                    const int32_t r = early ? val : earlyR ? valR : dist < distR ? val : valR;
-                    write_result(a, mt.liw >> 1, mt.liw & 1u, (uint32_t)r);
-                }
             } else if (pend) {
                 const int32_t r = lane_vote(row, nb, bw, mt.lo, mt.flags, k, l0);
                 write_result(a, mt.liw >> 1, mt.liw & 1u, (uint32_t)r);
@@ -2026,7 +1999,7 @@ __global__ __launch_bounds__(64 * WPB) SVT_OCC void refine_lane_kernel(KArgs a) 
         base = rdlane(base, 0);
         if ((redo >> ln) & 1ull) a.redo_list[base + mbcnt(redo)] = g0 + (uint32_t)ln;
     }
-    PH(if (ln == 0) { const long long pt4 = wall_clock64(); PH_ADD(0, pt1 - pt0); PH_ADD(1, pt2 - pt1); PH_ADD(2, pt3 - pt2); PH_ADD(3, pt4 - pt3); PH_ADD(4, 1); })
+    PH(if (ln == 0) { const long long pt4 = wall_clock64(); PH_ADD(0, ph_t0); PH_ADD(1, ph_t1); PH_ADD(2, pt3 - pt2); PH_ADD(3, pt4 - pt3); PH_ADD(4, 1); })
 }
 
 // The lane kernel's left-over windows (band off, > LV_CAP band elements, > CAP candidates,
@@ -2108,6 +2081,7 @@ struct svt_ctx {
     uint64_t ix_ranges = 32768;   // index ranges per pileup (SVTREK_IX_RANGES, A/B): ~n_ops / this ops each,
                                   // at most IX_TMAX ops (and IX_RCAP reads) a range
     int lane_w = 0;               // SVTREK_LANE_W=32 forces the lane kernel at every batch size (tests)
+    int lane_wide = -1;           // SVTREK_LANE_WIDE=0 / 1: 32 / 64 windows a wave at every size (-1: by window count)
     uint32_t *d_redo = nullptr;   // lane-vote launches: left-over window list
     size_t redo_cap = 0;
     uint32_t lane_par = 0;        // which of the two redo counters the next lane launch uses
@@ -2343,7 +2317,7 @@ svt_status launch(svt_ctx *c, const svt_locus *d_loci, svt_result *d_out, size_t
     if (count) {
         hipLaunchKernelGGL((refine_kernel<true, G_SPAN>), grid, block, 0, st, a);
     } else if (c->lane_vote && (c->lane_w != 0 || 2 * n >= (size_t)65536)) {
-        // lane kernel (32 windows a wave) once the batch has >= 64K windows; below that the
+        // lane kernel (32 or 64 windows a wave) once the batch has >= 64K windows; below that the
         // one-wave-per-window span kernel is as fast or faster (fewer, longer waves leave the
         // chip underfilled: cfg2 20K windows 33 us span vs 76 us lane<8>, 107 us lane<32>;
         // cfg3 100K windows 111 vs 109 us; cfg4 2M windows 2.23 ms vs 0.905 ms)
@@ -2373,9 +2347,18 @@ svt_status launch(svt_ctx *c, const svt_locus *d_loci, svt_result *d_out, size_t
         }
         // (16 windows a wave for the 250K-window launches of a 125K-locus shard measured slower:
         // 0.132-0.138 vs 0.117-0.121 ms, profiles/r04_sh)
-        const dim3 lgrid((unsigned)((2 * n + WPB * 32 - 1) / (WPB * 32)));
-        if (c->bk_ready) hipLaunchKernelGGL((refine_lane_kernel<32, true>), lgrid, block, 0, st, a);
-        else hipLaunchKernelGGL((refine_lane_kernel<32, false>), lgrid, block, 0, st, a);
+        // 64 windows a wave (phase 2 on every lane) once the launch still fills the chip with them,
+        // and whenever the lane kernel is forced; SVTREK_LANE_WIDE=0 / 1 overrides (A/B, tests)
+        const bool wide = c->lane_wide >= 0 ? c->lane_wide != 0 : (c->lane_w != 0 || 2 * n >= LANE_WIDE_MIN);
+        const unsigned per = WPB * (wide ? 64u : 32u);
+        const dim3 lgrid((unsigned)((2 * n + per - 1) / per));
+        if (wide) {
+            if (c->bk_ready) hipLaunchKernelGGL((refine_lane_kernel<64, SVT_WIDE_R, SVT_WIDE_OCC, true>), lgrid, block, 0, st, a);
+            else hipLaunchKernelGGL((refine_lane_kernel<64, SVT_WIDE_R, SVT_WIDE_OCC, false>), lgrid, block, 0, st, a);
+        } else {
+            if (c->bk_ready) hipLaunchKernelGGL((refine_lane_kernel<32, 32, SVT_REFINE_WAVES, true>), lgrid, block, 0, st, a);
+            else hipLaunchKernelGGL((refine_lane_kernel<32, 32, SVT_REFINE_WAVES, false>), lgrid, block, 0, st, a);
+        }
         hipLaunchKernelGGL(refine_redo_kernel, dim3(8192), block, 0, st, a);   // ~1 left-over window per wave
     } else {
         hipLaunchKernelGGL(refine_span_kernel, grid, block, 0, st, a);
@@ -2566,6 +2549,7 @@ svt_status svt_open(const svt_params *params, int device, svt_ctx **out) {
     if (const char *x = getenv("SVTREK_IX")) c->ix_mode = strcmp(x, "lane") == 0 ? 1 : strcmp(x, "stream") == 0 ? 2 : 0;
     if (const char *x = getenv("SVTREK_IX_RANGES")) c->ix_ranges = std::max<uint64_t>(1, strtoull(x, nullptr, 10));
     if (const char *lw = getenv("SVTREK_LANE_W")) c->lane_w = atoi(lw) == 32 ? 32 : 0;
+    if (const char *lw = getenv("SVTREK_LANE_WIDE")) c->lane_wide = atoi(lw) != 0 ? 1 : 0;
     if (const char *x = getenv("SVTREK_INDEX")) c->bk_on = strcmp(x, "lists") != 0;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
