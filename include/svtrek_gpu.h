@@ -295,8 +295,8 @@ typedef struct svt_load_stats {
     uint64_t index_kind;    /* the index build used: 1 lane per read, 2 stream walk              */
     /* the value-bucketed event index (0.24, DESIGN.md "Value buckets"): every candidate event
      * filed by its candidate value in 1 kb buckets, per window kind -- the refine kernels read a
-     * window's band from it, svt_reindex rebuilds it (and, with long reads, the span lists it is
-     * filed from).  0 everywhere with SVTREK_INDEX=lists (the span lists alone, rounds 1-5). */
+     * window's band from it, svt_reindex rebuilds it (the span lists stay as built at load).
+     * 0 everywhere with SVTREK_INDEX=lists (the span lists alone, rounds 1-5). */
     uint64_t bucket_index;  /* 1: on                                                              */
     uint64_t buckets;       /* buckets per event array (every contig's, incl. its overflow bucket) */
     uint64_t bucket_events; /* events filed per rebuild (a D > 50 op twice: by start and by end)   */
@@ -310,8 +310,10 @@ typedef struct svt_load_stats {
 svt_status svt_last_load_stats(const svt_ctx *ctx, svt_load_stats *out);
 
 /* Rebuild the device index from the resident pileup on `hip_stream` (asynchronous, ordered
- * after every launch of the context already issued): the same two kernels svt_load_pileup
- * runs, no host work and no transfers.  Results of later refines are unchanged; bench.py
+ * after every launch of the context already issued), no host work and no transfers.  With the
+ * value buckets on it refiles them -- ixb_lane_kernel for short reads, index_kernel +
+ * ixb_copy_kernel for long reads -- and the span lists stay as built at load; with
+ * SVTREK_INDEX=lists it rebuilds the span lists.  Results of later refines are unchanged; bench.py
  * times it as part of every step so that the step covers the whole per-read walk. */
 svt_status svt_reindex(svt_ctx *ctx, void *hip_stream);
 

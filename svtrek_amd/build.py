@@ -37,13 +37,17 @@ def _stale(out: str, deps: list[str]) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _engine_deps() -> list[str]:
+    """The engine's one translation unit first, then everything it includes: every csrc/*.inc,
+    svt_bamrec.h and the two public headers."""
+    incs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".inc"))
+    return [os.path.join(CSRC, "svt_engine.hip")] + incs + \
+        [os.path.join(CSRC, "svt_bamrec.h"), os.path.join(INC, "svtrek_gpu.h"), os.path.join(INC, "svtrek_evidence.h")]
+
+
 def build_engine(force: bool = False) -> str:
     out = os.path.join(PKG, "libsvtrek_hip.so")
-    deps = [os.path.join(CSRC, "svt_engine.hip"), os.path.join(INC, "svtrek_gpu.h"), os.path.join(CSRC, "svt_poa.inc"),
-            os.path.join(CSRC, "svt_index.inc"), os.path.join(CSRC, "svt_index2.inc"),
-            os.path.join(CSRC, "svt_inflate.inc"), os.path.join(CSRC, "svt_bamrec.h"), os.path.join(CSRC, "svt_bam.inc"),
-            os.path.join(CSRC, "svt_bucket.inc"), os.path.join(CSRC, "svt_bucket_build.inc"),
-            os.path.join(CSRC, "svt_evidence.inc"), os.path.join(INC, "svtrek_evidence.h")]
+    deps = _engine_deps()
     if force or _stale(out, deps):
         _run([HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared",
               "-Wall", "-I", INC, "-o", out, deps[0]])
@@ -54,11 +58,7 @@ def build_test_engine(force: bool = False) -> str:
     """Test artefact: the engine with a 2-row POA ring (svt_poa.inc SVT_POA_RING), so nearly
     every predecessor is read from a spill row -- tests/test_gpu_poa.py runs parity on it."""
     out = os.path.join(PKG, "variants", "libsvtrek_hip_ring2.so")
-    deps = [os.path.join(CSRC, "svt_engine.hip"), os.path.join(INC, "svtrek_gpu.h"), os.path.join(CSRC, "svt_poa.inc"),
-            os.path.join(CSRC, "svt_index.inc"), os.path.join(CSRC, "svt_index2.inc"),
-            os.path.join(CSRC, "svt_inflate.inc"), os.path.join(CSRC, "svt_bamrec.h"), os.path.join(CSRC, "svt_bam.inc"),
-            os.path.join(CSRC, "svt_bucket.inc"), os.path.join(CSRC, "svt_bucket_build.inc"),
-            os.path.join(CSRC, "svt_evidence.inc"), os.path.join(INC, "svtrek_evidence.h")]
+    deps = _engine_deps()
     if force or _stale(out, deps):
         os.makedirs(os.path.dirname(out), exist_ok=True)
         _run([HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-DSVT_POA_RING=2",

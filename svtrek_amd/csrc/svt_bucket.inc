@@ -1,5 +1,5 @@
-// svt_bucket.inc -- the value-bucketed event index, refine side (included by svt_engine.hip before
-// the refine kernels; the build kernels are in svt_bucket_build.inc).
+// svt_bucket.inc -- the value-bucketed event index, refine side (included by svt_engine.hip between
+// svt_vote.inc and svt_refine.inc; the build kernels are in svt_bucket_build.inc).
 //
 // Why (VERDICT r05, item 1): a window's candidates that matter to consensus_pos
 // (refinement.c:41-101) are its exact band -- values in (pos - w, pos + w), w = range + max(ci, 0)
@@ -29,8 +29,9 @@
 //     refine_end [hi, e + 1], then the leading-S reads starting in [s, e - 2] whose walk passes e
 //     (L) and the D ops spanning e (S, from e - longest D > 50 of the contig).
 // The per-window work is a fixed number of table reads plus the band's events; exactness is the
-// oracle's (tests/test_gpu_parity.py, tests/test_gpu_bucket.py), the design was checked against the
-// oracle on cfg2/cfg3/cfg4 and fuzzed pileups before this code existed (DESIGN.md "Value buckets").
+// oracle's (tests/test_gpu_parity.py, tests/test_gpu_lane_wide.py, tests/test_bucket_model.py), the
+// design was checked against the oracle on cfg2/cfg3/cfg4 and fuzzed pileups before this code
+// existed (DESIGN.md "Value buckets").
 __device__ __forceinline__ int bk_array(int kind) { return kind == K_START ? BA_S : kind == K_END ? BA_E : BA_I; }
 
 // Window [s, e] of a lane-path kind, its band (lo, hi) = (imp - w, imp + w).

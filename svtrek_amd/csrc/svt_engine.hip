@@ -1,27 +1,35 @@
-// svt_engine.hip -- MI355X (gfx950) SV-refinement engine: HIP kernels + the C ABI of
-// include/svtrek_gpu.h.
+// svt_engine.hip -- MI355X (gfx950) SV-refinement engine: the one translation unit behind the C ABI of
+// include/svtrek_gpu.h.  This file holds the shared constants and kernel argument structs, the
+// context (svt_ctx), the launch logic and the core entry points; the device code and the host
+// halves of the side modes are in the .inc files it includes.
 //
-// One wavefront (one 64-lane workgroup) per query WINDOW (a DEL locus has two: the
-// refine_start and refine_end windows; an INS locus one).  Per window the wave
-//   1. finds the yielded read range [lo, hi) of htslib's region query (A3) with a
-//      bucket index (first read per 4 kb of contig) + one 64-lane probe each for the
-//      sorted pos[] and the prefix-max-of-endpos emax[] arrays;
-//   2. streams the window's CIGAR words -- the reads [lo, hi) own ONE contiguous span
-//      of the CIGAR arena -- in 1024-op tiles, four 16-B loads per lane (4 KiB per wave,
-//      fully coalesced, next tile prefetched while the current one is processed).  A segmented wave prefix scan (DPP) of the reference advance, reset at
-//      each read's first op to its pos, gives every op's walk position at once; because
-//      the walk position only grows inside a read, "this op comes after the break of
-//      refinement.c:141-144" is just `position before the op > inter.end`, so no second
-//      scan is needed.  Breakpoint candidates (A4-A6) and the soft-clip candidates of
-//      each read's stop op are appended to LDS with LDS atomics; tails of reads that
-//      already broke (and reads that do not overlap the window) are skipped;
-//   3. bitonic-sorts the candidates in LDS and runs consensus_pos's asymmetric vote
-//      (A8-A10): per-element cluster counts in parallel (binary search + int64 prefix
-//      sums), the greedy accept with scalar readlanes.
-// Windows with more than SVT_LDS_CANDS candidates re-run on a slab of a device spill
-// pool (exact).  Reads whose walk could wrap uint32 go through a per-read wave walk
-// (walk_read) that replays the reference's uint32 arithmetic op by op.  No floating
-// point, no MFMA: integer scan + vote, HBM-streaming bound.
+// What a refine step does.  A locus has one window (INS) or two (DEL: refine_start, refine_end); a
+// window's result is the reference's consensus_pos vote (refinement.c:41-101) over the breakpoint
+// candidates its reads yield.
+//   * At load, every candidate event of every read is filed once by the value it votes with, in
+//     1 kb value buckets per contig and window kind (BkIndex); the per-read span lists (DevPileup's
+//     spD / spI) are built beside them.
+//   * refine_lane_kernel, the default: a wave takes 32 or 64 windows, reads each window's exact
+//     vote band from its buckets, and votes one window per LANE (in-register sort, 16-bit offsets).
+//   * Windows the lane path cannot take (band off or too full, positions past 2^30, ...) go on a list
+//     for refine_redo_kernel: one wave per window, the buckets wave-wide, else the span-list
+//     fallback (span walk, wave-wide sort + vote, a device spill pool past SVT_LDS_CANDS candidates).
+//   * refine_span_kernel is that wave-per-window path for every window (small batches,
+//     SVTREK_GATHER=span1); refine_kernel<true> is its counting build (svt_count_work).
+// No floating point on the vote's values, no MFMA: integer filters and votes, bound by dependent loads.
+//
+// Which file holds what (in include order):
+//   svt_wave.inc          wave primitives: ballots, readlanes, DPP scans, lane_xor, the PH() hooks
+//   svt_gather.inc        candidate sink, region query, per-read replay, span walk, gather
+//   svt_vote.inc          register / LDS sorts, band filter, consensus_pos and sliding votes, vote_window
+//   svt_bucket.inc        the value buckets, refine side
+//   svt_refine.inc        the wave-per-window kernels: refine_kernel, refine_span_kernel,
+//                         refine_redo_kernel, sw_kernel, sw_reduce_kernel
+//   svt_lane.inc          refine_lane_kernel and its helpers
+//   svt_evidence.inc      read support, depth and value range per refined breakpoint
+//   svt_index.inc, svt_index2.inc, svt_bucket_build.inc   the index builds (span lists, value buckets)
+//   svt_poa.inc, svt_poa_host.inc      allele consensus (POA): kernels, slot pools and poa_run
+//   svt_bam.inc, svt_inflate.inc, svt_bam_host.inc   BGZF inflate and BAM decode: kernels, svt_bam_dec_*
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -138,7 +146,7 @@ struct KArgs {
     BkIndex bk;                 // the value-bucketed event index
 };
 
-// svt_work counter slots (refine_window's wk[], the context's work words)
+// svt_work counter slots (gather_window's wk[], the context's work words)
 constexpr int W_WINDOWS = 0, W_READS = 1, W_OPS = 2, W_CANDS = 3, W_SPILLED = 4, W_QUERIES = 5, W_PROBE = 6,
               W_RANGE = 7, W_LREADS = 8, W_LENTRIES = 9, W_STOPS = 10, W_STOPCH = 11, W_SQUERIES = 12,
               W_SPAN = 13, W_BQ = 14, W_BEV = 15, W_N = 16;
@@ -146,1929 +154,20 @@ constexpr size_t CTL_BYTES = 256;   // context control words: pool head, status,
 constexpr size_t CTL_REDO = 200;    // redo counters: two alternating (direct launches), one + scratch (captured)
 static_assert(16 + 8 * W_N <= CTL_REDO && CTL_REDO + 16 <= CTL_BYTES, "control block too small");
 
-// ------------------------------------------------------------------ wave primitives
-#define SVT_COLD __forceinline__   // (cold paths inlined: out-of-line calls measured slower)
-__device__ __forceinline__ int lane_id() { return (int)__lane_id(); }
-// The lane mask of p straight from its compare (no v_cndmask / v_cmp round trip through a VGPR).
-__device__ __forceinline__ uint64_t ballot(bool p) { return (uint64_t)__builtin_amdgcn_ballot_w64(p); }
-__device__ __forceinline__ uint32_t rdlane(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
-__device__ __forceinline__ int32_t rdlane_i(int32_t v, int l) { return __builtin_amdgcn_readlane(v, l); }
-__device__ __forceinline__ uint64_t rdlane64(uint64_t v, int l) {
-    uint32_t lo = rdlane((uint32_t)v, l), hi = rdlane((uint32_t)(v >> 32), l);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ int32_t uniform_i(int32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-// Every window is owned by ONE wave (several independent waves share a workgroup), so the
-// only ordering ever needed is between the lanes of a wave: a workgroup-scope
-// release/acquire pair around a wave barrier (no s_barrier across the workgroup).
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ uint32_t dpp(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWMASK, 0xf, false);
-}
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ int32_t dpp_i(int32_t v, int32_t identity) {
-    return __builtin_amdgcn_update_dpp(identity, v, CTRL, ROWMASK, 0xf, false);
-}
-// DPP controls (GFX9): row_shr:n = 0x110+n, wave_shr:1 = 0x138, row_bcast:15 = 0x142, row_bcast:31 = 0x143
-
-// Inclusive wave64 prefix sum (mod 2^32).
-__device__ __forceinline__ uint32_t wave_scan_add(uint32_t v) {
-    v += dpp<0x111, 0xf>(v);
-    v += dpp<0x112, 0xf>(v);
-    v += dpp<0x114, 0xf>(v);
-    v += dpp<0x118, 0xf>(v);
-    v += dpp<0x142, 0xa>(v);
-    v += dpp<0x143, 0xc>(v);
-    return v;
-}
-
-// Inclusive wave64 max scan (identity -1).
-__device__ __forceinline__ int32_t wave_scan_max(int32_t v) {
-    v = max(v, dpp_i<0x111, 0xf>(v, -1));
-    v = max(v, dpp_i<0x112, 0xf>(v, -1));
-    v = max(v, dpp_i<0x114, 0xf>(v, -1));
-    v = max(v, dpp_i<0x118, 0xf>(v, -1));
-    v = max(v, dpp_i<0x142, 0xa>(v, -1));
-    v = max(v, dpp_i<0x143, 0xc>(v, -1));
-    return v;
-}
-
-__device__ __forceinline__ int64_t wave_scan_add64(int64_t x) {
-    int l = lane_id();
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        int64_t y = __shfl_up(x, (unsigned)d, WAVE);
-        if (l >= d) x += y;
-    }
-    return x;
-}
-
-// First index in [l, h) whose key satisfies pred (pred monotone false..true), 64-ary.
-template <typename Pred>
-__device__ SVT_COLD int64_t wave_partition_point(int64_t l, int64_t h, Pred pred) {   // cold: > 64 reads per bucket
-    const int ln = lane_id();
-    while (h - l > WAVE) {
-        int64_t span = h - l;
-        int64_t p = l + ((int64_t)(ln + 1) * span) / (WAVE + 1);
-        uint64_t m = ballot(pred(p));
-        int k = m ? __builtin_ctzll(m) : WAVE;
-        int64_t nl = k == 0 ? l : l + ((int64_t)k * span) / (WAVE + 1) + 1;
-        int64_t nh = k == WAVE ? h : l + ((int64_t)(k + 1) * span) / (WAVE + 1) + 1;
-        l = nl;
-        h = nh < h ? nh : h;
-    }
-    int64_t p = l + ln;
-    uint64_t m = ballot(p < h && pred(p));
-    return m ? l + __builtin_ctzll(m) : h;
-}
-
-// ------------------------------------------------------------------ candidate sink
-// Candidates are appended with LDS atomics: their order is irrelevant (the multiset is
-// sorted before the vote) and they are rare next to the CIGAR ops streamed, so a lane
-// that finds one appends it on its own, under any divergence.
-struct Sink {
-    int32_t *buf;   // LDS or a global spill slab
-    int32_t cap;
-    int32_t *cnt;   // LDS counter: candidates seen (may exceed cap -> spill re-run)
-    __device__ __forceinline__ void push1(int32_t val) {
-        int idx = atomicAdd(cnt, 1);
-        if (idx < cap) buf[idx] = val;
-    }
-    __device__ __forceinline__ void push(bool pred, int32_t val) {
-        if (pred) push1(val);
-    }
-};
-
-struct WinStats {
-    unsigned long long reads = 0, ops = 0;
-    // span walk's own reads (svt_count_work): see svt_work
-    unsigned long long queries = 0, probe = 0, range = 0, lreads = 0, lentries = 0, stops = 0, stopch = 0;
-    unsigned long long squeries = 0, span = 0;   // span walk (G_SPAN COUNT builds)
-};
-
-template <int KIND>
-__device__ __forceinline__ bool is_candidate_op(uint32_t op, uint32_t len) {
-    if (KIND == K_INS) return op == OP_INS && (uint32_t)SV_MIN_LENGTH <= len;   // refinement.c:299
-    return op == OP_DEL && (uint32_t)SV_MIN_LENGTH < len;                       // refinement.c:124,:188
-}
-
-// Per-read walk, 64 ops per step, replaying the reference's uint32 position arithmetic
-// exactly (refinement.c:118-159 / :184-221 / :295-318).  Used for reads whose walk could
-// wrap 2^32 (never in practice) and by the per-read gather variant.
-// SinkT: the LDS candidate sink, or svt_evidence.inc's counting sink (push(pred, val) per lane).
-template <int KIND, bool COUNT, typename SinkT>
-__device__ __forceinline__ void walk_read(const uint32_t *__restrict__ cigar, uint64_t off, uint32_t n, uint32_t rpos,
-                          uint32_t clip, uint32_t s, uint32_t e, SinkT &sink, WinStats &st) {
-    const int ln = lane_id();
-    uint32_t carry = rpos;
-    bool broke = false;
-    uint32_t stop_rp = 0;
-    uint32_t walked = n;
-    for (uint32_t cb = 0; cb < n; cb += WAVE) {
-        uint32_t i = cb + (uint32_t)ln;
-        bool v = i < n;
-        uint32_t w = v ? cigar[off + i] : 0u;
-        uint32_t op = w & 0xfu, len = w >> 4;
-        uint32_t adv = (op != OP_INS && op != OP_SOFT) ? len : 0u;   // refinement.c:141
-        uint32_t after = carry + wave_scan_add(adv);
-        uint32_t before = after - adv;
-        uint64_t bm = ballot(v && after > e);                         // refinement.c:145
-        int fb = bm ? __builtin_ctzll(bm) : WAVE;
-        bool hit = v && ln <= fb && is_candidate_op<KIND>(op, len);
-        sink.push(hit, KIND == K_END ? (int32_t)(before + len + 1u) : (int32_t)before);   // :198 / :134
-        if (bm) {
-            broke = true;
-            stop_rp = rdlane(after, fb);
-            walked = cb + (uint32_t)fb + 1u;
-            break;
-        }
-        carry = rdlane(after, WAVE - 1);
-    }
-    if (KIND == K_START) {   // trailing soft clip, refinement.c:120,:147-159
-        bool c = (clip & SVT_CLIP_LAST_S) && !broke && s <= carry && carry <= e;
-        sink.push(c && ln == 0, (int32_t)carry);
-    } else if (KIND == K_END) {   // leading soft clip, refinement.c:210-221 (rp = walked position)
-        bool c = (clip & SVT_CLIP_FIRST_S) && (int64_t)s <= (int64_t)(int32_t)rpos &&
-                 (int64_t)(int32_t)rpos <= (int64_t)e;
-        sink.push(c && ln == 0, (int32_t)((broke ? stop_rp : carry) + 1u));
-    }
-    if (COUNT) {
-        st.reads++;
-        uint64_t wk = walked;
-        if (KIND == K_START && (n == 0 || (broke && walked < n))) wk++;   // cigar[n-1] test
-        if (KIND == K_END && n == 0) wk++;                                 // cigar[0] test
-        st.ops += wk;
-    }
-}
-
-// ------------------------------------------------------------------ read range (A3)
-// sam_itr_queryi(idx, chrom-1, inter.start-1, inter.end-1) (refinement.c:114): the reads
-// [lo, hi) of contig tid may overlap [beg, end) (each still needs endpos > beg), with
-//   hi = first read with pos >= end,  lo = first read with emax > beg  (emax = prefix max
-//   of endpos, so every read before lo ends at or before beg).
-// The bucket table gives, per 4 kb bucket b, {first read with pos >= b*4096, first read with
-// emax >= b*4096}; each bound then lies inside one bucket, and the two searches share two
-// dependent steps: 4 bucket words, then one 64-lane probe each of pos[] and emax[].
-__device__ __forceinline__ int64_t probe_first(int64_t l, int64_t h, bool hit_in_lane, bool lane_valid) {
-    const uint64_t m = ballot(lane_valid && hit_in_lane);
-    return m ? l + __builtin_ctzll(m) : h;
-}
-
-__device__ __forceinline__ bool read_range(const DevPileup &P, int tid, int64_t beg, int64_t end, int64_t &lo,
-                                           int64_t &hi, WinStats *st = nullptr) {
-    if (tid < 0 || tid >= P.n_targets || end <= beg) return false;   // no reads (A3)
-    const int64_t ra = P.tid_off[tid], nr = P.tid_off[tid + 1] - ra;
-    if (nr == 0) return false;
-    const int64_t b0 = P.bkt_off[tid], nb = P.bkt_off[tid + 1] - b0;   // last bucket = {nr, nr}
-    const int ln = lane_id();
-    const int64_t bi = min((ln < 2 ? end >> BKT_SHIFT : beg >> BKT_SHIFT) + (ln & 1), nb - 1);
-    const uint2 bw = ln < 4 ? P.bkt[b0 + bi] : make_uint2(0, 0);
-    const int64_t hl = rdlane(bw.x, 0), hh = rdlane(bw.x, 1), ll = rdlane(bw.y, 2), lh = rdlane(bw.y, 3);
-    const int32_t *pos = P.pos + ra, *emax = P.emax + ra;
-    const bool vh = hl + ln < hh, vl = ll + ln < lh;
-    const int32_t pv = vh ? pos[hl + ln] : 0, ev = vl ? emax[ll + ln] : 0;
-    int64_t h = probe_first(hl, hh, (int64_t)pv >= end, vh);
-    int64_t l = probe_first(ll, lh, (int64_t)ev > beg, vl);
-    if (hh - hl > WAVE) h = wave_partition_point(hl, hh, [&](int64_t r) { return (int64_t)pos[r] >= end; });
-    if (lh - ll > WAVE) l = wave_partition_point(ll, lh, [&](int64_t r) { return (int64_t)emax[r] > beg; });
-    if (st) {   // COUNT builds: the bucket words + each search's entries up to its boundary
-        st->queries++;
-        st->probe += (unsigned long long)((h - hl) + (h < hh ? 1 : 0) + (l - ll) + (l < lh ? 1 : 0));
-    }
-    lo = ra + l;
-    hi = ra + h;
-    return lo < hi;
-}
-
-// ------------------------------------------------------------------ per-read gather (v1)
-template <int KIND, bool COUNT, typename SinkT>
-__device__ __forceinline__ void gather_perread(const DevPileup &P, int tid, uint32_t s, uint32_t e, SinkT &sink, WinStats &st) {
-    const int64_t beg = (int64_t)(uint32_t)(s - 1u), end = (int64_t)(uint32_t)(e - 1u);
-    int64_t lo, hi;
-    if (!read_range(P, tid, beg, end, lo, hi)) return;
-    const int ln = lane_id();
-    for (int64_t base = lo; base < hi; base += WAVE) {
-        int64_t r = base + ln;
-        bool valid = r < hi;
-        uint4 rc = valid ? P.rec[r] : make_uint4(0, 0, 0, 0);
-        bool ov = valid && (int64_t)(int32_t)rc.y > beg;   // pos < end holds below hi (hts_itr_next)
-        uint64_t m = ballot(ov);
-        while (m) {
-            int l = __builtin_ctzll(m);
-            m &= m - 1;
-            uint32_t z = rdlane(rc.z, l);
-            walk_read<KIND, COUNT>(P.cigar, P.off64[base + l], z & NCIG_MASK, rdlane(rc.x, l), z >> 30, s, e, sink,
-                                   st);
-        }
-    }
-}
-
-// ------------------------------------------------------------------ shared helpers
-__device__ __forceinline__ uint32_t ref_adv(uint32_t w) {   // refinement.c:141: every op but I (1) and S (4)
-    return (w >> 4) & (uint32_t)__builtin_amdgcn_sbfe((int)~0x12u, w & 0xfu, 1);
-}
-
-#ifndef SVT_DIAG
-#define SVT_DIAG 0               // diagnostic builds only (wrong results): 1 = region query only, 3 = no refine_end
-                                 // stop search, 4 = no sort/vote, 5 = sort + prefix sums, no vote, ...,
-                                 // 23 = the lane emit without its CIGAR walk (svt_index2.inc, profiles/r05_AK)
-#endif
-
-
-// ------------------------------------------------------------------ span walk (default)
-// The reads [lo, hi) of a window own one contiguous span of the D (or I) event list, and
-// every event carries what its tests need (its read's endpos for the overlap test of
-// hts_itr_next), so a window is: region query, the span's two bounds, then ONE filter over
-// the span, every load of a 256-event batch issued at once (no per-read dependent chain).
-// An op is processed by the reference walk iff the walk position before it is <= inter.end
-// (positions only grow along a read, refinement.c:145), so a candidate event counts iff
-// x <= e; the soft-clip events follow refinement.c:147-159 (trailing S: no break, s <= walk
-// end <= e) and :210-220 (leading S, s <= pos <= e: walk end + 1, or -- the walk passes e --
-// the position after the break op + 1, which votes as e + 2: KParams::sent_ok).
-constexpr int SPAN_U = 4;   // 16-B event loads in flight per lane
-
-__device__ __forceinline__ uint32_t mbcnt(uint64_t m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
-// The span walk's own reads, for svt_count_work: the region query and the events of the span.
-template <int KIND>
-__device__ __forceinline__ void span_count(const DevPileup &P, int tid, uint32_t s, uint32_t e, WinStats &st) {
-    const int64_t beg = (int64_t)(uint32_t)(s - 1u), end = (int64_t)(uint32_t)(e - 1u);
-    int64_t lo, hi;
-    if (!read_range(P, tid, beg, end, lo, hi, &st)) return;
-    const uint64_t *off = KIND == K_INS ? P.spoffI : P.spoffD;
-    st.squeries++;
-    st.span += off[hi] - off[lo];
-}
-
-// read_range (A3) with the span bounds read in the same dependent step as the pos/emax
-// probes: each probe lane also loads the span offset of its read, and the bounds are taken
-// from the lanes where the two searches end (one HBM round trip less per window).  Wider
-// bucket ranges fall back to read_range + one more step.
-template <int KIND>
-__device__ __forceinline__ bool span_query(const DevPileup &P, int tid, int64_t beg, int64_t end, uint64_t &E0,
-                                           uint64_t &E1) {
-    if (tid < 0 || tid >= P.n_targets || end <= beg) return false;   // no reads (A3)
-    const int64_t ra = P.tid_off[tid], nr = P.tid_off[tid + 1] - ra;
-    if (nr == 0) return false;
-    const uint64_t *off = KIND == K_INS ? P.spoffI : P.spoffD;
-    const int64_t b0 = P.bkt_off[tid], nb = P.bkt_off[tid + 1] - b0;   // last bucket = {nr, nr}
-    const int ln = lane_id();
-    const int64_t bi = min((ln < 2 ? end >> BKT_SHIFT : beg >> BKT_SHIFT) + (ln & 1), nb - 1);
-    const uint2 bw = ln < 4 ? P.bkt[b0 + bi] : make_uint2(0, 0);
-    const int64_t hl = rdlane(bw.x, 0), hh = rdlane(bw.x, 1), ll = rdlane(bw.y, 2), lh = rdlane(bw.y, 3);
-    if (hh - hl >= WAVE || lh - ll >= WAVE) {   // wide bucket: the general search, then the bounds
-        int64_t lo, hi;
-        if (!read_range(P, tid, beg, end, lo, hi)) return false;
-        const uint64_t ob = ln < 2 ? off[ln ? hi : lo] : 0ull;
-        E0 = rdlane64(ob, 0);
-        E1 = rdlane64(ob, 1);
-        return true;
-    }
-    // lanes [0, hh-hl] cover the hi candidates hl .. hh, lanes [0, lh-ll] the lo candidates
-    const bool vh = hl + ln <= hh, vl = ll + ln <= lh;
-    const int64_t rh = ra + (vh ? hl + ln : hl), rl = ra + (vl ? ll + ln : ll);
-    const int32_t pv = vh && hl + ln < hh ? P.pos[rh] : 0, ev = vl && ll + ln < lh ? P.emax[rl] : 0;
-    const uint64_t oh = off[rh], ol = off[rl];
-    const uint64_t mh = ballot(vh && hl + ln < hh && (int64_t)pv >= end);
-    const uint64_t ml = ballot(vl && ll + ln < lh && (int64_t)ev > beg);
-    const int kh = mh ? __builtin_ctzll(mh) : (int)(hh - hl), kl = ml ? __builtin_ctzll(ml) : (int)(lh - ll);
-    if (ll + kl >= hl + kh) return false;
-    E1 = rdlane64(oh, kh);
-    E0 = rdlane64(ol, kl);
-    return true;
-}
-
-// One span event's test for window [s, e] (query beg = s-1): it is a candidate with value val.
-// A leading-S read whose walk passes e (refine_end's stop, :210-221) is one at e + 2.
-template <int KIND>
-__device__ __forceinline__ bool span_cand(const uint4 &v, uint32_t s, uint32_t e, int32_t beg32, uint32_t &val) {
-    const uint32_t x = v.x, op = v.y & 0xfu, len = v.y >> 4;
-    const bool ovl = (int32_t)v.z > beg32;   // hts_itr_next overlap; pos < end holds below hi
-    val = x;
-    if (KIND == K_INS) return ovl && op == OP_INS && x <= e;                   // refinement.c:299
-    if (KIND == K_START) return ovl && x <= e && (op == OP_DEL || (op == SP_TRAIL && s <= x));   // :124 / :147-159
-    const bool lead = op == SP_LEAD && ovl && s <= x && x <= e;                // :210-220
-    val = op == OP_DEL ? x + len + 1u : v.w > e ? e + 2u : v.w + 1u;
-    return (ovl && x <= e && op == OP_DEL) || lead;                            // :188-199
-}
-
-template <int KIND>
-__device__ __forceinline__ void span_walk(const DevPileup &P, uint32_t s, uint32_t e, uint64_t E0, uint64_t E1,
-                                          Sink &sink) {
-    const int32_t beg32 = (int32_t)(uint32_t)(s - 1u);   // yielded reads: beg < end <= 2^30
-    const int ln = lane_id();
-    const uint4 *ev = KIND == K_INS ? P.spI : P.spD;
-    int32_t cnt = 0;   // candidates appended so far (wave-uniform)
-    for (uint64_t b = E0; b < E1; b += SPAN_U * WAVE) {
-        uint4 v[SPAN_U];
-        const uint64_t left = E1 - b;   // events from b on (wave-uniform): the u-slots past them are skipped
-        // loads with clamped indices and no branches, so that all of them are in flight
-        // before the first is used; lanes past E1 are masked below
-#pragma unroll
-        for (int u = 0; u < SPAN_U; u++) {
-            const uint64_t j = b + (uint64_t)(u * WAVE + ln);
-            if ((uint64_t)(u * WAVE) < left) v[u] = ev[j < E1 ? j : E1 - 1];
-        }
-#pragma unroll
-        for (int u = 0; u < SPAN_U; u++) {
-            if ((uint64_t)(u * WAVE) >= left) break;
-            if ((uint64_t)(u * WAVE + ln) >= left) v[u] = make_uint4(0, 0, 0, 0);   // zero event: no candidate
-            uint32_t val;
-            const bool c = span_cand<KIND>(v[u], s, e, beg32, val);
-            const uint64_t m = ballot(c);
-            const int32_t idx = cnt + (int32_t)mbcnt(m);
-            if (c && idx < sink.cap) sink.buf[idx] = (int32_t)val;
-            cnt += (int32_t)__popcll(m);
-        }
-    }
-    if (ln == 0) *sink.cnt = cnt;
-}
-
-// The wave-wide gather of one window: the span walk, or the reference's own per-read walk for
-// windows ending at or past WEXACT and for refine_end windows whose leading-S stops cannot
-// vote as e + 2 (!sent_ok).
-template <int KIND, bool COUNT>
-__device__ __forceinline__ void gather_span(const DevPileup &P, const KParams &k, int tid, uint32_t s, uint32_t e,
-                                            Sink &sink, WinStats &st) {
-    if (COUNT) {   // diagnostic: the reference's work by the exact per-read walk + what the span walk reads
-        gather_perread<KIND, true>(P, tid, s, e, sink, st);
-        if (e < WEXACT) span_count<KIND>(P, tid, s, e, st);
-        return;
-    }
-    if (e >= WEXACT || (KIND == K_END && !k.sent_ok)) { gather_perread<KIND, COUNT>(P, tid, s, e, sink, st); return; }
-    const int64_t beg = (int64_t)(uint32_t)(s - 1u), end = (int64_t)(uint32_t)(e - 1u);
-    uint64_t E0, E1;
-    if (!span_query<KIND>(P, tid, beg, end, E0, E1)) return;
-#if SVT_DIAG == 1
-    return;     // diagnostic build: region query only
-#endif
-    span_walk<KIND>(P, s, e, E0, E1, sink);
-}
-
-// ------------------------------------------------------------------ sort + vote (A8-A10)
-// Bitonic sort of buf[0..N) (N power of two, padded with INT32_MAX) by one wave.
-__device__ __forceinline__ void wave_bitonic_sort(int32_t *buf, int N) {
-    const int ln = lane_id();
-    for (int k = 2; k <= N; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = ln; i < N; i += WAVE) {
-                int p = i ^ j;
-                if (p > i) {
-                    int32_t a = buf[i], b = buf[p];
-                    bool up = (i & k) == 0;
-                    if ((a > b) == up) { buf[i] = b; buf[p] = a; }
-                }
-            }
-            wave_sync();
-        }
-    }
-}
-
-// x of lane ln ^ J without an LDS round trip: DPP quad permutes (1, 2), row shifts (4), row
-// rotate (8), and gfx950's permlane swaps (16, 32).  A swap of x with itself yields the two
-// halves {[lo, lo], [hi, hi]} (rows for 16); whichever of them does not hold this lane's own
-// value at this lane holds the partner's (and if both do, the two values are equal).
-template <int J>
-__device__ __forceinline__ int32_t lane_xor(int32_t x) {
-    if constexpr (J == 1) {
-        return __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
-    } else if constexpr (J == 2) {
-        return __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xf, 0xf, false);   // quad_perm [2,3,0,1]
-    } else if constexpr (J == 4) {
-        const int32_t up = __builtin_amdgcn_update_dpp(0, x, 0x104, 0xf, 0xf, false);   // row_shl:4 (lane + 4)
-        const int32_t dn = __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false);   // row_shr:4 (lane - 4)
-        return (lane_id() & 4) ? dn : up;
-    } else if constexpr (J == 8) {
-        return __builtin_amdgcn_update_dpp(0, x, 0x128, 0xf, 0xf, false);   // row_ror:8
-    } else if constexpr (J == 16) {
-        const auto r = __builtin_amdgcn_permlane16_swap((uint32_t)x, (uint32_t)x, false, false);
-        return (int32_t)((int32_t)r[0] == x ? r[1] : r[0]);
-    } else {
-        static_assert(J == 32, "lane_xor: J in {1, 2, 4, 8, 16, 32}");
-        const auto r = __builtin_amdgcn_permlane32_swap((uint32_t)x, (uint32_t)x, false, false);
-        return (int32_t)((int32_t)r[0] == x ? r[1] : r[0]);
-    }
-}
-__device__ __forceinline__ int32_t lane_xor(int32_t x, int j) {   // j a compile-time constant after unrolling
-    switch (j) {
-        case 1: return lane_xor<1>(x);
-        case 2: return lane_xor<2>(x);
-        case 4: return lane_xor<4>(x);
-        case 8: return lane_xor<8>(x);
-        case 16: return lane_xor<16>(x);
-        default: return lane_xor<32>(x);
-    }
-}
-
-// Bitonic sort of buf[0..n), n <= 64*E, in registers: element i = k*64 + lane lives in x[k];
-// exchanges at distance >= 64 stay inside a lane, shorter ones are lane-xor shuffles.
-// Padding is INT32_MAX; one load and one store per element.
-// NB < 64 (E == 1, n <= NB): the merge stages stop at block size NB; the padding above NB
-// stays in place (every exchange of a stage with block size kk stays inside its block).
-template <int E, int NB = E * WAVE>
-__device__ __forceinline__ int32_t reg_bitonic_sort(int32_t *buf, int32_t n) {   // returns element ln
-    const int ln = lane_id();
-    int32_t x[E];
-#pragma unroll
-    for (int k = 0; k < E; k++) x[k] = k * WAVE + ln < n ? buf[k * WAVE + ln] : INT32_MAX;
-#pragma unroll
-    for (int kk = 2; kk <= NB; kk <<= 1) {
-#pragma unroll
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            if (j >= WAVE) {
-                const int kj = j / WAVE;
-#pragma unroll
-                for (int k = 0; k < E; k++) {
-                    if (k & kj) continue;
-                    const bool asc = ((k * WAVE + ln) & kk) == 0;
-                    const int32_t a = x[k], b = x[k | kj];
-                    x[k] = asc ? min(a, b) : max(a, b);
-                    x[k | kj] = asc ? max(a, b) : min(a, b);
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < E; k++) {
-                    const int i = k * WAVE + ln;
-                    const int32_t y = lane_xor(x[k], j);
-                    x[k] = (((i & j) == 0) == ((i & kk) == 0)) ? min(x[k], y) : max(x[k], y);
-                }
-            }
-        }
-    }
-    wave_sync();
-#pragma unroll
-    for (int k = 0; k < E; k++) buf[k * WAVE + ln] = x[k];
-    return x[0];
-}
-
-__device__ __forceinline__ int32_t ref_abs(int32_t a) { return a < 0 ? -a : a; }   // refinement.h:41
-
-__device__ __forceinline__ int32_t first_greater(const int32_t *buf, int32_t l, int32_t h, int64_t key) {
-    while (l < h) {
-        int32_t m = (l + h) >> 1;
-        if ((int64_t)buf[m] > key) h = m; else l = m + 1;
-    }
-    return l;
-}
-__device__ __forceinline__ int32_t first_geq(const int32_t *buf, int32_t l, int32_t h, int64_t key) {
-    while (l < h) {
-        int32_t m = (l + h) >> 1;
-        if ((int64_t)buf[m] >= key) h = m; else l = m + 1;
-    }
-    return l;
-}
-
-__device__ SVT_COLD int32_t mean_round(int64_t tot, int32_t cnt) {   // cold: the 64-bit division
-    // (int)((uint64 total + count/2) / count), refinement.c:66
-    uint64_t t = (uint64_t)tot + (uint64_t)(int64_t)(cnt / 2);
-    return (int32_t)(uint32_t)(t / (uint64_t)(int64_t)cnt);
-}
-
-// mean_round of a cluster whose smallest value is `base`.  With base >= 0 every value is
-// >= 0, the reference's uint64 total is the exact sum, and (sum + cnt/2) / cnt =
-// base + (sum - cnt*base + cnt/2) / cnt: a 32-bit division whenever the offsets' sum fits.
-__device__ __forceinline__ int32_t mean_cluster(int64_t tot, int32_t cnt, int32_t base) {
-    if (base >= 0) {
-        const int64_t d = tot - (int64_t)cnt * (int64_t)base;
-        if (d < (int64_t)0x7fffffff) {
-            const uint32_t q = ((uint32_t)d + (uint32_t)(cnt / 2)) / (uint32_t)cnt;
-            return (int32_t)((uint32_t)base + q);
-        }
-    }
-    return mean_round(tot, cnt);
-}
-
-// Band filter (exact): consensus_pos only ever reads elements within `range` of pos and
-// their clusters (within ci of them), i.e. values in (pos - range - ci, pos + range + ci),
-// plus three facts about the whole multiset: whether any element is <= pos+25 (where the
-// left pass starts, lower_bound), its minimum (upper_bound's A[0] < pos-25 test and the
-// right pass's first element) and its maximum (the right pass's start when that test
-// fails).  Both passes stop at the first out-of-range element, and every element between
-// the band and the pass start is out of range, so voting over the band's sorted elements
-// with those three facts visits the same elements with the same clusters.  Requires
-// range > 25 (the left start pos+25 is then inside the band) and |pos|, |values| < 2^30
-// (the reference's int32 differences cannot wrap); otherwise the full multiset is voted.
-struct Band {
-    bool on = false;    // the vote runs over the band's elements (else over the full multiset)
-    bool f32 = false;   // ... and every band element is >= 0: 32-bit cluster sums (vote<true>)
-    int32_t u = 0;      // #elements <= pos+25 of the full multiset (the left pass start)
-    int32_t n_lt = 0;   // #elements <  pos-25 (upper_bound's A[0] < pos-25 test)
-    int32_t n_le = 0;   // #elements <= lo (is the full minimum inside the band?)
-    int32_t n_ge = 0;   // #elements >= hi (is the full maximum inside the band?)
-    int32_t lo = 0, hi = 0;   // the band: open interval (lo, hi)
-};
-
-// Compacts buf[0..n) (n <= 4*WAVE) to its band elements in place; returns their count.
-// Counts only (ballots), no reductions; int32 compares throughout, since the band is only
-// used when |pos| < 2^30 and range + max(ci, 0) <= 2^22 (so lo, hi fit) and every element
-// is within +-2^30.
-__device__ __forceinline__ int32_t band_filter(int32_t *buf, int32_t n, int32_t pos, const KParams &k, Band &bd) {
-    constexpr int32_t LIM = 1 << 30, WMAX = 1 << 22;
-    if (k.range <= SV_MIN_LENGTH / 2 || pos <= -LIM || pos >= LIM || k.range > WMAX || k.ci > WMAX - k.range ||
-        k.ci < -WMAX)
-        return n;
-    const int ln = lane_id();
-    const int32_t w = k.range + max(k.ci, 0);
-    const int32_t lo = pos - w, hi = pos + w;
-    constexpr int E = 4;
-    int32_t x[E];
-    int32_t u = 0, nlt = 0, nle = 0, nge = 0;
-    uint64_t bad = 0, neg = 0;
-#pragma unroll
-    for (int q = 0; q < E; q++) {
-        x[q] = 0;
-        if (q * WAVE >= n) break;   // wave-uniform: blocks past n hold nothing
-        const int i = q * WAVE + ln;
-        const bool v = i < n;
-        x[q] = v ? buf[i] : 0;
-        u += __popcll(ballot(v && x[q] <= pos + SV_MIN_LENGTH / 2));
-        nlt += __popcll(ballot(v && x[q] < pos - SV_MIN_LENGTH / 2));
-        nle += __popcll(ballot(v && x[q] <= lo));
-        nge += __popcll(ballot(v && x[q] >= hi));
-        bad |= ballot(v && (x[q] <= -LIM || x[q] >= LIM));
-        neg |= ballot(v && lo < x[q] && x[q] < hi && x[q] < 0);
-    }
-    if (bad) return n;
-    bd.on = true;
-    bd.f32 = neg == 0;
-    bd.u = u; bd.n_lt = nlt; bd.n_le = nle; bd.n_ge = nge;
-    bd.lo = lo; bd.hi = hi;
-    wave_sync();
-    int32_t cnt = 0;
-#pragma unroll
-    for (int q = 0; q < E; q++) {
-        if (q * WAVE >= n) break;
-        const int i = q * WAVE + ln;
-        const bool keep = i < n && lo < x[q] && x[q] < hi;
-        const uint64_t m = ballot(keep);
-        if (keep) buf[cnt + (int32_t)mbcnt(m)] = x[q];
-        cnt += (int32_t)__popcll(m);
-    }
-    wave_sync();
-    return cnt;
-}
-
-// band_filter for any n (the spill slab, > 4*WAVE candidates): the same counts and the same
-// in-place compaction, 64 elements per step (writes never pass the block being read).
-__device__ __forceinline__ int32_t band_filter_large(int32_t *buf, int32_t n, int32_t pos, const KParams &k,
-                                                     Band &bd) {
-    constexpr int32_t LIM = 1 << 30, WMAX = 1 << 22;
-    if (k.range <= SV_MIN_LENGTH / 2 || pos <= -LIM || pos >= LIM || k.range > WMAX || k.ci > WMAX - k.range ||
-        k.ci < -WMAX)
-        return n;
-    const int ln = lane_id();
-    const int32_t w = k.range + max(k.ci, 0);
-    const int32_t lo = pos - w, hi = pos + w;
-    int32_t u = 0, nlt = 0, nle = 0, nge = 0;
-    uint64_t bad = 0, neg = 0;
-    for (int32_t b = 0; b < n; b += WAVE) {
-        const int32_t i = b + ln;
-        const bool v = i < n;
-        const int32_t x = v ? buf[i] : 0;
-        u += __popcll(ballot(v && x <= pos + SV_MIN_LENGTH / 2));
-        nlt += __popcll(ballot(v && x < pos - SV_MIN_LENGTH / 2));
-        nle += __popcll(ballot(v && x <= lo));
-        nge += __popcll(ballot(v && x >= hi));
-        bad |= ballot(v && (x <= -LIM || x >= LIM));
-        neg |= ballot(v && lo < x && x < hi && x < 0);
-    }
-    if (bad) return n;
-    bd.on = true;
-    bd.f32 = neg == 0;
-    bd.u = u; bd.n_lt = nlt; bd.n_le = nle; bd.n_ge = nge;
-    bd.lo = lo; bd.hi = hi;
-    wave_sync();
-    int32_t cnt = 0;
-    for (int32_t b = 0; b < n; b += WAVE) {
-        const int32_t i = b + ln;
-        const int32_t x = i < n ? buf[i] : 0;
-        const bool keep = i < n && lo < x && x < hi;
-        const uint64_t m = ballot(keep);
-        wave_sync();
-        if (keep) buf[cnt + (int32_t)mbcnt(m)] = x;
-        cnt += (int32_t)__popcll(m);
-        wave_sync();
-    }
-    return cnt;
-}
-
-__device__ __forceinline__ int32_t first_greater32(const int32_t *buf, int32_t l, int32_t h, int32_t key) {
-    while (l < h) {
-        int32_t m = (l + h) >> 1;
-        if (buf[m] > key) h = m; else l = m + 1;
-    }
-    return l;
-}
-__device__ __forceinline__ int32_t first_geq32(const int32_t *buf, int32_t l, int32_t h, int32_t key) {
-    while (l < h) {
-        int32_t m = (l + h) >> 1;
-        if (buf[m] >= key) h = m; else l = m + 1;
-    }
-    return l;
-}
-
-// consensus_pos (refinement.c:41-101) on sorted A[0..n) with prefix sums P[0..n].
-// reg: x0 holds A[lane] for lanes < min(n, 64) (the register sorts), read instead of LDS.
-// F32: A is a band with every element >= 0 and P holds 32-bit sums of A[j] - A0 (A0 = A[0]):
-// the reference's rounded uint64 mean (sum + c/2) / c of a cluster of non-negative values is
-// then A0 + (its offset sum + c/2) / c exactly, in 32 bits (offset sums < 2^31, band_filter).
-template <bool F32>
-__device__ __forceinline__ int32_t vote(const int32_t *A, const void *Pv, int32_t n, int32_t pos, const KParams &k,
-                                        int32_t x0, bool reg, const Band &bd, int32_t A0) {
-    const int64_t *P = reinterpret_cast<const int64_t *>(Pv);
-    const uint32_t *P32 = reinterpret_cast<const uint32_t *>(Pv);
-    const int ln = lane_id();
-    const int32_t ci = k.ci, range = k.range;
-    int32_t valL = -1, maxL = k.min_count - 1, distL = 0x7fffffff;
-    int32_t valR = -1, maxR = k.min_count - 1, distR = 0x7fffffff;
-
-    // lower_bound(A, n, pos+25): (#elements <= pos+25) - 1, clamped at 0  (refinement.c:3-10)
-    int32_t u = 0;
-    for (int32_t b = 0; b < n; b += WAVE) {
-        int32_t i = b + ln;
-        u += __popcll(ballot(i < n && (reg && b == 0 ? x0 : A[i]) <= pos + SV_MIN_LENGTH / 2));
-    }
-    int32_t p = u == 0 ? 0 : u - 1;
-    if (bd.on) {   // A = the band of the full multiset (see Band): start where the full pass would
-        p = bd.u == 0 ? 0 : u == 0 ? -1 : u - 1;   // u >= 1 elements <= pos+25 but none in the band:
-        if (n == 0) p = -1;                         // the full pass stops at once (below the band)
-    }
-
-    // left pass: i = p, p-1, ... while |pos - A[i]| < range   (refinement.c:58-77)
-    for (int32_t top = p; top >= 0; top -= WAVE) {
-        int32_t i = top - ln;
-        bool inr = i >= 0 && ref_abs(pos - A[i < 0 ? 0 : i]) < range;
-        uint64_t stop = ballot(!inr);
-        int lim = stop ? __builtin_ctzll(stop) : WAVE;   // lanes [0, lim) are in the pass
-        int32_t cnt = 0, cand = 0;
-        if (ln < lim) {
-            int32_t a = A[i];
-            if (F32) {
-                const int32_t kk = first_geq32(A, 0, i, a - ci);   // contiguous j<i with a <= A[j]+ci
-                cnt = i - kk + 1;
-                cand = A0 + (int32_t)((P32[i + 1] - P32[kk] + (uint32_t)(cnt / 2)) / (uint32_t)cnt);
-            } else {
-                int32_t kk = first_geq(A, 0, i, (int64_t)a - ci);   // contiguous j<i with a <= A[j]+ci
-                cnt = i - kk + 1;
-                cand = mean_cluster(P[i + 1] - P[kk], cnt, A[kk]);
-            }
-        }
-        // the greedy accept in pass order, visiting only elements whose count beats maxL
-        const int32_t dd = ref_abs(pos - cand);
-        for (int l = -1;;) {
-            const uint64_t cm = ballot(ln < lim && ln > l && cnt > maxL);
-            if (!cm) break;
-            l = __builtin_ctzll(cm);
-            const int32_t c = rdlane_i(cnt, l), v = rdlane_i(cand, l), d = rdlane_i(dd, l);
-            if (d < ci) return v;                        // early return, refinement.c:67-68
-            if (d < distL) { maxL = c; valL = v; distL = d; }
-        }
-        if (stop) break;
-    }
-
-    // upper_bound(A, n, pos-25): 0 if A[0] < pos-25 else n-1   (refinement.c:12-19)
-    int32_t q = (n > 0 && (reg ? rdlane_i(x0, 0) : A[0]) < pos - SV_MIN_LENGTH / 2) ? 0 : n - 1;
-    if (bd.on)   // the full multiset's A[0] / A[n-1]: in the band they are A's first / last element
-        q = bd.n_lt > 0 ? (bd.n_le == 0 ? 0 : n) : (bd.n_ge == 0 ? n - 1 : n);
-    for (int32_t bot = q; bot < n; bot += WAVE) {
-        int32_t i = bot + ln;
-        const int32_t ai = reg && bot == 0 ? x0 : A[i < n ? i : 0];
-        bool inr = i < n && ref_abs(pos - ai) < range;
-        uint64_t stop = ballot(!inr);
-        int lim = stop ? __builtin_ctzll(stop) : WAVE;
-        int32_t cnt = 0, cand = 0;
-        if (ln < lim) {
-            int32_t a = ai;
-            if (F32) {
-                const int32_t m = first_greater32(A, i + 1, n, a + ci);   // contiguous j>i with A[j] <= a+ci
-                cnt = m - i;
-                cand = A0 + (int32_t)((P32[m] - P32[i] + (uint32_t)(cnt / 2)) / (uint32_t)cnt);
-            } else {
-                int32_t m = first_greater(A, i + 1, n, (int64_t)a + ci);   // contiguous j>i with A[j] <= a+ci
-                cnt = m - i;
-                cand = mean_cluster(P[m] - P[i], cnt, a);
-            }
-        }
-        const int32_t dd = ref_abs(pos - cand);
-        for (int l = -1;;) {
-            const uint64_t cm = ballot(ln < lim && ln > l && cnt > maxR);
-            if (!cm) break;
-            l = __builtin_ctzll(cm);
-            const int32_t c = rdlane_i(cnt, l), v = rdlane_i(cand, l), d = rdlane_i(dd, l);
-            if (d < ci) return v;                        // refinement.c:88-89
-            if (d < distR) { maxR = c; valR = v; distR = d; }
-        }
-        if (stop) break;
-    }
-    return distL < distR ? valL : valR;   // refinement.c:100
-}
-
-// sliding_window_ins's vote (sliding_window.c:65-84) on sorted A[0..n) with prefix sums
-// P[0..n]: for i = 0, slide, 2*slide, ...: support = #{j >= i : A[j] - A[i] <= ws}; the
-// first i reaching the largest support >= min_count wins, its candidate is the rounded
-// mean of A[i..i+support) in the reference's 32-bit int arithmetic (sum wraps mod 2^32).
-__device__ __forceinline__ int32_t sw_vote(const int32_t *A, const int64_t *P, int32_t n, const KParams &k,
-                                           int32_t &support_out) {
-    const int ln = lane_id();
-    const int32_t ws = k.sw_window, slide = k.sw_slide;
-    const int32_t nstart = (n + slide - 1) / slide;
-    int32_t best_sup = 0, best_i = -1;
-    for (int32_t b = 0; b < nstart; b += WAVE) {
-        const int32_t t = b + ln;
-        int32_t sup = 0, i = 0;
-        if (t < nstart) {
-            i = t * slide;
-            sup = first_greater(A, i, n, (int64_t)A[i] + ws) - i;         // :71-75
-        }
-        const bool ok = sup >= k.min_count;                                  // :76
-        // wave max of qualifying supports; ties -> the smallest i (strict > in :76)
-        int32_t m = wave_scan_max(ok ? sup : -1);
-        m = rdlane_i(m, WAVE - 1);
-        if (m > best_sup) {
-            const uint64_t at = ballot(ok && sup == m);
-            best_sup = m;
-            best_i = rdlane_i(i, __builtin_ctzll(at));
-        }
-    }
-    support_out = best_sup;
-    if (best_i < 0) return -1;
-    const uint32_t sum = (uint32_t)(uint64_t)(P[best_i + best_sup] - P[best_i]);      // :78-81, int wrap
-    return (int32_t)(sum + (uint32_t)(best_sup / 2)) / best_sup;                      // :82
-}
-
-constexpr int V_CONSENSUS = 0, V_SLIDING = 1;
-
-// Sort + prefix sums + vote over buf[0..n) with scratch for P (n+1 int64).
-// LARGE: n > 4*WAVE is known (the spill slab): only the global bitonic + the int64 vote.
-template <int VOTE, bool LARGE = false>
-__device__ __forceinline__ int32_t sort_and_vote(int32_t *buf, int64_t *P, int32_t n, int32_t pos, const KParams &k,
-                                                 int32_t &support, const Band *given = nullptr) {
-    const int ln = lane_id();
-    Band bd;
-    if (given) bd = *given;   // buf already holds the band (band_filter_large)
-    else if (!LARGE && VOTE == V_CONSENSUS && n <= 4 * WAVE) n = band_filter(buf, n, pos, k, bd);
-    int32_t x0 = 0;   // sorted element ln, from the register sorts (no LDS read-back below)
-    if (LARGE) {
-        int N = 1;
-        while (N < n) N <<= 1;
-        for (int i = n + ln; i < N; i += WAVE) buf[i] = INT32_MAX;
-        wave_sync();
-        wave_bitonic_sort(buf, N);
-    } else if (n <= 16) x0 = reg_bitonic_sort<1, 16>(buf, n);
-    else if (n <= 32) x0 = reg_bitonic_sort<1, 32>(buf, n);
-    else if (n <= WAVE) x0 = reg_bitonic_sort<1>(buf, n);
-    else if (n <= 2 * WAVE) x0 = reg_bitonic_sort<2>(buf, n);
-    else if (n <= 4 * WAVE) x0 = reg_bitonic_sort<4>(buf, n);
-    else {
-        int N = 1;
-        while (N < n) N <<= 1;
-        for (int i = n + ln; i < N; i += WAVE) buf[i] = INT32_MAX;
-        wave_sync();
-        wave_bitonic_sort(buf, N);
-    }
-    if (!LARGE && VOTE == V_CONSENSUS && bd.on && bd.f32) {   // 32-bit offset sums (see vote<true>)
-        uint32_t *P32 = reinterpret_cast<uint32_t *>(P);
-        const int32_t A0 = n > 0 ? rdlane_i(x0, 0) : 0;
-        uint32_t carry = 0;
-        if (ln == 0) P32[0] = 0;
-        for (int32_t b = 0; b < n; b += WAVE) {
-            const int32_t i = b + ln;
-            const uint32_t x = i < n ? (uint32_t)((b == 0 ? x0 : buf[i]) - A0) : 0u;
-            const uint32_t sc = carry + wave_scan_add(x);
-            if (i < n) P32[i + 1] = sc;
-            carry = rdlane(sc, WAVE - 1);
-        }
-        wave_sync();
-        if (SVT_DIAG == 5) return n;
-        return vote<true>(buf, P32, n, pos, k, x0, true, bd, A0);
-    }
-    int64_t carry = 0;
-    if (ln == 0) P[0] = 0;
-    for (int32_t b = 0; b < n; b += WAVE) {
-        int32_t i = b + ln;
-        int64_t x = i < n ? (int64_t)(!LARGE && b == 0 && n <= 4 * WAVE ? x0 : buf[i]) : 0;
-        int64_t s = carry + wave_scan_add64(x);
-        if (i < n) P[i + 1] = s;
-        carry = (int64_t)rdlane64((uint64_t)s, WAVE - 1);
-    }
-    wave_sync();
-    if (SVT_DIAG == 5) return n;   // diagnostic build: sort + prefix sums, no vote
-    if (VOTE == V_SLIDING) return sw_vote(buf, P, n, k, support);
-    return vote<false>(buf, P, n, pos, k, x0, !LARGE && n <= 4 * WAVE, bd, 0);
-}
-
-struct WinLds {
-    int64_t pre[CAP + 1];         // the wave-wide vote's prefix sums
-    int32_t cand[CAP];
-    int32_t ncand;
-};
-
-// The window gather: the span walk (gather_span).  Round 1-2's A/B variants (per-read, CIGAR
-// stream, chunk index, candidate-op lists) are retired; G stays a template parameter of the
-// wave-wide window path so that diagnostic builds can plug a gather in.
-constexpr int G_SPAN = 4;
-
-template <int KIND, bool COUNT, int G>
-__device__ __forceinline__ int32_t gather(const KArgs &a, int tid, uint32_t s, uint32_t e, Sink &sink, WinStats &st,
-                                          WinLds &L) {
-    if (lane_id() == 0) *sink.cnt = 0;
-    wave_sync();
-    static_assert(G == G_SPAN, "span walk only");
-    (void)L;
-    gather_span<KIND, COUNT>(a.pile, a.prm, tid, s, e, sink, st);
-    wave_sync();
-    return uniform_i(*sink.cnt);
-}
-
-template <int KIND, bool COUNT, int G, int VOTE>
-__device__ __forceinline__ int32_t vote_window(const KArgs &a, WinLds &lds, int chrom, uint32_t s, uint32_t e,
-                                               uint32_t imprecise, int32_t n, unsigned long long *wk, int32_t &support);
-
-template <int KIND, bool COUNT, int G, int VOTE = V_CONSENSUS>
-__device__ __forceinline__ int32_t refine_window(const KArgs &a, WinLds &lds, int chrom, uint32_t s, uint32_t e, uint32_t imprecise,
-                                 unsigned long long *wk, int32_t &support) {
-    WinStats st;
-    Sink sink{lds.cand, CAP, &lds.ncand};
-    int32_t n = gather<KIND, COUNT, G>(a, chrom - 1, s, e, sink, st, lds);
-    if (COUNT && lane_id() == 0) {
-        wk[W_WINDOWS] += 1; wk[W_READS] += st.reads; wk[W_OPS] += st.ops; wk[W_CANDS] += (unsigned long long)n;
-        wk[W_QUERIES] += st.queries; wk[W_PROBE] += st.probe; wk[W_RANGE] += st.range; wk[W_LREADS] += st.lreads;
-        wk[W_LENTRIES] += st.lentries; wk[W_STOPS] += st.stops; wk[W_STOPCH] += st.stopch;
-        wk[W_SQUERIES] += st.squeries; wk[W_SPAN] += st.span;
-    }
-    return vote_window<KIND, COUNT, G, VOTE>(a, lds, chrom, s, e, imprecise, n, wk, support);
-}
-
-// After the gather: n candidates in lds.cand (the first CAP of them) -> consensus_pos.
-template <int KIND, bool COUNT, int G, int VOTE>
-__device__ __forceinline__ int32_t vote_window(const KArgs &a, WinLds &lds, int chrom, uint32_t s, uint32_t e,
-                                               uint32_t imprecise, int32_t n, unsigned long long *wk, int32_t &support) {
-    support = 0;
-    if (n < a.prm.min_count) return -1;                    // refinement.c:43-45 (sliding: no support >= min_count)
-    if (SVT_DIAG == 4) return n;   // diagnostic build: no sort/vote
-    if (n <= CAP) return sort_and_vote<VOTE>(lds.cand, lds.pre, n, (int32_t)imprecise, a.prm, support);
-    // spill: a slab for N ints + (n+1) int64 from the device pool, then re-gather into it
-    if (COUNT && lane_id() == 0) wk[W_SPILLED] += 1;
-    int N = 1;
-    while (N < n) N <<= 1;
-    unsigned long long words = (unsigned long long)N + 2ull * (unsigned long long)(n + 2);
-    // the pool restarts for every launch: a head word tagged with another launch's epoch
-    // counts as empty (no per-launch reset on the host)
-    unsigned long long base = 0;
-    if (lane_id() == 0) {
-        unsigned long long old = __hip_atomic_load(a.pool_head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), seen;
-        do {
-            seen = old;
-            base = (uint32_t)(seen >> 40) == a.epoch ? (seen & ((1ull << 40) - 1ull)) : 0ull;
-            old = atomicCAS(a.pool_head, seen, ((unsigned long long)a.epoch << 40) | (base + words));
-        } while (old != seen);
-    }
-    base = rdlane64(base, 0);
-    if (base + words > a.pool_words) {
-        if (lane_id() == 0) atomicOr(a.status, 1);
-        return -1;
-    }
-    int32_t *g = a.pool + base;
-    int64_t *gp = (int64_t *)(a.pool + ((base + (unsigned long long)N + 1ull) & ~1ull));
-    WinStats st2;
-    Sink s2{g, N, &lds.ncand};
-    gather<KIND, false, G>(a, chrom - 1, s, e, s2, st2, lds);
-    if (VOTE == V_CONSENSUS) {   // the exact band first: usually small enough for the register sort
-        Band bd;
-        const int32_t nb = band_filter_large(g, n, (int32_t)imprecise, a.prm, bd);
-        if (bd.on && nb <= CAP) {
-            for (int32_t i = lane_id(); i < nb; i += WAVE) lds.cand[i] = g[i];
-            wave_sync();
-            return sort_and_vote<VOTE>(lds.cand, lds.pre, nb, (int32_t)imprecise, a.prm, support, &bd);
-        }
-        if (bd.on) return sort_and_vote<VOTE, true>(g, gp, nb, (int32_t)imprecise, a.prm, support, &bd);
-    }
-    return sort_and_vote<VOTE, true>(g, gp, n, (int32_t)imprecise, a.prm, support);
-}
-
 constexpr int LV_WMAX = 1023;   // band half-width for 16-bit offsets and prefix sums (32 * 2046 < 2^16)
 
+#include "svt_wave.inc"
+#include "svt_gather.inc"
+#include "svt_vote.inc"
 #include "svt_bucket.inc"
-
-// One wave per query window, WPB independent waves per workgroup.  Window g < n is locus
-// g's first window (DEL: refine_start over [pos-wider, pos+narrow], INS: refine_ins),
-// window n + i is locus i's second (DEL: refine_end over end +- narrow): the wide windows
-// are dispatched first, so the short ones fill the tail.
-// (Workgroups in dispatch order: an XCD-aware swizzle -- each XCD a contiguous run of
-// neighbouring loci -- measured slower, 37.1 vs 35.3 us on cfg2: the launch's records stay in
-// the MALL across launches, so L2 locality buys nothing.)
-constexpr int WPB = 4;
-
-// The refine kernels are held to 64 VGPRs = 8 waves per SIMD (the CU's maximum): their walks
-// are bound by dependent-load latency, so resident waves are what hide it.
-#ifndef SVT_REFINE_WAVES
-#define SVT_REFINE_WAVES 8
-#endif
-#define SVT_OCC __attribute__((amdgpu_waves_per_eu(SVT_REFINE_WAVES, SVT_REFINE_WAVES)))
-// refine_lane_kernel at 64 windows per wave: the windows per round of its phases 0-1 and the waves
-// per SIMD its LDS allows (LaneLds<64, 32>: 5 632 B a wave, 7 workgroups a CU; <64, 64>: 6 400 B, 6).
-#ifndef SVT_WIDE_R
-#define SVT_WIDE_R 32
-#endif
-#ifndef SVT_WIDE_OCC
-#define SVT_WIDE_OCC (SVT_WIDE_R == 32 ? 7 : 6)
-#endif
-// Windows a launch needs for 64 per wave (svt_ctx::launch): the 250K-window launch of a 125K-locus
-// shard is the smallest measured, and 64 per wave wins there (0.118 vs 0.127 ms a step at 32,
-// profiles/e0260); smaller launches keep 32 per wave.
-constexpr size_t LANE_WIDE_MIN = 250000;
-template <bool COUNT, int G>
-__device__ __forceinline__ void refine_body(const KArgs &a);
-
-template <bool COUNT, int G>
-__global__ __launch_bounds__(64 * WPB) void refine_kernel(KArgs a) { refine_body<COUNT, G>(a); }
-
-__global__ __launch_bounds__(64 * WPB) SVT_OCC void refine_span_kernel(KArgs a) { refine_body<false, G_SPAN>(a); }
-
-__device__ __forceinline__ void write_result(const KArgs &a, uint32_t li, uint32_t w, uint32_t r) {
-    if (a.rec_out) {   // gather record {index, start, end, 0}
-        uint32_t *o = reinterpret_cast<uint32_t *>(a.rec_out + li);
-        o[1 + w] = r;
-        if (w == 0) {
-            o[0] = a.rec_index ? a.rec_index[li] : a.rec_base + li;
-            o[3] = 0u;
-        }
-    } else {
-        uint32_t *o = reinterpret_cast<uint32_t *>(a.out + li);
-        o[w] = r;
-    }
-}
-
-// The gather of one window kind (+ the COUNT builds' work counters); the candidates are
-// left in lds.cand, their count is returned.
-template <int KIND, bool COUNT, int G>
-__device__ __forceinline__ int32_t gather_window(const KArgs &a, WinLds &lds, int chrom, uint32_t s, uint32_t e,
-                                                 unsigned long long *wk) {
-    WinStats st;
-    Sink sink{lds.cand, CAP, &lds.ncand};
-    const int32_t n = gather<KIND, COUNT, G>(a, chrom - 1, s, e, sink, st, lds);
-    if (COUNT && lane_id() == 0) {
-        wk[W_WINDOWS] += 1; wk[W_READS] += st.reads; wk[W_OPS] += st.ops; wk[W_CANDS] += (unsigned long long)n;
-        wk[W_QUERIES] += st.queries; wk[W_PROBE] += st.probe; wk[W_RANGE] += st.range; wk[W_LREADS] += st.lreads;
-        wk[W_LENTRIES] += st.lentries; wk[W_STOPS] += st.stops; wk[W_STOPCH] += st.stopch;
-        wk[W_SQUERIES] += st.squeries; wk[W_SPAN] += st.span;
-    }
-    return n;
-}
-
-template <bool COUNT, int G>
-__device__ __forceinline__ void refine_body(const KArgs &a) {
-    __shared__ WinLds lds_all[WPB];
-    const uint32_t wid = threadIdx.x >> 6;
-    const uint32_t g = blockIdx.x * WPB + wid;
-    if (g >= 2 * a.n) return;
-    WinLds &lds = lds_all[wid];
-    const uint32_t w = g >= a.n ? 1u : 0u, li = g - w * a.n;
-    const svt_locus L = a.loci[li];
-    const int32_t type = uniform_i(L.type), chrom = uniform_i(L.chrom);
-    const uint32_t pos = (uint32_t)uniform_i((int32_t)L.pos), end = (uint32_t)uniform_i((int32_t)L.end);
-    unsigned long long wk[W_N] = {};
-    const KParams &k = a.prm;
-    // A2 (audit.c:176-225): the window of this wave.  INV: refine_point collects only when
-    // sv_type == SV_INS (refinement.c:250), so both windows vote on 0 candidates -> -1 for
-    // every min_count >= 1 (validated): NA, NA.
-    int kind = -1;
-    uint32_t s = 0, e = 0, imp = 0;
-    if (type == T_INS && w == 0) {
-        kind = K_INS; s = pos - (uint32_t)k.median; e = pos + (uint32_t)k.median; imp = pos;
-    } else if (type == T_DEL) {
-        if (w == 0) { kind = K_START; s = pos - (uint32_t)k.wider; e = pos + (uint32_t)k.narrow; imp = pos; }
-        else { kind = K_END; s = end - (uint32_t)k.narrow; e = end + (uint32_t)k.narrow; imp = end; }
-    }
-    uint32_t r = SVT_NA;
-    // the value buckets first (svt_bucket.inc); the span lists for the windows they do not take
-    const bool bk_done = !COUNT && kind >= 0 && refine_any_bk<false>(a, lds, kind, chrom, s, e, imp, wk, r);
-    if (kind >= 0 && !bk_done) {
-        // the kind-specific gathers, then ONE copy of the sort + vote for all kinds (code size:
-        // the three inlined copies of the vote no longer compete for the instruction cache)
-        int32_t n;
-        if (kind == K_INS) n = gather_window<K_INS, COUNT, G>(a, lds, chrom, s, e, wk);
-        else if (kind == K_START) n = gather_window<K_START, COUNT, G>(a, lds, chrom, s, e, wk);
-        else n = gather_window<K_END, COUNT, G>(a, lds, chrom, s, e, wk);
-        n = uniform_i(n);
-        int32_t sup = 0;
-        if (n < k.min_count) r = SVT_NA;                    // refinement.c:43-45
-        else if (SVT_DIAG == 4) r = (uint32_t)n;           // diagnostic build: no sort/vote
-        else if (n <= CAP) r = (uint32_t)sort_and_vote<V_CONSENSUS>(lds.cand, lds.pre, n, (int32_t)imp, k, sup);
-        else if (kind == K_INS) r = (uint32_t)vote_window<K_INS, COUNT, G, V_CONSENSUS>(a, lds, chrom, s, e, imp, n, wk, sup);
-        else if (kind == K_START) r = (uint32_t)vote_window<K_START, COUNT, G, V_CONSENSUS>(a, lds, chrom, s, e, imp, n, wk, sup);
-        else r = (uint32_t)vote_window<K_END, COUNT, G, V_CONSENSUS>(a, lds, chrom, s, e, imp, n, wk, sup);
-        if (COUNT) {   // what the bucket path reads for this window (its result is the same)
-            wave_sync();
-            uint32_t rb = 0;
-            (void)refine_any_bk<true>(a, lds, kind, chrom, s, e, imp, wk, rb);
-        }
-    }
-    if (lane_id() == 0) {
-        write_result(a, li, w, r);
-        if (COUNT)
-            for (int i = 0; i < W_N; i++)
-                if (wk[i]) atomicAdd(a.work + i, wk[i]);
-    }
-}
-
-// ------------------------------------------------------------------ lane-vote kernel
-// The default timed kernel.  A wave takes LV_W consecutive windows.  Phase 1, per window
-// and wave-wide: the A2 window, the span query and walk (A3-A7) and the exact band filter
-// (band_filter); a window whose band holds <= LV_CAP elements, all >= 0, within +-1023 of
-// pos (the common case: ~20 candidates of its own breakpoint) is staged in LDS as 16-bit
-// offsets from the band's low end, with the band's three whole-multiset facts.  Phase 2,
-// one LANE per staged window: an in-register sorting network over the lane's offsets,
-// 16-bit prefix sums, and consensus_pos (refinement.c:41-101) run per lane as the
-// reference's own loops -- with the cluster starts/ends as two pointers that only move
-// one way along a pass -- so the sort and the vote cost a few instructions per window
-// instead of a wave-wide network and per-lane searches for every window.  Phase 3: the
-// other windows (band off, > LV_CAP band elements, > CAP candidates) are re-gathered and
-// voted wave-wide (refine_window), as refine_span_kernel does.  Same results.
-// Windows per wave (<= 64: one lane each in phase 2): 64, so that the sort network and the
-// vote's loops issue with every lane at work -- taken through phases 0-1 in two rounds of 32,
-// which keeps the win table and so the wave's LDS small (7 waves per SIMD) -- or 32 for
-// launches too small to fill the chip with 64 per wave (svt_ctx::launch).
-constexpr int LV_CAP = 32;   // band elements a lane votes on
-constexpr int LV_S = 34;     // u16 per staged row (17 words: odd -> no bank conflicts)
-static_assert(LV_S > LV_CAP, "a staged row needs a spare slot past LV_CAP");
-// LV_BELOW / LV_ABOVE: some candidate lies at or below the band's low end / at or above its high
-// end (with the band itself they give band_filter's whole-multiset facts, see lane_vote)
-constexpr uint32_t LV_PENDING = 1u << 8, LV_BELOW = 1u << 9, LV_ABOVE = 1u << 10,
-                   LV_REDO = 1u << 13;
-
-// A window's flags word (LaneLds::flags): nb | LV_* bits.  It is the only per-window fact another
-// lane writes in phase 1; the band's low end stays in the owning lane's registers.
-constexpr uint32_t LV_NONE = 1u << 14;   // no window (INV / other types): NA
-// diagnostic build 11: why a window left the lane path (bits 16+), reported as its result
-#if SVT_DIAG == 11
-#define LV_WHY(r) ((uint32_t)(r) << 16)
-#else
-#define LV_WHY(r) 0u
-#endif
-
-// Phase 1's packed walk: the windows with a span to walk, in wave order, one entry
-// each (written by their phase-0 lanes); consecutive windows of <= 64 events together share
-// one 64-event slot.
-// (24 B: the band's low end is not kept -- lv_lo gives it back from s and the kind -- so that
-// the wide kernel's LDS leaves room for 6-7 waves per SIMD.)
-constexpr uint32_t LVW_BELOW = 1u << 16;
-struct alignas(8) LvWin {
-    uint64_t e0;    // the span's first event
-    uint32_t s, e;  // the window
-    uint32_t kl;    // kind | the window's row << 8 | LVW_BELOW (value buckets: the prefix maxima below
-                    // the band's buckets hold a candidate)
-    uint32_t len;   // span events (> 0)
-};
-// The band's low end pos - (range + max(ci, 0)) from the window's start: s = pos - wider / median /
-// narrow in uint32 (window_of), so s + that width is pos again, bit for bit.
-__device__ __forceinline__ int32_t lv_lo(const KParams &k, uint32_t kind, uint32_t s, int32_t bw) {
-    const int32_t d = kind == (uint32_t)K_INS ? k.median : kind == (uint32_t)K_START ? k.wider : k.narrow;
-    return (int32_t)(s + (uint32_t)d) - bw;
-}
-
-// W rows for phase 2 (one lane each), R windows per round of phases 0-1 (the win table is per round).
-template <int W, int R>
-struct LaneLds {
-    uint16_t stage[W * LV_S];   // band offsets (phase 1 -> 2)
-    uint32_t flags[W];
-    LvWin win[R];
-    uint32_t sink[WAVE];        // lane_walk: the store target of lanes without a band member
-};
-
-// Phase 1 of one window, wave-wide (A4-A7 + the band): the window's span events [E0, E0+len)
-// are tested 64 * LW_U at a time (LW_U 16-B loads per lane in flight), and each candidate goes
-// straight to the exact band of consensus_pos (band_filter's rule, see there): members in
-// (lo, hi) are written to the window's row as 16-bit offsets from lo, and whether any candidate
-// lies at or below lo / at or above hi is accumulated per lane (with the band they give the
-// whole-multiset facts, lane_vote).  Values are walk positions < 2^29 + 1 (reads reaching 2^28
-// bases or position 2^29 are slow and carry no events), so every candidate is >= 0 and within
-// +-2^30: no int64 path is ever needed.  refine_end's leading-S reads whose walk passes e count
-// as one candidate at or above the band's high end (KParams::sent_ok).
-struct LaneBand {
-    int32_t nb;       // band members (> LV_CAP: the row overflowed)
-    uint32_t flags;   // LV_BELOW | LV_ABOVE
-};
-
-constexpr int LW_U = 4;   // 64-event slots per step of lane_walk (loads in flight per lane)
-// lane_walk reads the span through a buffer descriptor of the window's own span (wave-uniform
-// base and byte count): a lane's byte offset is the constant ln * 16 (+ the slot's immediate
-// offset), so a load costs no VALU address arithmetic, and a load past the span returns zeros --
-// an op-0 (M) event, never a candidate -- so no clamp and no partial-slot mask either.  Spans of
-// 2^27 events or more take the wave-wide path (LvQuery), so the byte count fits 32 bits.
-constexpr uint32_t LW_BUF_MAX = 1u << 27;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-// The min_count test (refinement.c:43) is made on the band size instead of the candidate count.
-// Exact: an accepted cluster lies inside the band (its elements are within ci of an element
-// within range of pos), so the vote returns -1 whenever the band holds fewer than min_count
-// elements, and n < min_count implies nb < min_count.  The walk then keeps no count.
-
-// One slot as vector arithmetic.  The kernel is bound by scalar issue (one SALU instruction per
-// CU and cycle): every test is the sign bit of a difference ("fail" bits), OR-ed per lane; the
-// band is one unsigned compare whose lane mask is the only ballot, and below / above accumulate
-// as sign bits in VGPRs (one ballot each per window).  Exact: the operands' ranges keep every
-// difference inside int32 -- walk positions and candidate values <= 2^30 + 2^28 + 1 (IX_SAT, one
-// op < 2^28), endpos in [1, 2^30) (slow reads carry no events), e < 2^30 (WEXACT),
-// lo >= -2^29 (lane_query), the window start clamped (LwWin).
-struct LwWin {
-    int32_t b1;     // max(s - 1, -2^30) + 1: the overlap test endpos > s - 1 is endpos - b1 >= 0
-    uint32_t e;
-    int32_t sc;     // s, or 2^31 - 1 when s >= 2^31 (a window start that wrapped: x >= s never holds)
-    int32_t lo1;    // lo + 1: a value v is at or below the band when v - lo1 < 0
-    int32_t hm1;    // hi - 1: at or above it when hm1 - v < 0
-    uint32_t wb;    // hi - lo - 1: in the band when (uint32)(v - lo1) < wb
-    int32_t em2;    // e - 2 (value buckets: the event's read is yielded when its pos <= e - 2)
-};
-__device__ __forceinline__ uint32_t sgn(int32_t d) { return (uint32_t)d >> 31; }
-__device__ __forceinline__ uint32_t opbit(uint32_t set, uint32_t op) { return __builtin_amdgcn_ubfe(set, op, 1); }
-
-// One 64-event slot: the band's lane mask; below / above accumulated into the sign bits of
-// belv / abv; iv = the lane's candidate value.
-template <int KIND, bool BK>
-__device__ __forceinline__ uint64_t slot_vl(const uint4 &v, const LwWin &W, uint32_t &belv, uint32_t &abv, int32_t &iv) {
-    const uint32_t op = v.y & 0xfu;
-    // value buckets: the event's read must also be yielded (its pos -- v.w, v.x for a leading S --
-    // below the query end); a span holds only yielded reads' events
-    const uint32_t yld = BK ? sgn(W.em2 - (int32_t)v.w) : 0u;
-    const uint32_t far = sgn((int32_t)v.z - W.b1) | sgn((int32_t)W.e - (int32_t)v.x) | yld;   // no overlap / not reached
-    uint32_t fail;
-    if (BK && KIND == K_END) {                                            // :188, :210-220
-        const uint32_t isD = opbit(1u << OP_DEL, op), isL = opbit(1u << SP_LEAD, op);
-        const uint32_t lead = isL & (sgn((int32_t)v.z - W.b1) ^ 1u) & (sgn((int32_t)v.x - W.sc) ^ 1u) &
-                              (sgn(W.em2 - (int32_t)v.x) ^ 1u);
-        const uint32_t brk = lead & sgn((int32_t)W.e - (int32_t)v.w);   // walk passes e: a value >= e + 2
-        abv |= brk << 31;
-        fail = ((isD & (far ^ 1u)) | (lead & (brk ^ 1u))) ^ 1u;
-        iv = (int32_t)(isD ? v.x + (v.y >> 4) + 1u : v.w + 1u);
-    } else if (KIND == K_INS) {                                           // refinement.c:299
-        fail = far | (opbit(1u << OP_INS, op) ^ 1u);
-        iv = (int32_t)v.x;
-    } else if (KIND == K_START) {                                         // :124, :147
-        fail = far | (opbit(1u << OP_DEL | 1u << SP_TRAIL, op) ^ 1u) |
-               (opbit(1u << SP_TRAIL, op) & sgn((int32_t)v.x - W.sc));
-        iv = (int32_t)v.x;
-    } else {                                                              // :188, :210-220
-        const uint32_t isD = opbit(1u << OP_DEL, op);
-        const uint32_t lead = opbit(1u << SP_LEAD, op) & (far ^ 1u) & (sgn((int32_t)v.x - W.sc) ^ 1u);
-        const uint32_t brk = lead & sgn((int32_t)W.e - (int32_t)v.w);   // walk passes e: a value >= e + 2
-        abv |= brk << 31;
-        fail = ((isD & (far ^ 1u)) | (lead & (brk ^ 1u))) ^ 1u;
-        iv = (int32_t)(isD ? v.x + (v.y >> 4) + 1u : v.w + 1u);
-    }
-    const uint32_t d = (uint32_t)(iv - W.lo1);
-    const uint32_t pass = (fail ^ 1u) << 31;
-    belv |= d & pass;
-    abv |= (uint32_t)(W.hm1 - iv) & pass;
-    return ballot((d | fail << 31) < W.wb);
-}
-
-// The window's scalar inputs (base address of its span, span length, LwWin, lo, its staging
-// row) come from the caller's v_readlane of per-lane values computed once per wave.  Every lane
-// stores in every slot -- members to their row slot, the others to their own sink word -- so a
-// slot costs no exec-mask round trip on the scalar unit.
-template <int KIND, bool BK>
-__device__ __forceinline__ LaneBand lane_walk(uint64_t evaddr, uint32_t len, const LwWin &W, int32_t lo, uint16_t *row,
-                                              uint16_t *sink) {
-    const int ln = lane_id();
-    int32_t nb = 0;
-    uint32_t belv = 0, abv = 0;
-    for (uint32_t b = 0; b < len; b += LW_U * WAVE) {
-        const uint32_t left = len - b;
-        uint4 v[LW_U];
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            reinterpret_cast<void *>(evaddr + (uint64_t)b * 16u), (short)0, (int)(left * 16u), 0x00020000);
-#pragma unroll
-        for (int u = 0; u < LW_U; u++) {   // all four in flight at once; past the span: zeros
-            const u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(rs, ln * 16 + u * WAVE * 16, 0, 0);
-            v[u] = make_uint4(r.x, r.y, r.z, r.w);
-        }
-#pragma unroll
-        for (int u = 0; u < LW_U; u++) {
-            if ((uint32_t)(u * WAVE) >= left) break;
-            int32_t iv;
-            const uint64_t mb = slot_vl<KIND, BK>(v[u], W, belv, abv, iv);
-            // members past LV_CAP all land in the row's spare slot LV_CAP (the window is redone);
-            // the slot is computed by every lane (the empty asm keeps the compiler from moving it
-            // under a branch on the member mask), then one select
-            uint32_t at = (uint32_t)min(nb + (int32_t)mbcnt(mb), LV_CAP);
-            asm volatile("" : "+v"(at));
-            uint16_t *dst = __builtin_amdgcn_inverse_ballot_w64(mb) ? row + at : sink;
-            *dst = (uint16_t)(iv - lo);
-            nb += (int32_t)__popcll(mb);
-        }
-    }
-    const uint64_t below = ballot((int32_t)belv < 0), above = ballot((int32_t)abv < 0);
-    return LaneBand{nb, (below ? LV_BELOW : 0u) | (above ? LV_ABOVE : 0u)};
-}
-
-// Two windows of the same kind with 65-128 span events each, walked together: their four slots'
-// loads are in flight at once, so the pair costs one memory round trip instead of two (phase 1
-// is a chain of one round trip per window per wave, ~24 a wave on cfg4).
-struct LwOne {
-    uint64_t base;
-    uint32_t len;
-    LwWin W;
-    int32_t lo;
-    uint16_t *row;
-};
-template <int KIND, bool BK>
-__device__ __forceinline__ void lane_walk2(const LwOne &A, const LwOne &B, uint16_t *sink, LaneBand &ra, LaneBand &rb) {
-    const int ln = lane_id();
-    const __amdgpu_buffer_rsrc_t sa = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(A.base), (short)0,
-                                                                        (int)(A.len * 16u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t sb = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(B.base), (short)0,
-                                                                        (int)(B.len * 16u), 0x00020000);
-    uint4 v[4];
-    {
-        const u32x4 r0 = __builtin_amdgcn_raw_buffer_load_b128(sa, ln * 16, 0, 0);
-        const u32x4 r1 = __builtin_amdgcn_raw_buffer_load_b128(sa, ln * 16 + WAVE * 16, 0, 0);
-        const u32x4 r2 = __builtin_amdgcn_raw_buffer_load_b128(sb, ln * 16, 0, 0);
-        const u32x4 r3 = __builtin_amdgcn_raw_buffer_load_b128(sb, ln * 16 + WAVE * 16, 0, 0);
-        v[0] = make_uint4(r0.x, r0.y, r0.z, r0.w);
-        v[1] = make_uint4(r1.x, r1.y, r1.z, r1.w);
-        v[2] = make_uint4(r2.x, r2.y, r2.z, r2.w);
-        v[3] = make_uint4(r3.x, r3.y, r3.z, r3.w);
-    }
-#pragma unroll
-    for (int w = 0; w < 2; w++) {
-        const LwOne &O = w ? B : A;
-        int32_t nb = 0;
-        uint32_t belv = 0, abv = 0;
-#pragma unroll
-        for (int u = 0; u < 2; u++) {
-            int32_t iv;
-            const uint64_t mb = slot_vl<KIND, BK>(v[2 * w + u], O.W, belv, abv, iv);
-            uint32_t at = (uint32_t)min(nb + (int32_t)mbcnt(mb), LV_CAP);
-            asm volatile("" : "+v"(at));
-            uint16_t *dst = __builtin_amdgcn_inverse_ballot_w64(mb) ? O.row + at : sink;
-            *dst = (uint16_t)(iv - O.lo);
-            nb += (int32_t)__popcll(mb);
-        }
-        const uint64_t below = ballot((int32_t)belv < 0), above = ballot((int32_t)abv < 0);
-        (w ? rb : ra) = LaneBand{nb, (below ? LV_BELOW : 0u) | (above ? LV_ABOVE : 0u)};
-    }
-}
-
-// One 64-event slot holding the whole spans of consecutive walkable windows win[c0..]: bit i of
-// M marks the first lane of a window (bit 0 always), tot <= 64 events in all.  Lane j walks
-// event j - f of the window that starts at f = the highest mark <= j, with that window's own
-// s / e / band (the tests of span_cand_mask, per lane); members go to the window's row at
-// their rank among its members, and each window's first lane writes its flags word (band size,
-// below / above) -- everything lane_walk gives a window, for 1-64 events at once.
-// The event lane ln tests in the packed slot of windows win[c0..] with marks M (value buckets: one
-// event array) -- loaded ahead of the slot's tests so that a run of packed slots keeps the next
-// slot's loads in flight while the current one is tested.
-__device__ __forceinline__ uint4 lane_packed_load(const BkIndex &B, const LvWin *win, uint32_t c0, uint64_t M) {
-    const int ln = lane_id();
-    const uint64_t upto = M & ((2ull << ln) - 1ull);
-    const uint32_t r = (uint32_t)__popcll(upto) - 1u, f = 63u - (uint32_t)__clzll(upto);
-    const LvWin &w = win[c0 + r];
-    return B.ev[w.e0 + min((uint32_t)ln - f, w.len - 1u)];
-}
-
-template <bool BK>
-__device__ __forceinline__ void lane_packed(const DevPileup &P, const BkIndex &B, const KParams &prm, const LvWin *win,
-                                            uint32_t *flags, uint16_t *stage, uint32_t c0, uint64_t M, uint32_t tot,
-                                            int32_t bw2, const uint4 *vpre = nullptr) {
-    const int ln = lane_id();
-    const uint64_t upto = M & ((2ull << ln) - 1ull);   // marks at or below this lane (ln 63: all)
-    const uint32_t r = (uint32_t)__popcll(upto) - 1u, f = 63u - (uint32_t)__clzll(upto);
-    const LvWin w = win[c0 + r];
-    const uint32_t kind = w.kl & 0xffu, k = (w.kl >> 8) & 0xffu;
-    const uint4 *evb = (BK ? B.ev : kind == (uint32_t)K_INS ? P.spI : P.spD) + w.e0;
-    const uint4 v = vpre ? *vpre : evb[min((uint32_t)ln - f, w.len - 1u)];   // lanes past tot: their window's last event
-    const uint32_t s = w.s, e = w.e, x = v.x, op = v.y & 0xfu;
-    const int32_t lo = lv_lo(prm, kind, s, bw2 >> 1);
-    const uint64_t isI = ballot(kind == (uint32_t)K_INS), isE = ballot(kind == (uint32_t)K_END);
-    const uint64_t oD = ballot(op == OP_DEL), sx = ballot(s <= x), oL = ballot(op == SP_LEAD);
-    const uint64_t ovl = ballot((int32_t)v.z > (int32_t)(s - 1u));
-    // value buckets: the event's read is yielded (pos < e - 1: v.w, or v.x for a leading S)
-    const uint64_t yw = BK ? ballot(v.w + 2u <= e) : ~0ull, yx = BK ? ballot(x + 2u <= e) : ~0ull;
-    const uint64_t base = ballot((uint32_t)ln < tot) & ovl & ballot(x <= e) & (yw | (isE & oL));
-    const uint64_t lead = ballot((uint32_t)ln < tot) & ovl & isE & oL & sx & (BK ? yx : ballot(x <= e));   // :210-220
-    const uint64_t brk = lead & ballot(v.w > e);
-    const uint64_t cm = (base & ((isI & ballot(op == OP_INS)) | (~(isI | isE) & (oD | (ballot(op == SP_TRAIL) & sx))) |
-                                 (isE & oD))) |
-                        (lead & ~brk);
-    const int32_t iv = (int32_t)(kind == (uint32_t)K_END ? (op == OP_DEL ? x + (v.y >> 4) + 1u : v.w + 1u) : x);
-    const uint64_t gt = ballot(iv > lo), lt = ballot(iv < lo + bw2);
-    const uint64_t mb = cm & gt & lt;
-    if ((mb >> ln) & 1ull) {
-        const uint32_t rank = mbcnt(mb) - (uint32_t)__popcll(mb & ((1ull << f) - 1ull));
-        stage[k * LV_S + min(rank, (uint32_t)LV_CAP)] = (uint16_t)(iv - lo);
-    }
-    if ((M >> ln) & 1ull) {   // the window's first lane: its totals over lanes [ln, ln + len)
-        const uint64_t rm = (w.len >= 64u ? ~0ull : ((1ull << w.len) - 1ull)) << ln;
-        const uint32_t nb = (uint32_t)__popcll(mb & rm);
-        const bool below = (cm & ~gt & rm) != 0ull, above = ((brk | (cm & ~lt)) & rm) != 0ull;
-        flags[k] = nb > (uint32_t)LV_CAP ? (LV_REDO | LV_WHY(3))
-                                         : nb | LV_PENDING | (below || (w.kl & LVW_BELOW) ? LV_BELOW : 0u) |
-                                               (above ? LV_ABOVE : 0u);
-    }
-}
-
-// Phase 0 fills every window's band slots with 0xffff, so phase 2 takes its band straight from
-// the row (no per-slot test against the band size).  The band is sorted by Batcher's odd-even
-// merge sort (19 / 63 / 191 compare-exchanges for 8 / 16 / 32 elements against 24 / 80 / 240 for
-// the bitonic network, all ascending).
-__device__ __forceinline__ void lv_cx(uint32_t (&x)[LV_CAP], int i, int j) {
-    const uint32_t p = x[i], q = x[j];
-    x[i] = min(p, q);
-    x[j] = max(p, q);
-}
-template <int LO, int N, int R>
-__device__ __forceinline__ void lv_oe_merge(uint32_t (&x)[LV_CAP]) {
-    if constexpr (2 * R < N) {
-        lv_oe_merge<LO, N, 2 * R>(x);
-        lv_oe_merge<LO + R, N, 2 * R>(x);
-#pragma unroll
-        for (int i = LO + R; i + R < LO + N; i += 2 * R) lv_cx(x, i, i + R);
-    } else {
-        lv_cx(x, LO, LO + R);
-    }
-}
-template <int LO, int N>
-__device__ __forceinline__ void lv_oe_sort(uint32_t (&x)[LV_CAP]) {
-    if constexpr (N > 1) {
-        lv_oe_sort<LO, N / 2>(x);
-        lv_oe_sort<LO + N / 2, N / 2>(x);
-        lv_oe_merge<LO, N, 1>(x);
-    }
-}
-
-// floor(x / c) for x < 2^17, 1 <= c <= 64: ((x + 1/2) * rcp(c)) lies at least 1/(2c) >= 2^-7
-// inside [q, q+1) exactly, and the f32 product is within 2^-9 of it (x + 1/2 < 2^17,
-// v_rcp_f32 within 1 ulp), so the truncation is exact.
-__device__ __forceinline__ uint32_t div_small(uint32_t x, uint32_t c) {
-    return (uint32_t)(((float)x + 0.5f) * __builtin_amdgcn_rcpf((float)c));
-}
-
-// consensus_pos (refinement.c:41-101) for one lane's staged window: B[0..nb) its band's
-// sorted offsets (value - lo), w = pos - lo.  Every band value is >= 0, so the reference's
-// rounded uint64 mean of a cluster is lo + (offset sum + c/2) / c.  The clusters are sliding
-// windows whose ends only move one way along each pass, so their sums are kept up to date
-// element by element (no prefix array).
-__device__ __forceinline__ int32_t lane_vote(const uint16_t *B, int32_t nb, int32_t w, int32_t lo, uint32_t fl,
-                                             const KParams &k, int32_t l0 = -1) {
-    const int32_t ci = k.ci, range = k.range;
-    int32_t valL = -1, maxL = k.min_count - 1, distL = 0x7fffffff;
-    int32_t valR = -1, maxR = k.min_count - 1, distR = 0x7fffffff;
-    // lower_bound(pos+25) over the band (refinement.c:3-10), started where the full pass would
-    // (l0 >= 0: the caller counted the band elements <= pos+25 already)
-    if (l0 < 0) {
-        int32_t h0 = nb;
-        l0 = 0;
-        while (l0 < h0) {
-            const int32_t md = (l0 + h0) >> 1;
-            if ((int32_t)B[md] > w + SV_MIN_LENGTH / 2) h0 = md; else l0 = md + 1;
-        }
-    }
-    // band_filter's whole-multiset facts: the band's own elements (B[0] its minimum) plus
-    // whether candidates lie below / above it
-    const bool below = fl & LV_BELOW, above = fl & LV_ABOVE;
-    const bool u0 = !below && l0 == 0;                                          // none <= pos+25
-    const bool lt = below || (nb > 0 && (int32_t)B[0] < w - SV_MIN_LENGTH / 2);   // some < pos-25
-    int32_t p = u0 ? 0 : l0 == 0 ? -1 : l0 - 1;
-    if (nb == 0) p = -1;
-    int32_t kk = p + 1, prev = 0;   // cluster [kk, i] below i, its offset sum S
-    uint32_t S = 0;
-    for (int32_t i = p; i >= 0; i--) {                                       // refinement.c:58
-        const int32_t a = B[i];
-        if (ref_abs(w - a) >= range) break;
-        if (i < p) S -= (uint32_t)prev;                                      // element i+1 leaves
-        if (kk > i) { kk = i; S = (uint32_t)a; }
-        while (kk > 0 && (int32_t)B[kk - 1] >= a - ci) { kk--; S += B[kk]; }   // :61-64
-        prev = a;
-        const int32_t c = i - kk + 1;
-        if (c > maxL) {                                                      // :67-76
-            const int32_t co = (int32_t)div_small(S + (uint32_t)(c / 2), (uint32_t)c);   // :65
-            const int32_t d = ref_abs(w - co);
-            if (d < ci) return lo + co;
-            if (d < distL) { maxL = c; valL = lo + co; distL = d; }
-        }
-    }
-    // upper_bound(pos-25) (refinement.c:12-19): the full multiset's A[0] / A[n-1]
-    const int32_t q = lt ? (!below ? 0 : nb) : (!above ? nb - 1 : nb);
-    int32_t m = q;   // cluster [i, m) above i
-    S = 0;
-    for (int32_t i = q; i < nb; i++) {                                       // :80
-        const int32_t a = B[i];
-        if (ref_abs(w - a) >= range) break;
-        if (i > q) S -= (uint32_t)prev;                                      // element i-1 leaves
-        if (m <= i) { m = i + 1; S = (uint32_t)a; }
-        while (m < nb && (int32_t)B[m] <= a + ci) { S += B[m]; m++; }        // :83-86
-        prev = a;
-        const int32_t c = m - i;
-        if (c > maxR) {                                                      // :88-97
-            const int32_t co = (int32_t)div_small(S + (uint32_t)(c / 2), (uint32_t)c);   // :87
-            const int32_t d = ref_abs(w - co);
-            if (d < ci) return lo + co;
-            if (d < distR) { maxR = c; valR = lo + co; distR = d; }
-        }
-    }
-    return distL < distR ? valL : valR;                                      // :100
-}
-
-// A2 (audit.c:176-225) for window g: kind (-1: none -> NA), s, e, pos of the vote.
-__device__ __forceinline__ int window_of(const KArgs &a, uint32_t g, uint32_t &li, uint32_t &w, int32_t &chrom,
-                                         uint32_t &s, uint32_t &e, uint32_t &imp) {
-    w = g >= a.n ? 1u : 0u;
-    li = g - w * a.n;
-    const svt_locus L = a.loci[li];
-    const int32_t type = uniform_i(L.type);
-    chrom = uniform_i(L.chrom);
-    const uint32_t pos = (uint32_t)uniform_i((int32_t)L.pos), end = (uint32_t)uniform_i((int32_t)L.end);
-    const KParams &k = a.prm;
-    // INV: refine_point collects only when sv_type == SV_INS (refinement.c:250): NA, NA
-    if (type == T_INS && w == 0) { s = pos - (uint32_t)k.median; e = pos + (uint32_t)k.median; imp = pos; return K_INS; }
-    if (type == T_DEL) {
-        if (w == 0) { s = pos - (uint32_t)k.wider; e = pos + (uint32_t)k.narrow; imp = pos; return K_START; }
-        s = end - (uint32_t)k.narrow; e = end + (uint32_t)k.narrow; imp = end;
-        return K_END;
-    }
-    return -1;
-}
-
-
-// One window's A2 + A3 answer, computed by one lane (phase 0).  u32 words only (the rows
-// it is parked in are 4-byte aligned).
-constexpr int32_t LQ_REDO = 1 << 4;   // kind bit: the window takes the wave-wide path
-struct LvQuery {
-    int32_t kind;          // K_* (| LQ_REDO), -1: no window (NA)
-    int32_t lo;            // the vote's band low end: pos - (range + max(ci, 0))
-    uint32_t s, e, liw, len;        // the window, li << 1 | w, its span's event count
-    uint32_t e0[2];                 // the span's first event
-    uint32_t fl;                    // value buckets: LV_BELOW from the prefix maxima
-};
-static_assert(sizeof(LvQuery) <= LV_S * 2, "LvQuery must fit a staging row");
-
-__device__ __forceinline__ void lane_query(const KArgs &a, uint32_t g, bool band_ok, LvQuery &q) {
-    const DevPileup &P = a.pile;
-    const KParams &k = a.prm;
-    const uint32_t w = g >= a.n ? 1u : 0u, li = g - w * a.n;
-    const svt_locus L = a.loci[li];
-    q.kind = -1;
-    q.liw = li << 1 | w;
-    const uint32_t pos = L.pos, end = L.end;
-    uint32_t imp = 0;
-    if (L.type == T_INS && w == 0) { q.kind = K_INS; q.s = pos - (uint32_t)k.median; q.e = pos + (uint32_t)k.median; imp = pos; }
-    else if (L.type == T_DEL && w == 0) { q.kind = K_START; q.s = pos - (uint32_t)k.wider; q.e = pos + (uint32_t)k.narrow; imp = pos; }
-    else if (L.type == T_DEL) { q.kind = K_END; q.s = end - (uint32_t)k.narrow; q.e = end + (uint32_t)k.narrow; imp = end; }
-    // INV: refine_point collects only when sv_type == SV_INS (refinement.c:250): NA, NA
-    if (q.kind < 0) return;
-    // the wave-wide path (refine_redo_kernel) when the window ends at or past WEXACT or is a
-    // refine_end window whose stops need the per-read replay (gather_span), when the band is off
-    // (band_ok) or pos is beyond +-2^30 (int32 differences could wrap)
-    constexpr int32_t LIM = 1 << 30;
-    if (q.e >= WEXACT || (q.kind == K_END && !k.sent_ok) || !band_ok || (int32_t)imp <= -LIM || (int32_t)imp >= LIM) {
-        q.kind |= LQ_REDO;
-        return;
-    }
-    q.lo = (int32_t)imp - (k.range + max(k.ci, 0));
-    if (q.lo < -(1 << 29)) { q.kind |= LQ_REDO; return; }   // (keeps slot_vl's differences in int32)
-    q.len = 0;   // empty span: no reads
-    const int tid = L.chrom - 1;
-    const int64_t beg = (int64_t)(uint32_t)(q.s - 1u), qend = (int64_t)(uint32_t)(q.e - 1u);
-    if (tid < 0 || tid >= P.n_targets || qend <= beg) return;   // A3: no reads
-    const int64_t ra = P.tid_off[tid], nr = P.tid_off[tid + 1] - ra;
-    if (nr == 0) return;
-    const int64_t b0 = P.bkt_off[tid], nb = P.bkt_off[tid + 1] - b0;   // last bucket = {nr, nr}
-    const int64_t bh = min(qend >> BKT_SHIFT, nb - 1), bl = min(beg >> BKT_SHIFT, nb - 1);
-    const uint2 h0 = P.bkt[b0 + bh], h1 = P.bkt[b0 + min(bh + 1, nb - 1)];
-    const uint2 l0 = P.bkt[b0 + bl], l1 = P.bkt[b0 + min(bl + 1, nb - 1)];
-    // hi = first read with pos >= qend in [h0.x, h1.x]; lo = first with emax > beg in [l0.y, l1.y]
-    int64_t hl = h0.x, hh = h1.x, ll = l0.y, lh = l1.y;
-    const int32_t *pp = P.pos + ra, *em = P.emax + ra;
-    while (hl < hh || ll < lh) {   // the two binary searches interleaved (their loads overlap)
-        const int64_t hm = (hl + hh) >> 1, lm = (ll + lh) >> 1;
-        const int32_t pv = hl < hh ? pp[hm] : 0, evv = ll < lh ? em[lm] : 0;
-        if (hl < hh) { if ((int64_t)pv >= qend) hh = hm; else hl = hm + 1; }
-        if (ll < lh) { if ((int64_t)evv > beg) lh = lm; else ll = lm + 1; }
-    }
-    const int64_t lo = ra + ll, hi = ra + hl;
-    if (lo >= hi) return;
-    const uint64_t *off = q.kind == K_INS ? P.spoffI : P.spoffD;
-    const uint64_t E0 = off[lo], E1 = off[hi];
-    // spans of 2^27 events or more: the wave-wide path (lane_walk's buffer byte count)
-    if (E1 - E0 >= (uint64_t)LW_BUF_MAX) { q.kind |= LQ_REDO; return; }
-    q.e0[0] = (uint32_t)E0; q.e0[1] = (uint32_t)(E0 >> 32);
-    q.len = (uint32_t)(E1 - E0);
-}
-
-// lane_query for the value buckets (svt_bucket.inc): A2, the window's eligibility, its band's bucket
-// span and the prefix maxima's BELOW -- no region query, no binary search (one dependent step after
-// the locus: the contig's bucket base, then the two bucket offsets and one prefix-max key).
-__device__ __forceinline__ void lane_query_bk(const KArgs &a, uint32_t g, LvQuery &q) {
-    const KParams &k = a.prm;
-    const uint32_t w = g >= a.n ? 1u : 0u, li = g - w * a.n;
-    const svt_locus L = a.loci[li];
-    q.kind = -1;
-    q.liw = li << 1 | w;
-    q.len = 0;
-    q.fl = 0;
-    const uint32_t pos = L.pos, end = L.end;
-    uint32_t imp = 0;
-    if (L.type == T_INS && w == 0) { q.kind = K_INS; q.s = pos - (uint32_t)k.median; q.e = pos + (uint32_t)k.median; imp = pos; }
-    else if (L.type == T_DEL && w == 0) { q.kind = K_START; q.s = pos - (uint32_t)k.wider; q.e = pos + (uint32_t)k.narrow; imp = pos; }
-    else if (L.type == T_DEL) { q.kind = K_END; q.s = end - (uint32_t)k.narrow; q.e = end + (uint32_t)k.narrow; imp = end; }
-    if (q.kind < 0) return;   // INV: refine_point collects only when sv_type == SV_INS (refinement.c:250): NA, NA
-    BkWin W;
-    const int el = bk_eligible(a, q.kind, L.chrom, q.s, q.e, imp, W);
-    if (el == 0) { q.kind |= LQ_REDO; return; }   // the span-list path (refine_redo_kernel)
-    q.lo = (int32_t)imp - (k.range + max(k.ci, 0));
-    if (el < 0) return;                            // A3: no reads -> nb = 0 -> NA
-    uint32_t E0, E1;
-    bool below;
-    bk_query(a.bk, q.kind, L.chrom - 1, W, E0, E1, below);
-    if (E1 - E0 >= LW_BUF_MAX) { q.kind |= LQ_REDO; return; }   // (lane_walk's buffer byte count)
-    q.e0[0] = E0;
-    q.e0[1] = 0u;
-    q.len = E1 - E0;
-    q.fl = below ? LV_BELOW : 0u;
-}
-
-// SVT_PHASE_PROF (diagnostic builds): every wave of refine_lane_kernel adds its phases' wall
-// time (100 MHz ticks) and work counts into ph_prof, read (and cleared) by svt_diag_phase.
-#ifndef SVT_PHASE_PROF
-#define SVT_PHASE_PROF 0
-#endif
-// PH(...) / PH_T(t): the instrumentation's statements, compiled out of the product.
-#if SVT_PHASE_PROF
-__device__ unsigned long long ph_prof[16];
-#define PH_ADD(i, v) atomicAdd(&ph_prof[i], (unsigned long long)(v))
-#define PH(...) __VA_ARGS__
-#define PH_T(t) const long long t = wall_clock64()
-#else
-#define PH(...)
-#define PH_T(t)
-#endif
-// LV_W windows per wave (phase 2: one lane each, so <= 64), taken through phases 0-1 LV_R at a
-// time (LV_R == LV_W: one round); OCC waves per SIMD (what the workgroup's LDS allows).
-template <int LV_W, int LV_R, int OCC, bool BK>
-__global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void refine_lane_kernel(KArgs a) {
-    static_assert(LV_W <= WAVE && LV_W % LV_R == 0, "one lane per window in phase 2, whole rounds");
-    __shared__ LaneLds<LV_W, LV_R> lds_all[WPB];
-    const uint32_t wid = threadIdx.x >> 6;
-    const int ln = lane_id();
-    const uint32_t g0 = (blockIdx.x * WPB + wid) * LV_W, nw = 2u * a.n;
-    if (g0 >= nw) return;
-    LaneLds<LV_W, LV_R> &L = lds_all[wid];
-    const KParams &k = a.prm;
-    const uint32_t cnt = min((uint32_t)LV_W, nw - g0);
-    const int32_t bw = k.range + max(k.ci, 0);   // the band's half-width
-    PH(long long ph_t0 = 0, ph_t1 = 0;)
-    const bool band_ok = k.range > SV_MIN_LENGTH / 2 && bw <= LV_WMAX && k.ci >= -LV_WMAX &&
-                         SVT_DIAG != 7;
-    // Window g0 + l is lane l's in phase 2: its row, its flags word, and (in registers) its band's
-    // low end; in a round of phases 0-1 it is lane l - r0's.
-    uint32_t aflags = 0;   // phase 1: the flags of a window walked alone, in its phase-2 lane
-    int32_t mylo = 0;
-#pragma nounroll
-    for (uint32_t r0 = 0; r0 < cnt; r0 += (uint32_t)LV_R) {
-    PH_T(pt0);
-    // ---- phase 0: every window's A2 + A3 at once, one lane each (the dependent loads of
-    // locus -> bucket words -> pos/emax searches -> span bounds run once per LV_R windows).
-    // The flags word is final here unless the window has a span to walk, and the walkable
-    // windows' table entries go to win[] in lane order.
-    uint32_t nwin;
-    {
-        const bool mine = (uint32_t)ln < min((uint32_t)LV_R, cnt - r0);
-        const uint32_t row = r0 + (uint32_t)ln;
-        LvQuery q{};
-        if (mine) {
-            if (BK) lane_query_bk(a, g0 + row, q);
-            else lane_query(a, g0 + row, band_ok, q);
-        }
-        const bool walk = mine && q.kind >= 0 && !(q.kind & LQ_REDO) && q.len != 0u;
-        if (mine) {
-            uint32_t *row32 = reinterpret_cast<uint32_t *>(L.stage + row * LV_S);
-#pragma unroll
-            for (int j = 0; j < LV_CAP / 2; j++) row32[j] = 0xffffffffu;   // unused band slots read as 0xffff
-            L.flags[row] = q.kind < 0 ? LV_NONE : (q.kind & LQ_REDO) ? (LV_REDO | LV_WHY(1)) : LV_PENDING;
-        }
-        if constexpr (LV_R < LV_W) {   // the band's low end moves to the window's phase-2 lane
-            const int32_t t = __shfl(q.lo, ln & (LV_R - 1), WAVE);
-            if (((uint32_t)ln & ~(uint32_t)(LV_R - 1)) == r0) mylo = t;
-        } else {
-            mylo = q.lo;
-        }
-        const uint64_t wm = ballot(walk);
-        if (walk) {
-            LvWin wn;
-            wn.e0 = (uint64_t)q.e0[0] | (uint64_t)q.e0[1] << 32;
-            wn.s = q.s;
-            wn.e = q.e;
-            wn.kl = (uint32_t)q.kind | row << 8 | (q.fl ? LVW_BELOW : 0u);
-            wn.len = q.len;
-            L.win[mbcnt(wm)] = wn;
-        }
-        nwin = (uint32_t)__popcll(wm);
-    }
-    wave_sync();
-    PH_T(pt1);
-    PH(ph_t0 += pt1 - pt0;)
-    if (SVT_DIAG == 6) {   // diagnostic build: phase 0 only (its answers written out, so it is not dead code)
-        const uint32_t g = g0 + r0 + (uint32_t)ln;
-        if (g < g0 + cnt && (uint32_t)ln < (uint32_t)LV_R) {
-            const LvWin wn = L.win[min((uint32_t)ln, nwin > 0 ? nwin - 1 : 0u)];
-            write_result(a, g >= a.n ? g - a.n : g, g >= a.n ? 1u : 0u, L.flags[r0 + (uint32_t)ln] ^ (uint32_t)wn.e0 ^ wn.len);
-        }
-        wave_sync();
-        continue;
-    }
-    // ---- phase 1 (packed): windows of <= 64 events share slots (lane_packed), longer ones are
-    // walked alone (lane_walk).  Lane c holds walkable window c's walk constants, computed here
-    // once for the wave; the scalar window loop reads them with v_readlane (no LDS round trip and
-    // no scalar arithmetic per window), and a window walked alone leaves its flags in lane kw of
-    // aflags (a v_cndmask on the lane index) instead of a store to its flags word.
-    {
-        const bool has = (uint32_t)ln < nwin;
-        const LvWin wv = L.win[has ? (uint32_t)ln : 0u];   // (entry 0 unused when nwin == 0)
-        const uint32_t lenv = has ? wv.len : 0u, klv = wv.kl & 0xffffu, ev = wv.e;
-        const uint32_t flv = wv.kl & LVW_BELOW ? LV_BELOW : 0u;
-        const int32_t em2v = (int32_t)(wv.e - 2u);
-        const int32_t lov = lv_lo(k, klv & 0xffu, wv.s, bw);
-        const int32_t b1v = max((int32_t)(wv.s - 1u), -(1 << 30)) + 1;
-        const int32_t scv = (int32_t)min(wv.s, 0x7fffffffu);
-        const uint64_t addrv = reinterpret_cast<uint64_t>(
-            (BK ? a.bk.ev : (klv & 0xffu) == (uint32_t)K_INS ? a.pile.spI : a.pile.spD) +
-            wv.e0);
-        uint16_t *sink = reinterpret_cast<uint16_t *>(&L.sink[ln]);
-        const int32_t bw2 = 2 * bw;
-        PH({ const uint32_t tl = rdlane(wave_scan_add(lenv), WAVE - 1); if (ln == 0) { PH_ADD(8, nwin); PH_ADD(9, tl); } })
-        for (uint32_t c = 0; c < nwin;) {
-            const uint32_t l0 = rdlane(lenv, (int)c);
-            PH(if (ln == 0) { if (l0 > (uint32_t)WAVE) { PH_ADD(10, 1); PH_ADD(11, (l0 + 255u) / 256u); } else PH_ADD(12, 1); })
-            if (l0 > (uint32_t)WAVE && l0 <= 2u * WAVE && c + 1u < nwin) {   // a pair of 2-slot windows?
-                const uint32_t l1 = rdlane(lenv, (int)(c + 1u));
-                const uint32_t ka = rdlane(klv, (int)c), kb = rdlane(klv, (int)(c + 1u));
-                if (l1 > (uint32_t)WAVE && l1 <= 2u * WAVE && ((ka ^ kb) & 0xffu) == 0u) {
-                    auto one = [&](uint32_t cc, uint32_t kl, uint32_t len) {
-                        const int32_t lo = rdlane_i(lov, (int)cc);
-                        return LwOne{rdlane64(addrv, (int)cc), len,
-                                     LwWin{rdlane_i(b1v, (int)cc), rdlane(ev, (int)cc), rdlane_i(scv, (int)cc), lo + 1,
-                                           lo + bw2 - 1, (uint32_t)(bw2 - 1), rdlane_i(em2v, (int)cc)},
-                                     lo, L.stage + (kl >> 8) * LV_S};
-                    };
-                    const LwOne A = one(c, ka, l0), B = one(c + 1u, kb, l1);
-                    LaneBand ra, rb;
-                    if ((ka & 0xffu) == (uint32_t)K_INS) lane_walk2<K_INS, BK>(A, B, sink, ra, rb);
-                    else if ((ka & 0xffu) == (uint32_t)K_START) lane_walk2<K_START, BK>(A, B, sink, ra, rb);
-                    else lane_walk2<K_END, BK>(A, B, sink, ra, rb);
-                    const uint32_t fa = ra.nb > LV_CAP ? (LV_REDO | LV_WHY(3))
-                                                       : (uint32_t)ra.nb | LV_PENDING | ra.flags | rdlane(flv, (int)c);
-                    const uint32_t fb = rb.nb > LV_CAP ? (LV_REDO | LV_WHY(3))
-                                                       : (uint32_t)rb.nb | LV_PENDING | rb.flags | rdlane(flv, (int)(c + 1u));
-                    aflags = (uint32_t)ln == (ka >> 8) ? fa : (uint32_t)ln == (kb >> 8) ? fb : aflags;
-                    c += 2u;
-                    continue;
-                }
-            }
-            if (l0 > (uint32_t)WAVE) {
-                const uint32_t kl = rdlane(klv, (int)c), kind = kl & 0xffu, kw = kl >> 8;
-                const int32_t lo = rdlane_i(lov, (int)c);
-                const LwWin W{rdlane_i(b1v, (int)c), rdlane(ev, (int)c), rdlane_i(scv, (int)c), lo + 1, lo + bw2 - 1,
-                              (uint32_t)(bw2 - 1), rdlane_i(em2v, (int)c)};
-                const uint64_t base = rdlane64(addrv, (int)c);
-                uint16_t *row = L.stage + kw * LV_S;
-                LaneBand r;
-                if (kind == (uint32_t)K_INS) r = lane_walk<K_INS, BK>(base, l0, W, lo, row, sink);
-                else if (kind == (uint32_t)K_START) r = lane_walk<K_START, BK>(base, l0, W, lo, row, sink);
-                else r = lane_walk<K_END, BK>(base, l0, W, lo, row, sink);
-                const uint32_t f = r.nb > LV_CAP ? (LV_REDO | LV_WHY(3)) : (uint32_t)r.nb | LV_PENDING | r.flags | rdlane(flv, (int)c);
-                aflags = (uint32_t)ln == kw ? f : aflags;
-                c++;
-                continue;
-            }
-            uint64_t M = 1ull;
-            uint32_t tot = l0, c1 = c + 1u;
-            for (; c1 < nwin; c1++) {
-                const uint32_t l = rdlane(lenv, (int)c1);
-                if (tot + l > (uint32_t)WAVE) break;
-                M |= 1ull << tot;
-                tot += l;
-            }
-            if (!BK) {
-                lane_packed<BK>(a.pile, a.bk, k, L.win, L.flags, L.stage, c, M, tot, bw2);
-                c = c1;
-                continue;
-            }
-            // value buckets: most windows hold < 64 events, so a wave's phase 1 is a run of packed
-            // slots -- each slot's events are loaded while the previous slot is tested (the loads,
-            // not the tests, were the run's length: one round trip per slot, ~9 slots a wave on cfg4)
-            uint4 v = lane_packed_load(a.bk, L.win, c, M);
-            for (;;) {
-                uint64_t Mn = 1ull;
-                uint32_t totn = 0, cn1 = c1;
-                const bool more = c1 < nwin && rdlane(lenv, (int)c1) <= (uint32_t)WAVE;
-                if (more) {
-                    totn = rdlane(lenv, (int)c1);
-                    for (cn1 = c1 + 1u; cn1 < nwin; cn1++) {
-                        const uint32_t l = rdlane(lenv, (int)cn1);
-                        if (totn + l > (uint32_t)WAVE) break;
-                        Mn |= 1ull << totn;
-                        totn += l;
-                    }
-                }
-                // (unconditional: a load under a branch would be waited for at the join)
-                const uint4 vn = lane_packed_load(a.bk, L.win, more ? c1 : c, more ? Mn : M);
-                lane_packed<BK>(a.pile, a.bk, k, L.win, L.flags, L.stage, c, M, tot, bw2, &v);
-                c = c1;
-                if (!more) break;
-                v = vn;
-                M = Mn;
-                tot = totn;
-                c1 = cn1;
-            }
-        }
-        wave_sync();
-    }
-    PH(ph_t1 += wall_clock64() - pt1;)
-    }   // (the round)
-    if (SVT_DIAG == 6) return;
-    PH_T(pt2);
-    const bool mine = (uint32_t)ln < cnt;
-    struct { int32_t lo; uint32_t liw, flags; } mt;   // the window's facts, in its own lane
-    {
-        const uint32_t g = g0 + (uint32_t)ln, w = g >= a.n ? 1u : 0u;
-        mt.lo = mylo;
-        mt.liw = (g - w * a.n) << 1 | w;
-        mt.flags = mine ? L.flags[ln] : 0u;
-    }
-    if (aflags) mt.flags = aflags;   // the window was walked alone
-    if (SVT_DIAG == 8) {   // diagnostic build: phases 0-1 only (a checksum of their LDS output written out)
-        if (mine) {
-            const uint32_t *row32 = reinterpret_cast<const uint32_t *>(L.stage + (uint32_t)ln * LV_S);
-            uint32_t h = mt.flags ^ (uint32_t)mt.lo;
-            for (int j = 0; j < LV_S / 2; j++) h = h * 31u + row32[j];
-            write_result(a, mt.liw >> 1, mt.liw & 1u, h);
-        }
-        return;
-    }
-    // ---- phase 2: one lane per staged window
-    uint64_t redo;   // the windows left over for refine_redo_kernel
-    {
-        // decisions: no window or fewer than min_count band members -> NA (refinement.c:43-45,
-        // LaneBand); the wave-wide path; or this lane's vote
-        const bool na = mine && ((mt.flags & LV_NONE) || (!(mt.flags & LV_REDO) && (int32_t)(mt.flags & 0xffu) < k.min_count));
-        if (na) write_result(a, mt.liw >> 1, mt.liw & 1u, SVT_NA);
-        redo = ballot(mine && !na && (mt.flags & LV_REDO));
-        const bool pend = mine && !na && !(mt.flags & LV_REDO) && (mt.flags & LV_PENDING);
-        const int32_t nb = pend ? (int32_t)(mt.flags & 0xffu) : 0;
-        const uint64_t any = ballot(pend);
-        if (any) {
-            uint32_t x[LV_CAP];
-            // lanes without a staged window use row 0 read-only (rows exist for LV_W lanes only)
-            uint16_t *row = L.stage + (pend ? (uint32_t)ln : 0u) * LV_S;
-            const uint32_t *row32 = reinterpret_cast<const uint32_t *>(row);
-#pragma unroll
-            for (int j = 0; j < LV_CAP; j += 2) {   // two offsets per 4-byte LDS read
-                const uint32_t v = row32[j >> 1];
-                x[j] = v & 0xffffu;   // (slots past the band hold 0xffff: phase 0)
-                x[j + 1] = v >> 16;
-            }
-            int32_t nmax = nb;   // wave max of nb: the smallest network that sorts every lane
-#pragma unroll
-            for (int d = 32; d > 0; d >>= 1) nmax = max(nmax, __shfl_xor(nmax, d, WAVE));
-            PH(if (ln == 0) PH_ADD(nmax <= 8 ? 13 : nmax <= 16 ? 14 : 15, 1));
-            if (nmax <= 8) lv_oe_sort<0, 8>(x);
-            else if (nmax <= 16) lv_oe_sort<0, 16>(x);
-            else lv_oe_sort<0, 32>(x);
-            uint32_t *wrow = reinterpret_cast<uint32_t *>(row);
-            int32_t l0 = 0;
-            if (pend) {
-#pragma unroll
-                for (int j = 0; j < LV_CAP; j += 2) wrow[j >> 1] = x[j] | x[j + 1] << 16;
-                // the band elements <= pos + 25, counted on the sorted registers (no search)
-#pragma unroll
-                for (int j = 0; j < LV_CAP; j++) l0 += (int32_t)(x[j] <= (uint32_t)(bw + SV_MIN_LENGTH / 2));
-                l0 = min(l0, nb);
-            }
-            // value buckets: ABOVE was only seen as far as the band's buckets; the vote reads it
-            // only when no candidate lies below pos - 25 (lane_vote's q) -- then the wave walks for
-            // it, window by window (bk_above: the bounded walks of svt_bucket.inc)
-            const bool needA = BK && pend && !(mt.flags & (LV_BELOW | LV_ABOVE)) &&
-                               (int32_t)x[0] >= bw - SV_MIN_LENGTH / 2;
-            if (BK && SVT_DIAG != 41 && SVT_DIAG != 43) {   // (41, 43: diagnostic builds, no ABOVE walks)
-                for (uint64_t na = ballot(needA); na; na &= na - 1ull) {
-                    const int l = __builtin_ctzll(na);
-                    uint32_t li, wi, ws = 0, we = 0, wimp = 0;
-                    int32_t chrom;
-                    const int kind = window_of(a, g0 + (uint32_t)l, li, wi, chrom, ws, we, wimp);
-                    BkWin W;
-                    bool ab = false;
-                    if (bk_eligible(a, kind, chrom, ws, we, wimp, W) == 1) {
-                        unsigned long long wk_ = 0;
-                        if (kind == K_INS) ab = bk_above<K_INS>(a.bk, chrom - 1, W, wk_);
-                        else if (kind == K_START) ab = bk_above<K_START>(a.bk, chrom - 1, W, wk_);
-                        else ab = bk_above<K_END>(a.bk, chrom - 1, W, wk_);
-                    }
-                    if (ln == l && ab) mt.flags |= LV_ABOVE;
-                }
-            }
-            if (SVT_DIAG == 42 || SVT_DIAG == 43) {   // diagnostic builds: no vote (42), no vote or ABOVE walks (43)
-                if (pend) write_result(a, mt.liw >> 1, mt.liw & 1u, x[0] + (uint32_t)l0 + (uint32_t)needA);
-            } else if (pend) {
-                const int32_t r = lane_vote(row, nb, bw, mt.lo, mt.flags, k, l0);
-                write_result(a, mt.liw >> 1, mt.liw & 1u, (uint32_t)r);
-            }
-        }
-        wave_sync();
-    }
-    PH_T(pt3);
-    // ---- the windows voted wave-wide go to refine_redo_kernel (rare: 0.6 % of cfg4's)
-    if (SVT_DIAG == 11) {   // diagnostic build: each left-over window's result = 0xF0000000 | its reason
-        if ((redo >> ln) & 1ull) write_result(a, mt.liw >> 1, mt.liw & 1u, 0xF0000000u | (mt.flags >> 16));
-        return;
-    }
-    if (SVT_DIAG == 9) {   // diagnostic build: count them (status word bits 8+), nothing else
-        if (ln == 0 && redo) atomicAdd(a.status, (int32_t)__popcll(redo) << 8);
-        return;
-    }
-    if (redo) {
-        uint32_t base = 0;
-        if (ln == 0) base = atomicAdd(a.redo_ctr, (uint32_t)__popcll(redo));
-        base = rdlane(base, 0);
-        if ((redo >> ln) & 1ull) a.redo_list[base + mbcnt(redo)] = g0 + (uint32_t)ln;
-    }
-    PH(if (ln == 0) { const long long pt4 = wall_clock64(); PH_ADD(0, ph_t0); PH_ADD(1, ph_t1); PH_ADD(2, pt3 - pt2); PH_ADD(3, pt4 - pt3); PH_ADD(4, 1); })
-}
-
-// The lane kernel's left-over windows (band off, > LV_CAP band elements, > CAP candidates,
-// slow reads, windows ending at or past 2^31), one wave each, re-gathered and voted
-// wave-wide (refine_window); the grid strides over the list.  Also resets the counter the
-// next launch will use.
-__global__ __launch_bounds__(64 * WPB) SVT_OCC void refine_redo_kernel(KArgs a) {
-    __shared__ WinLds lds_all[WPB];
-    const uint32_t wid = threadIdx.x >> 6;
-    const uint32_t gw = blockIdx.x * WPB + wid, nwv = gridDim.x * WPB;
-    if (gw == 0 && lane_id() == 0) *a.redo_next = 0u;
-    const uint32_t cnt = (uint32_t)uniform_i((int32_t)__hip_atomic_load(a.redo_ctr, __ATOMIC_RELAXED,
-                                                                         __HIP_MEMORY_SCOPE_AGENT));
-    WinLds &lds = lds_all[wid];
-    for (uint32_t idx = gw; idx < cnt; idx += nwv) {
-        const uint32_t g = (uint32_t)uniform_i((int32_t)a.redo_list[idx]);
-        uint32_t li, w, s = 0, e = 0, imp = 0;
-        int32_t chrom;
-        const int kind = window_of(a, g, li, w, chrom, s, e, imp);
-        unsigned long long wk[W_N];
-        int32_t sup;
-        uint32_t r = SVT_NA;
-        if (kind >= 0 && refine_any_bk<false>(a, lds, kind, chrom, s, e, imp, wk, r)) {}   // the value buckets
-        else if (kind == K_INS) r = (uint32_t)refine_window<K_INS, false, G_SPAN>(a, lds, chrom, s, e, imp, wk, sup);
-        else if (kind == K_START) r = (uint32_t)refine_window<K_START, false, G_SPAN>(a, lds, chrom, s, e, imp, wk, sup);
-        else if (kind == K_END) r = (uint32_t)refine_window<K_END, false, G_SPAN>(a, lds, chrom, s, e, imp, wk, sup);
-        if (lane_id() == 0) write_result(a, li, w, r);
-        wave_sync();
-    }
-}
-
-// sliding_window_ins mode (sliding_window.c:8-97): one wave per sub-window.  A sub-window
-// is refine_ins's window exactly -- the same region query (sub_start-1, sub_end-1, :27),
-// the same walk (I >= 50 collects rp, advance unless I/S, break when rp > sub_end,
-// :30-54) -- so it reuses the stream gather; only the vote differs (sw_vote).
-template <int G>
-__global__ __launch_bounds__(64 * WPB) void sw_kernel(KArgs a) {
-    __shared__ WinLds lds_all[WPB];
-    const uint32_t wid = threadIdx.x >> 6;
-    const uint32_t g = blockIdx.x * WPB + wid;
-    if (g >= a.n) return;
-    const uint4 q = a.sw_sub[g];
-    const int32_t chrom = uniform_i((int32_t)q.x);
-    const uint32_t s = (uint32_t)uniform_i((int32_t)q.y), e = (uint32_t)uniform_i((int32_t)q.z);
-    unsigned long long wk[W_N];
-    int32_t sup = 0;
-    const int32_t c = refine_window<K_INS, false, G, V_SLIDING>(a, lds_all[wid], chrom, s, e, 0u, wk, sup);
-    if (lane_id() == 0) a.sw_out[g] = make_int2(c, sup);
-}
-
-// bestCandidateOverall per query over its sub-windows in order (sliding_window.c:86-92).
-__global__ void sw_reduce_kernel(const int2 *sub, const uint64_t *off, uint32_t nq, int32_t *best) {
-    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= nq) return;
-    int32_t b = -1, m = 0;
-    for (uint64_t k = off[q]; k < off[q + 1]; k++) {
-        const int2 v = sub[k];
-        if (v.x != -1 && v.y > m) { m = v.y; b = v.x; }
-    }
-    best[q] = b;
-}
-
+#include "svt_refine.inc"
+#include "svt_lane.inc"
 #include "svt_evidence.inc"
 #include "svt_index.inc"
 #include "svt_index2.inc"
 #include "svt_bucket_build.inc"
 #include "svt_poa.inc"
 #include "svt_bam.inc"
-
 #include "svt_inflate.inc"
 
 }  // namespace
@@ -2315,7 +414,7 @@ svt_status launch(svt_ctx *c, const svt_locus *d_loci, svt_result *d_out, size_t
     a.rec_base = rec_base;
     dim3 grid((unsigned)((2 * n + WPB - 1) / WPB)), block(64 * WPB);
     if (count) {
-        hipLaunchKernelGGL((refine_kernel<true, G_SPAN>), grid, block, 0, st, a);
+        hipLaunchKernelGGL((refine_kernel<true>), grid, block, 0, st, a);
     } else if (c->lane_vote && (c->lane_w != 0 || 2 * n >= (size_t)65536)) {
         // lane kernel (32 or 64 windows a wave) once the batch has >= 64K windows; below that the
         // one-wave-per-window span kernel is as fast or faster (fewer, longer waves leave the
@@ -2353,11 +452,11 @@ svt_status launch(svt_ctx *c, const svt_locus *d_loci, svt_result *d_out, size_t
         const unsigned per = WPB * (wide ? 64u : 32u);
         const dim3 lgrid((unsigned)((2 * n + per - 1) / per));
         if (wide) {
-            if (c->bk_ready) hipLaunchKernelGGL((refine_lane_kernel<64, SVT_WIDE_R, SVT_WIDE_OCC, true>), lgrid, block, 0, st, a);
-            else hipLaunchKernelGGL((refine_lane_kernel<64, SVT_WIDE_R, SVT_WIDE_OCC, false>), lgrid, block, 0, st, a);
+            if (c->bk_ready) hipLaunchKernelGGL((refine_lane_kernel<64, true>), lgrid, block, 0, st, a);
+            else hipLaunchKernelGGL((refine_lane_kernel<64, false>), lgrid, block, 0, st, a);
         } else {
-            if (c->bk_ready) hipLaunchKernelGGL((refine_lane_kernel<32, 32, SVT_REFINE_WAVES, true>), lgrid, block, 0, st, a);
-            else hipLaunchKernelGGL((refine_lane_kernel<32, 32, SVT_REFINE_WAVES, false>), lgrid, block, 0, st, a);
+            if (c->bk_ready) hipLaunchKernelGGL((refine_lane_kernel<32, true>), lgrid, block, 0, st, a);
+            else hipLaunchKernelGGL((refine_lane_kernel<32, false>), lgrid, block, 0, st, a);
         }
         hipLaunchKernelGGL(refine_redo_kernel, dim3(8192), block, 0, st, a);   // ~1 left-over window per wave
     } else {
@@ -2387,147 +486,7 @@ svt_status upload(svt_ctx *c, T *&dst, const T *src, size_t n, size_t pad_elems 
     return SVT_OK;
 }
 
-// POA scratch, kept across calls: one slot per persistent wave in two pools.  The many
-// small slots hold graphs up to POA_SMALL_NODES nodes with POA_SMALL_SPILL spill rows (a
-// typical allele's graph is a few thousand nodes and spills none); loci that outgrow them
-// rerun on the few full-size slots.  Sizes at the default parameters: 2560 x 8.6 MB
-// (10 waves per CU: the LDS ring bounds occupancy at 11) and 256 x 50 MB.
-#ifndef SVT_POA_SLOTS_SMALL
-#define SVT_POA_SLOTS_SMALL 2560
-#endif
-constexpr uint64_t POA_SLOTS_SMALL = SVT_POA_SLOTS_SMALL;
-constexpr uint64_t POA_SLOTS_BIG = 256;
-constexpr int32_t POA_SMALL_NODES = 16384;
-constexpr int32_t POA_SMALL_SPILL = 256;
-
-svt_status poa_pool(svt_ctx *c, PoaPool &pl, int32_t node_cap, int32_t spill_cap, const svt_poa_params *p,
-                    uint64_t want) {
-    const uint64_t sb = poa_slot_bytes(node_cap, spill_cap, p->max_len);
-    if (pl.d && pl.slot_bytes == sb && pl.nslots >= want) return SVT_OK;
-    hfree(pl.d);
-    pl.nslots = 0;
-    if (hipMalloc(&pl.d, want * sb) != hipSuccess) {
-        pl.d = nullptr;
-        return fail(c, SVT_ENOMEM, "%s", "poa scratch (lower max_nodes / max_len)");
-    }
-    pl.slot_bytes = sb;
-    pl.nslots = (uint32_t)want;
-    return SVT_OK;
-}
-
-// SVTREK_POA_SMALL_NODES overrides the small slots' node budget (tests force deferral).
-int32_t poa_small_cap(const svt_poa_params *p) {
-    const char *ev = getenv("SVTREK_POA_SMALL_NODES");
-    const int32_t want = ev ? (int32_t)atoi(ev) : POA_SMALL_NODES;
-    return std::min(p->max_nodes, std::max(want, p->max_len + 2));
-}
-
-// One persistent launch of poa_kernel over d_list (or all n loci) on pool pl; synchronous.
-svt_status poa_launch(svt_ctx *c, PoaArgs a, const PoaPool &pl, int32_t node_cap, int32_t spill_cap,
-                      const uint32_t *d_list, uint32_t n, uint32_t *d_queue) {
-    a.slots = pl.d;
-    a.slot_bytes = pl.slot_bytes;
-    a.node_cap = node_cap;
-    a.spill_cap = spill_cap;
-    a.list = d_list;
-    a.n = n;
-    a.queue = d_queue;
-    a.diag = nullptr;
-    HIP_TRY(c, hipMemset(d_queue, 0, sizeof(uint32_t)));
-#if SVT_POA_DIAG
-    HIP_TRY(c, hipMalloc(&a.diag, PD_N * sizeof(unsigned long long)));
-    HIP_TRY(c, hipMemset(a.diag, 0, PD_N * sizeof(unsigned long long)));
-    HIP_TRY(c, hipMemset(a.diag + PD_T0, 0xff, sizeof(unsigned long long)));
-#endif
-    const unsigned grid = (unsigned)std::min<uint64_t>(pl.nslots, n);
-    hipLaunchKernelGGL(poa_kernel, dim3(grid), dim3(64), 0, nullptr, a);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipDeviceSynchronize());
-#if SVT_POA_DIAG
-    unsigned long long h[PD_N];
-    HIP_TRY(c, hipMemcpy(h, a.diag, sizeof h, hipMemcpyDeviceToHost));
-    (void)hipFree(a.diag);
-    fprintf(stderr, "poa_diag node_cap=%d grid=%u loci=%u wave-ms: support %.1f load %.1f rows %.1f trace %.1f "
-            "fuse %.1f cons %.1f | rows %llu steps %llu seqs %llu far %llu\n", node_cap, grid, n, h[PD_SUPPORT] * 1e-5,
-            h[PD_LOAD] * 1e-5, h[PD_ROWS] * 1e-5, h[PD_TRACE] * 1e-5, h[PD_FUSE] * 1e-5, h[PD_CONS] * 1e-5,
-            h[PD_NROWS], h[PD_NSTEPS], h[PD_NSEQ], h[PD_NFAR]);
-    fprintf(stderr, "poa_diag span %.1f ms, longest locus %.1f ms, busiest wave %.1f ms\n",
-            (h[PD_T1] - h[PD_T0]) * 1e-5, h[PD_LOCMAX] * 1e-5, h[PD_WAVEMAX] * 1e-5);
-#endif
-    return SVT_OK;
-}
-
-svt_status poa_run(svt_ctx *c, const svt_poa_params *p, const svt_locus *loci, const svt_result *refined, size_t n,
-                   int32_t cap, uint8_t *bases, svt_poa_result *res) {
-    svt_locus *d_loci = nullptr;
-    svt_result *d_ref = nullptr;
-    uint8_t *d_out = nullptr;
-    int4 *d_res = nullptr;
-    uint32_t *d_aux = nullptr;   // [0] work queue, [1 .. n] locus order, [n+1 .. 2n] cost estimates
-    int32_t *d_sup = nullptr;    // [n] supporting sequences found, then [n][max_support] their indices
-    svt_status s = SVT_OK;
-    auto chk = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && s == SVT_OK) s = fail(c, SVT_EDEVICE, what, hipGetErrorString(e));
-        return s == SVT_OK;
-    };
-    const int32_t small_cap = poa_small_cap(p);
-    if (chk(hipMalloc(&d_loci, n * sizeof(svt_locus)), "hipMalloc: %s") &&
-        chk(hipMalloc(&d_ref, n * sizeof(svt_result)), "hipMalloc: %s") &&
-        chk(hipMalloc(&d_out, std::max<size_t>(1, n * (size_t)cap)), "hipMalloc: %s") &&
-        chk(hipMalloc(&d_res, n * sizeof(int4)), "hipMalloc: %s") &&
-        chk(hipMalloc(&d_aux, (2 * n + 1) * sizeof(uint32_t)), "hipMalloc: %s") &&
-        chk(hipMalloc(&d_sup, n * (1 + (size_t)p->max_support) * sizeof(int32_t)), "hipMalloc: %s") &&
-        chk(hipMemcpy(d_loci, loci, n * sizeof(svt_locus), hipMemcpyHostToDevice), "H2D: %s") &&
-        chk(hipMemcpy(d_ref, refined, n * sizeof(svt_result), hipMemcpyHostToDevice), "H2D: %s")) {
-        const KArgs k = make_args(c, nullptr, nullptr, 0, false);
-        PoaArgs a;
-        a.pile = k.pile;
-        a.prm = k.prm;
-        a.pp = PoaParams{p->match, p->mismatch, p->gap_open, p->gap_ext, p->band_b, p->band_f_permille,
-                         p->max_seqs, p->max_len, p->max_nodes, p->support_radius, p->max_support};
-        a.loci = d_loci;
-        a.refined = d_ref;
-        a.n = (uint32_t)n;
-        a.ins_base = c->d_spoffI;
-        a.ins_off = c->d_ins_off;
-        a.ins_bases = c->d_ins_bases;
-        a.cap = cap;
-        a.out = d_out;
-        a.res = d_res;
-        a.nsupg = d_sup;
-        a.supg = d_sup + n;
-        a.est = d_aux + 1 + n;
-        a.diag = nullptr;
-        // supports + cost estimates, then the loci longest first (ties: input order)
-        hipLaunchKernelGGL(poa_support_kernel, dim3((unsigned)std::min<size_t>(n, 8192)), dim3(64), 0, nullptr, a);
-        std::vector<uint32_t> est(n), order(n);
-        if (chk(hipGetLastError(), "poa_support_kernel: %s") &&
-            chk(hipMemcpy(est.data(), a.est, n * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H: %s")) {
-            for (size_t i = 0; i < n; i++) order[i] = (uint32_t)i;
-            std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return est[x] > est[y]; });
-            chk(hipMemcpy(d_aux + 1, order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice), "H2D: %s");
-        }
-        if (s == SVT_OK)
-            s = poa_pool(c, c->poa_small, small_cap, POA_SMALL_SPILL, p, std::min<uint64_t>(n, POA_SLOTS_SMALL));
-        if (s == SVT_OK) s = poa_launch(c, a, c->poa_small, small_cap, POA_SMALL_SPILL, d_aux + 1, (uint32_t)n, d_aux);
-        if (s == SVT_OK && chk(hipMemcpy(res, d_res, n * sizeof(int4), hipMemcpyDeviceToHost), "D2H: %s")) {
-            std::vector<uint32_t> deferred;   // in the same longest-first order
-            for (size_t q = 0; q < n; q++)
-                if (res[order[q]].status == POA_DEFER) deferred.push_back(order[q]);
-            if (!deferred.empty()) {
-                const uint32_t nd = (uint32_t)deferred.size();
-                if (chk(hipMemcpy(d_aux + 1, deferred.data(), nd * sizeof(uint32_t), hipMemcpyHostToDevice), "H2D: %s"))
-                    s = poa_pool(c, c->poa_big, p->max_nodes, p->max_nodes + 2, p, std::min<uint64_t>(nd, POA_SLOTS_BIG));
-                if (s == SVT_OK) s = poa_launch(c, a, c->poa_big, p->max_nodes, p->max_nodes + 2, d_aux + 1, nd, d_aux);
-                if (s == SVT_OK) chk(hipMemcpy(res, d_res, n * sizeof(int4), hipMemcpyDeviceToHost), "D2H: %s");
-            }
-            c->poa_deferred = deferred.size();
-            if (s == SVT_OK && cap > 0) chk(hipMemcpy(bases, d_out, n * (size_t)cap, hipMemcpyDeviceToHost), "D2H: %s");
-        }
-    }
-    hfree(d_loci); hfree(d_ref); hfree(d_out); hfree(d_res); hfree(d_aux); hfree(d_sup);
-    return s;
-}
+#include "svt_poa_host.inc"
 
 }  // namespace
 
@@ -2747,8 +706,9 @@ BkBuild bk_args(const svt_ctx *c, bool count, bool captured) {
     return b;
 }
 
-// One counting or filing pass on st: short reads walked from the CIGAR stream, long reads filed
-// from the span lists (which the caller rebuilt first).
+// One counting or filing pass on st: short reads walked from the CIGAR stream; long reads counted
+// from the span lists (at load) and filed from the stream walk's stage (index_kernel, which the
+// caller ran first).
 svt_status bk_pass(svt_ctx *c, hipStream_t st, bool count, bool captured) {
     const IxArgs a = ix_args(c);
     const BkBuild b = bk_args(c, count, captured);
@@ -3126,9 +1086,10 @@ svt_status svt_reindex(svt_ctx *c, void *stream) {
     svt_status s = order_on(c, st);   // after every launch already issued (they read the index)
     if (s) return s;
     if (!c->bk_ready) return build_index(c, st, false, nullptr);
-    // the value buckets: short reads filed straight from the CIGAR stream; long reads from the
-    // span lists, rebuilt first.  A captured build files through its own cursors (zeroed by the
-    // graph), a direct one through the epoch cursors (svt_bucket_build.inc).
+    // the value buckets: short reads filed straight from the CIGAR stream (ixb_lane_kernel); long
+    // reads walked by index_kernel and filed from its stage (ixb_copy_kernel).  The span lists stay
+    // as built at load.  A captured build files through its own cursors (zeroed by the graph), a
+    // direct one through the epoch cursors (svt_bucket_build.inc).
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (st) HIP_TRY(c, hipStreamIsCapturing(st, &cap));
     const bool captured = cap == hipStreamCaptureStatusActive;
@@ -3190,11 +1151,6 @@ svt_status svt_sync(svt_ctx *c, void *stream) {
                     : st2[1] == 3 ? "device index build: an event outside its value bucket's extent (results invalid)"
                                   : "device index build: emit overran the census's sizes (results invalid)");
     }
-#if SVT_DIAG == 9
-    fprintf(stderr, "[diag] wave-wide (phase 3) windows: %d\n", status >> 8);
-    HIP_TRY(c, hipMemset(c->d_ctl + 8, 0, 4));
-    status &= 1;
-#endif
     if (status & 1) {
         HIP_TRY(c, hipMemset(c->d_ctl + 8, 0, 4));   // sticky until reported
         const svt_status g = grow_pool(c);            // a re-run of the batch now fits
@@ -3346,7 +1302,7 @@ static svt_status sw_1(svt_ctx *c, const svt_sw_query *q, size_t n, int32_t wind
             a.sw_sub = d_sub;
             a.sw_out = d_res;
             const dim3 grid((unsigned)((ns + WPB - 1) / WPB)), block(64 * WPB);
-            hipLaunchKernelGGL(sw_kernel<G_SPAN>, grid, block, 0, nullptr, a);
+            hipLaunchKernelGGL(sw_kernel, grid, block, 0, nullptr, a);
             chk(hipGetLastError(), "sw_kernel: %s");
         }
         if (s == SVT_OK) {
@@ -3563,254 +1519,6 @@ void svt_host_free(svt_ctx *c, void *p) {
     (void)hipHostFree(p);
 }
 
-// ---- BAM records decoded on the device (svt_bam.inc)
-}  // extern "C"
-
-// svt_bam_dec_feed is pipelined one batch deep: a call copies its batch's compressed bytes to the
-// device (a copy stream, into one of two input buffers) while the previous batch still inflates,
-// then decodes the previous batch (whose carried tail fixes where this batch's bytes go) and
-// launches this batch's inflate; the next call or svt_bam_dec_load decodes it.  (Copying a batch in
-// parts beside its own inflate measured slower: every part's launch waits for its slowest block,
-// profiles/r05_I.)
-struct svt_bam_dec {
-    svt_ctx *c = nullptr;
-    int32_t n_ref = 0;
-    hipStream_t st = nullptr;
-    hipStream_t cst = nullptr;                // the copy stream
-    hipEvent_t cev = nullptr;                 // the latest batch's bytes are on the device
-    uint8_t *d_comp[2] = {nullptr, nullptr};  // compressed batches (alternating)
-    size_t comp_cap[2] = {0, 0};
-    svt_bgzf_block *d_blk[2] = {nullptr, nullptr};
-    size_t blk_cap[2] = {0, 0};
-    int ib = 0;                               // the next batch's input buffer
-    uint32_t *d_err = nullptr;                // the inflate's first bad block (this decoder's own word)
-    bool pend = false;                        // a batch inflated (or inflating) but not yet decoded
-    size_t pend_n = 0;
-    uint64_t pend_u = 0, pend_r0 = 0;
-    uint8_t *d_buf[2] = {nullptr, nullptr};   // inflated batches: [carried tail | this batch]
-    size_t buf_cap[2] = {0, 0};
-    int cur = 0;
-    uint64_t tail = 0;                        // bytes of the incomplete record at the front of d_buf[cur]
-    bool first = true;
-    BdChunk *d_ch = nullptr;
-    uint32_t *d_base = nullptr;
-    size_t ch_cap = 0, base_cap = 0;
-    BdRec *d_rec = nullptr;
-    BdTot *d_pre = nullptr;
-    size_t rec_cap = 0, pre_cap = 0;
-    BdCheck *d_chk = nullptr;
-    void *d_tmp = nullptr;
-    size_t tmp_cap = 0;
-    BdCols cols{};
-    uint64_t col_cap = 0, word_cap = 0;       // capacities of the columns (reads) and the stream (words)
-    uint64_t nkept = 0, nwords = 0;
-    svt_bam_dec_stats stats{};
-};
-
-namespace {
-template <typename T>
-svt_status bd_grow(svt_ctx *c, T *&p, size_t &cap, size_t need, size_t keep = 0) {   // device, keeping `keep` elements
-    if (need <= cap) return SVT_OK;
-    const size_t nc = std::max(need, cap + cap / 2);
-    T *q = nullptr;
-    if (hipMalloc(&q, nc * sizeof(T)) != hipSuccess) return fail(c, SVT_ENOMEM, "%s", "device memory for the BAM decode");
-    if (keep && p) HIP_TRY(c, hipMemcpy(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice));
-    hfree(p);
-    p = q;
-    cap = nc;
-    return SVT_OK;
-}
-}  // namespace
-
-extern "C" {
-
-svt_status svt_bam_dec_open(svt_ctx *c, int32_t n_targets, svt_bam_dec **out) {
-    if (!c || !out || n_targets < 0) return SVT_EINVAL;
-    *out = nullptr;
-    DEV_GUARD(c);
-    svt_bam_dec *d = new (std::nothrow) svt_bam_dec();
-    if (!d) return fail(c, SVT_ENOMEM, "%s", "host memory");
-    d->c = c;
-    d->n_ref = n_targets;
-    const bool ok = hipStreamCreateWithFlags(&d->st, hipStreamNonBlocking) == hipSuccess &&
-                    hipStreamCreateWithFlags(&d->cst, hipStreamNonBlocking) == hipSuccess &&
-                    hipEventCreateWithFlags(&d->cev, hipEventDisableTiming) == hipSuccess &&
-                    hipMalloc(&d->d_chk, sizeof(BdCheck)) == hipSuccess && hipMalloc(&d->d_err, sizeof(uint32_t)) == hipSuccess;
-    if (!ok) {
-        svt_bam_dec_close(d);
-        return fail(c, SVT_EDEVICE, "%s", "BAM decode: stream / buffers");
-    }
-    *out = d;
-    return SVT_OK;
-}
-
-namespace {
-// The pending batch's records: it was inflated into d_buf[cur] after the carried tail (its
-// kernels run on d->st, so the decode's launches wait for them).  The incomplete last record
-// moves to the front of the other buffer.
-svt_status bd_decode(svt_bam_dec *d) {
-    svt_ctx *c = d->c;
-    svt_status s;
-    d->pend = false;
-    uint8_t *buf = d->d_buf[d->cur];
-    const uint64_t N = d->tail + d->pend_u, r0 = d->pend_r0;
-    const uint64_t span = N - r0;
-    const uint32_t nch = (uint32_t)((span + BD_CHUNK - 1) / BD_CHUNK);
-    BdCheck chk{1u, 0u, 0ull, N, 0u, 0u, 0ull};
-    if (nch) {
-        if ((s = bd_grow(c, d->d_ch, d->ch_cap, nch)) || (s = bd_grow(c, d->d_base, d->base_cap, nch))) return s;
-        hipLaunchKernelGGL(bd_chunk_kernel, dim3(nch), dim3(WAVE), 0, d->st, buf, r0, N, nch, d->n_ref, d->d_ch);
-        hipLaunchKernelGGL(bd_check_kernel, dim3(1), dim3(WAVE), 0, d->st, buf, d->d_ch, nch, r0, N, d->d_chk);
-        HIP_TRY(c, hipGetLastError());
-        uint32_t ierr = 0xffffffffu;
-        HIP_TRY(c, hipMemcpyAsync(&chk, d->d_chk, sizeof chk, hipMemcpyDeviceToHost, d->st));
-        HIP_TRY(c, hipMemcpyAsync(&ierr, d->d_err, sizeof ierr, hipMemcpyDeviceToHost, d->st));
-        HIP_TRY(c, hipStreamSynchronize(d->st));
-        if (d->pend_n && ierr != 0xffffffffu) {
-            char m[64];
-            snprintf(m, sizeof m, "%u", ierr);
-            return fail(c, SVT_EINVAL, "corrupt BGZF block %s of the batch (does not inflate to its ISIZE)", m);
-        }
-        if (!chk.ok) {   // a wrong guess: the exact chain, hop by hop from the first wrong chunk on
-            d->stats.rechained++;
-            d->stats.rechained_chunks += nch - chk.kfail;
-            hipLaunchKernelGGL(bd_chain_kernel, dim3(1), dim3(WAVE), 0, d->st, buf, r0, N, nch, chk.kfail, chk.efail,
-                               d->d_ch);
-            hipLaunchKernelGGL(bd_check_kernel, dim3(1), dim3(WAVE), 0, d->st, buf, d->d_ch, nch, r0, N, d->d_chk);
-            HIP_TRY(c, hipGetLastError());
-            HIP_TRY(c, hipMemcpyAsync(&chk, d->d_chk, sizeof chk, hipMemcpyDeviceToHost, d->st));
-            HIP_TRY(c, hipStreamSynchronize(d->st));
-            if (!chk.ok) return fail(c, SVT_EDEVICE, "%s", "BAM decode: the exact record chain failed its own check");
-        }
-        if (chk.bad) return fail(c, SVT_EINVAL, "%s", "corrupt BAM record (block_size < 32)");
-    }
-    if (chk.nrec) {
-        const uint64_t nrec = chk.nrec;
-        if (nrec >= 0xffffffffull) return fail(c, SVT_EINVAL, "%s", "BAM decode: more than 2^32 records in one batch");
-        if ((s = bd_grow(c, d->d_rec, d->rec_cap, nrec)) || (s = bd_grow(c, d->d_pre, d->pre_cap, nrec))) return s;
-        // the chunks' record counts -> their first record's index; the records; their kept / word prefixes
-        const auto cnt = hipcub::TransformInputIterator<uint32_t, BdCntOf, const BdChunk *>(d->d_ch, BdCntOf());
-        const auto tot = hipcub::TransformInputIterator<BdTot, BdTotOf, const BdRec *>(d->d_rec, BdTotOf());
-        size_t need1 = 0, need2 = 0;
-        HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(nullptr, need1, cnt, d->d_base, (int)chk.nk, d->st));
-        HIP_TRY(c, hipcub::DeviceScan::ExclusiveScan(nullptr, need2, tot, d->d_pre, BdTotSum(), BdTot{0, 0, 0, 0, 0},
-                                                     (int)nrec, d->st));
-        if ((s = bd_grow(c, reinterpret_cast<uint8_t *&>(d->d_tmp), d->tmp_cap, std::max(need1, need2)))) return s;
-        size_t t1 = d->tmp_cap, t2 = d->tmp_cap;
-        HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(d->d_tmp, t1, cnt, d->d_base, (int)chk.nk, d->st));
-        hipLaunchKernelGGL(bd_rec_kernel, dim3(chk.nk), dim3(WAVE), 0, d->st, buf, d->d_ch, d->d_base, chk.nk, d->n_ref,
-                           d->d_rec);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipcub::DeviceScan::ExclusiveScan(d->d_tmp, t2, tot, d->d_pre, BdTotSum(), BdTot{0, 0, 0, 0, 0},
-                                                     (int)nrec, d->st));
-        BdTot last{};
-        BdRec lr{};
-        HIP_TRY(c, hipMemcpyAsync(&last, d->d_pre + nrec - 1, sizeof last, hipMemcpyDeviceToHost, d->st));
-        HIP_TRY(c, hipMemcpyAsync(&lr, d->d_rec + nrec - 1, sizeof lr, hipMemcpyDeviceToHost, d->st));
-        HIP_TRY(c, hipStreamSynchronize(d->st));
-        const BdTot all = BdTotSum()(last, BdTotOf()(lr));
-        if (all.bad) return fail(c, SVT_EINVAL, "%s", "corrupt BAM record");
-        // the columns and the stream (STREAM_PAD spare words), grown keeping what they hold
-        const uint64_t G = d->nkept + all.keep + 1, W = d->nwords + all.words + STREAM_PAD;
-        if (G > d->col_cap) {   // every column to the same capacity
-            size_t cc;
-            cc = d->col_cap; if ((s = bd_grow(c, d->cols.tid, cc, G, d->nkept))) return s;
-            cc = d->col_cap; if ((s = bd_grow(c, d->cols.pos, cc, G, d->nkept))) return s;
-            cc = d->col_cap; if ((s = bd_grow(c, d->cols.endpos, cc, G, d->nkept))) return s;
-            cc = d->col_cap; if ((s = bd_grow(c, d->cols.nc, cc, G, d->nkept))) return s;
-            cc = d->col_cap; if ((s = bd_grow(c, d->cols.soff, cc, G, d->nkept))) return s;
-            d->col_cap = cc;
-        }
-        if ((s = bd_grow(c, d->cols.stream, d->word_cap, W, d->nwords))) return s;
-        hipLaunchKernelGGL(bd_copy_kernel, dim3((unsigned)std::min<uint64_t>((nrec + 3) / 4, 16384)), dim3(256), 0, d->st,
-                           buf, d->d_rec, d->d_pre, nrec, d->cols, d->nkept, d->nwords);
-        HIP_TRY(c, hipGetLastError());
-        d->nkept += all.keep;
-        d->nwords += all.words;
-        d->stats.records += nrec;
-        d->stats.reads += all.keep;
-        d->stats.cigar_ops += all.ops;
-        d->stats.cg_restored += all.cg;
-    }
-    // the incomplete last record moves to the front of the other buffer
-    const uint64_t nt = N - chk.tail;
-    int nx = d->cur ^ 1;
-    if ((s = bd_grow(c, d->d_buf[nx], d->buf_cap[nx], std::max<uint64_t>(nt, 1) + 64))) return s;
-    if (nt) HIP_TRY(c, hipMemcpyAsync(d->d_buf[nx], buf + chk.tail, nt, hipMemcpyDeviceToDevice, d->st));
-    HIP_TRY(c, hipStreamSynchronize(d->st));
-    d->cur = nx;
-    d->tail = nt;
-    return SVT_OK;
-}
-}  // namespace
-
-svt_status svt_bam_dec_feed(svt_bam_dec *d, const uint8_t *comp, size_t comp_bytes, const svt_bgzf_block *blocks,
-                            size_t n, uint64_t skip) {
-    if (!d) return SVT_EINVAL;
-    svt_ctx *c = d->c;
-    if (n && (!comp || !blocks)) return fail(c, SVT_EINVAL, "%s", "null buffer");
-    if (n > 0xfffffffeull) return fail(c, SVT_EINVAL, "%s", "more than 2^32 - 2 blocks in one call");
-    uint64_t U = 0, lo = ~0ull, hi = 0;
-    for (size_t i = 0; i < n; i++) {   // every block inside its buffers (the kernel trusts the table)
-        const svt_bgzf_block &k = blocks[i];
-        if (k.clen > 65536u || k.ulen > 65536u || k.coff > comp_bytes || k.clen > comp_bytes - k.coff)
-            return fail(c, SVT_EINVAL, "%s", "BGZF block outside its buffers (or over 64 KiB)");
-        U = std::max<uint64_t>(U, k.uoff + k.ulen);
-        lo = std::min<uint64_t>(lo, k.coff);
-        hi = std::max<uint64_t>(hi, k.coff + k.clen);
-    }
-    DEV_GUARD(c);
-    using clk = std::chrono::steady_clock;
-    const clk::time_point t0 = clk::now();
-    svt_status s;
-    const uint64_t r0 = d->first ? skip : 0;   // (the first batch carries no tail)
-    if (r0 > (d->first ? 0 : d->tail) + U) return fail(c, SVT_EINVAL, "%s", "BAM decode: the header runs past the first batch");
-    d->first = false;
-    // this batch's bytes cross PCIe while the previous batch inflates (its input is the other buffer)
-    const int ib = d->ib;
-    d->ib ^= 1;
-    if ((s = bd_grow(c, d->d_comp[ib], d->comp_cap[ib], comp_bytes + 64)) ||
-        (s = bd_grow(c, d->d_blk[ib], d->blk_cap[ib], std::max<size_t>(n, 1))))
-        return s;
-    // Once this batch's copies are queued, every return waits for them first: the header lets the
-    // caller reuse `comp` / `blocks` as soon as the call returns, error returns included.
-    struct CopyWait {
-        hipStream_t cst = nullptr;
-        ~CopyWait() {
-            if (cst) (void)hipStreamSynchronize(cst);
-        }
-    } copy_wait;
-    if (n) {
-        copy_wait.cst = d->cst;
-        HIP_TRY(c, hipMemcpyAsync(d->d_blk[ib], blocks, n * sizeof(svt_bgzf_block), hipMemcpyHostToDevice, d->cst));
-        if (hi > lo) HIP_TRY(c, hipMemcpyAsync(d->d_comp[ib] + lo, comp + lo, hi - lo, hipMemcpyHostToDevice, d->cst));
-        HIP_TRY(c, hipEventRecord(d->cev, d->cst));
-    }
-    // the previous batch's records: fixes the carried tail this batch's bytes follow
-    if (d->pend && (s = bd_decode(d))) return s;
-    const uint64_t T = d->tail, N = T + U;
-    if ((s = bd_grow(c, d->d_buf[d->cur], d->buf_cap[d->cur], N + 64, T))) return s;
-    if (n) {
-        if ((s = order_on(c, d->st))) return s;
-        HIP_TRY(c, hipMemsetAsync(d->d_err, 0xff, sizeof(uint32_t), d->st));
-        HIP_TRY(c, hipStreamWaitEvent(d->st, d->cev, 0));
-        const unsigned grid = (unsigned)std::min<size_t>(n, (size_t)INF_GRID);
-        hipLaunchKernelGGL(inflate_kernel, dim3(grid), dim3(WAVE), 0, d->st, d->d_comp[ib], d->d_blk[ib], 0u, (uint32_t)n,
-                           d->d_buf[d->cur] + T, d->d_err);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipEventSynchronize(d->cev));   // the caller may reuse its buffers
-        copy_wait.cst = nullptr;
-    }
-    d->pend = true;
-    d->pend_n = n;
-    d->pend_u = U;
-    d->pend_r0 = r0;
-    d->stats.batches++;
-    d->stats.inflated_bytes += U;
-    d->stats.feed_ms += std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-    return SVT_OK;
-}
-
 #if SVT_PHASE_PROF
 // diagnostic builds: refine_lane_kernel's phase times and counts since the last call (then cleared)
 int svt_diag_phase(unsigned long long *out) {
@@ -3819,124 +1527,6 @@ int svt_diag_phase(unsigned long long *out) {
     return hipMemcpyToSymbol(HIP_SYMBOL(ph_prof), z, sizeof z) != hipSuccess;
 }
 #endif
-
-svt_status svt_bam_dec_stats_get(const svt_bam_dec *d, svt_bam_dec_stats *out) {
-    if (!d || !out) return SVT_EINVAL;
-    *out = d->stats;
-    return SVT_OK;
-}
-
-svt_status svt_bam_dec_load(svt_bam_dec *d) {
-    if (!d) return SVT_EINVAL;
-    svt_ctx *c = d->c;
-    DEV_GUARD(c);
-    using clk = std::chrono::steady_clock;
-    if (d->pend) {   // the last batch's records
-        const clk::time_point tf = clk::now();
-        const svt_status sd = bd_decode(d);
-        d->stats.feed_ms += std::chrono::duration<double, std::milli>(clk::now() - tf).count();
-        if (sd) return sd;
-    }
-    if (d->tail) return fail(c, SVT_EINVAL, "%s", "truncated BAM record at end of file");
-    const clk::time_point t0 = clk::now();
-    free_pileup(c);
-    c->load_stats = svt_load_stats{};
-    const int32_t nt = d->n_ref;
-    const uint64_t n = d->nkept;
-    svt_status s;
-    // sortedness and the contig boundaries, on the device
-    int64_t *d_toff = nullptr;
-    uint32_t *d_uns = nullptr;
-    HIP_TRY(c, hipMalloc(&d_toff, ((size_t)nt + 1) * sizeof(int64_t)));
-    if (hipMalloc(&d_uns, sizeof(uint32_t)) != hipSuccess) { hfree(d_toff); return fail(c, SVT_ENOMEM, "%s", "device"); }
-    std::vector<int64_t> toff((size_t)nt + 1, 0);
-    uint32_t uns = 0;
-    hipError_t e = hipMemsetAsync(d_uns, 0, sizeof(uint32_t), d->st);
-    if (e == hipSuccess) e = hipMemsetAsync(d_toff, 0, ((size_t)nt + 1) * sizeof(int64_t), d->st);
-    if (e == hipSuccess) {
-        const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 256) / 256, 65536));
-        hipLaunchKernelGGL(bd_finish_kernel, dim3(g), dim3(256), 0, d->st, d->cols.tid, d->cols.pos, n, nt, d_toff, d_uns);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(toff.data(), d_toff, toff.size() * sizeof(int64_t), hipMemcpyDeviceToHost, d->st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&uns, d_uns, sizeof uns, hipMemcpyDeviceToHost, d->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(d->st);
-    hfree(d_toff);
-    hfree(d_uns);
-    if (e != hipSuccess) return fail(c, SVT_EDEVICE, "BAM decode finish: %s", hipGetErrorString(e));
-    // the per-read columns the host pass reads (pos, endpos, n_cigar | clip, stream offsets)
-    std::vector<int32_t> pos(n), endpos(n), tid(uns ? n : 0);
-    std::vector<uint32_t> nc(n);
-    std::vector<uint64_t> soff(n + 1);
-    if (n) {
-        HIP_TRY(c, hipMemcpy(pos.data(), d->cols.pos, n * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(endpos.data(), d->cols.endpos, n * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(nc.data(), d->cols.nc, n * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(soff.data(), d->cols.soff, n * 8, hipMemcpyDeviceToHost));
-        if (uns) HIP_TRY(c, hipMemcpy(tid.data(), d->cols.tid, n * 4, hipMemcpyDeviceToHost));
-    }
-    soff[n] = d->nwords;
-    const double pre = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-    if (uns) {   // not coordinate-sorted: sort on the host (stable, by tid then pos), as the host ingest does
-        std::vector<uint32_t> strm(d->nwords);
-        if (d->nwords) HIP_TRY(c, hipMemcpy(strm.data(), d->cols.stream, d->nwords * 4, hipMemcpyDeviceToHost));
-        std::vector<size_t> idx(n);
-        for (size_t i = 0; i < n; i++) idx[i] = i;
-        std::stable_sort(idx.begin(), idx.end(), [&](size_t x, size_t y) {
-            return tid[x] != tid[y] ? tid[x] < tid[y] : pos[x] < pos[y];
-        });
-        std::vector<int32_t> p2(n), e2(n);
-        std::vector<uint32_t> n2(n), s2;
-        std::vector<uint64_t> o2(n + 1);
-        s2.reserve(d->nwords);
-        std::fill(toff.begin(), toff.end(), 0);
-        for (size_t k = 0; k < n; k++) {
-            const size_t i = idx[k];
-            p2[k] = pos[i]; e2[k] = endpos[i]; n2[k] = nc[i];
-            o2[k] = s2.size();
-            s2.insert(s2.end(), strm.begin() + (ptrdiff_t)soff[i], strm.begin() + (ptrdiff_t)soff[i + 1]);
-            toff[(size_t)tid[i] + 1]++;
-        }
-        o2[n] = s2.size();
-        for (int32_t t = 0; t < nt; t++) toff[(size_t)t + 1] += toff[(size_t)t];
-        s = load_core(c, nt, toff.data(), p2.data(), e2.data(), n2.data(), o2.data(), s2.data(), nullptr,
-                      d->stats.cigar_ops, pre);
-    } else {
-        // the stream stays where the decode wrote it (its spare words zeroed): the context adopts it;
-        // a BAM without records never allocated one, so it gets just the spare words here
-        if ((s = bd_grow(c, d->cols.stream, d->word_cap, d->nwords + STREAM_PAD, d->nwords))) return s;
-        HIP_TRY(c, hipMemset(d->cols.stream + d->nwords, 0, STREAM_PAD * 4));
-        s = load_core(c, nt, toff.data(), pos.data(), endpos.data(), nc.data(), soff.data(), nullptr, d->cols.stream,
-                      d->stats.cigar_ops, pre);
-        if (c->d_cigar == d->cols.stream) {
-            d->cols.stream = nullptr;
-            d->word_cap = 0;
-        }
-    }
-    c->load_stats.total_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-    return s;
-}
-
-void svt_bam_dec_close(svt_bam_dec *d) {
-    if (!d) return;
-    {
-        DevGuard dg(d->c->device);
-        if (d->st) (void)hipStreamSynchronize(d->st);
-        // the context's launch order may point at this stream (svt_bam_dec_feed's order_on): all of
-        // its work is done, so nothing later has to wait for it, and it must not be named again
-        if (d->c->have_last && d->c->last_stream == d->st) d->c->have_last = false;
-        if (d->cst) (void)hipStreamSynchronize(d->cst);
-        hfree(d->d_comp[0]); hfree(d->d_comp[1]); hfree(d->d_blk[0]); hfree(d->d_blk[1]); hfree(d->d_err);
-        hfree(d->d_buf[0]); hfree(d->d_buf[1]);
-        hfree(d->d_ch); hfree(d->d_base); hfree(d->d_rec); hfree(d->d_pre); hfree(d->d_chk); hfree(d->d_tmp);
-        hfree(d->cols.tid); hfree(d->cols.pos); hfree(d->cols.endpos); hfree(d->cols.nc); hfree(d->cols.soff);
-        hfree(d->cols.stream);
-        if (d->cev) (void)hipEventDestroy(d->cev);
-        if (d->st) (void)hipStreamDestroy(d->st);
-        if (d->cst) (void)hipStreamDestroy(d->cst);
-    }
-    delete d;
-}
 
 void svt_close(svt_ctx *c) {
     if (!c) return;
@@ -3951,3 +1541,5 @@ void svt_close(svt_ctx *c) {
 }
 
 }  // extern "C"
+
+#include "svt_bam_host.inc"

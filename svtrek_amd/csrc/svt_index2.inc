@@ -120,7 +120,7 @@ __device__ __forceinline__ void ix2_emit(const IxArgs &a, uint64_t r, bool act, 
         if (stage) ev[tD + i] = v;
         else ix_store4(v, rI, i * 16u);
     };
-    if (act && SVT_DIAG != 23) ix2_emit_read(a, r, xD, xI, putD, putI);   // (23: diagnostic build, no walk: the rest's traffic)
+    if (act) ix2_emit_read(a, r, xD, xI, putD, putI);
     if (stage) {
         wave_sync();
         if (fits) {

@@ -536,8 +536,7 @@ __device__ __forceinline__ int iw_codes(IwLds &L, IwBits &br, IwOut &o) {
                 if (du >= lu) return src + i;   // no overlap (the common case)
                 return src + (i < len ? i % dist : 0u);
             };
-            // (diagnostic build 21: far matches read the ring -- wrong bytes; the far loads' cost)
-            if (du <= IW_RING - IW_AHEAD || SVT_DIAG == 21) {
+            if (du <= IW_RING - IW_AHEAD) {
                 const uint32_t su = iw_rfl(src);
                 if (pend && su < pdst + plen && su + min(du, lu) > pdst) flush();   // it reads them
                 const __attribute__((address_space(3))) uint8_t *rg =

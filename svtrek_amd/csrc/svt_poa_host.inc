@@ -1,0 +1,145 @@
+// svt_poa_host.inc -- host half of the allele-consensus mode (included by svt_engine.hip inside its
+// anonymous namespace, after svt_ctx and its helpers): the POA slot pools and poa_run.  The kernels
+// are in svt_poa.inc.
+
+// POA scratch, kept across calls: one slot per persistent wave in two pools.  The many
+// small slots hold graphs up to POA_SMALL_NODES nodes with POA_SMALL_SPILL spill rows (a
+// typical allele's graph is a few thousand nodes and spills none); loci that outgrow them
+// rerun on the few full-size slots.  Sizes at the default parameters: 2560 x 8.6 MB
+// (10 waves per CU: the LDS ring bounds occupancy at 11) and 256 x 50 MB.
+#ifndef SVT_POA_SLOTS_SMALL
+#define SVT_POA_SLOTS_SMALL 2560
+#endif
+constexpr uint64_t POA_SLOTS_SMALL = SVT_POA_SLOTS_SMALL;
+constexpr uint64_t POA_SLOTS_BIG = 256;
+constexpr int32_t POA_SMALL_NODES = 16384;
+constexpr int32_t POA_SMALL_SPILL = 256;
+
+svt_status poa_pool(svt_ctx *c, PoaPool &pl, int32_t node_cap, int32_t spill_cap, const svt_poa_params *p,
+                    uint64_t want) {
+    const uint64_t sb = poa_slot_bytes(node_cap, spill_cap, p->max_len);
+    if (pl.d && pl.slot_bytes == sb && pl.nslots >= want) return SVT_OK;
+    hfree(pl.d);
+    pl.nslots = 0;
+    if (hipMalloc(&pl.d, want * sb) != hipSuccess) {
+        pl.d = nullptr;
+        return fail(c, SVT_ENOMEM, "%s", "poa scratch (lower max_nodes / max_len)");
+    }
+    pl.slot_bytes = sb;
+    pl.nslots = (uint32_t)want;
+    return SVT_OK;
+}
+
+// SVTREK_POA_SMALL_NODES overrides the small slots' node budget (tests force deferral).
+int32_t poa_small_cap(const svt_poa_params *p) {
+    const char *ev = getenv("SVTREK_POA_SMALL_NODES");
+    const int32_t want = ev ? (int32_t)atoi(ev) : POA_SMALL_NODES;
+    return std::min(p->max_nodes, std::max(want, p->max_len + 2));
+}
+
+// One persistent launch of poa_kernel over d_list (or all n loci) on pool pl; synchronous.
+svt_status poa_launch(svt_ctx *c, PoaArgs a, const PoaPool &pl, int32_t node_cap, int32_t spill_cap,
+                      const uint32_t *d_list, uint32_t n, uint32_t *d_queue) {
+    a.slots = pl.d;
+    a.slot_bytes = pl.slot_bytes;
+    a.node_cap = node_cap;
+    a.spill_cap = spill_cap;
+    a.list = d_list;
+    a.n = n;
+    a.queue = d_queue;
+    a.diag = nullptr;
+    HIP_TRY(c, hipMemset(d_queue, 0, sizeof(uint32_t)));
+#if SVT_POA_DIAG
+    HIP_TRY(c, hipMalloc(&a.diag, PD_N * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemset(a.diag, 0, PD_N * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemset(a.diag + PD_T0, 0xff, sizeof(unsigned long long)));
+#endif
+    const unsigned grid = (unsigned)std::min<uint64_t>(pl.nslots, n);
+    hipLaunchKernelGGL(poa_kernel, dim3(grid), dim3(64), 0, nullptr, a);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipDeviceSynchronize());
+#if SVT_POA_DIAG
+    unsigned long long h[PD_N];
+    HIP_TRY(c, hipMemcpy(h, a.diag, sizeof h, hipMemcpyDeviceToHost));
+    (void)hipFree(a.diag);
+    fprintf(stderr, "poa_diag node_cap=%d grid=%u loci=%u wave-ms: support %.1f load %.1f rows %.1f trace %.1f "
+            "fuse %.1f cons %.1f | rows %llu steps %llu seqs %llu far %llu\n", node_cap, grid, n, h[PD_SUPPORT] * 1e-5,
+            h[PD_LOAD] * 1e-5, h[PD_ROWS] * 1e-5, h[PD_TRACE] * 1e-5, h[PD_FUSE] * 1e-5, h[PD_CONS] * 1e-5,
+            h[PD_NROWS], h[PD_NSTEPS], h[PD_NSEQ], h[PD_NFAR]);
+    fprintf(stderr, "poa_diag span %.1f ms, longest locus %.1f ms, busiest wave %.1f ms\n",
+            (h[PD_T1] - h[PD_T0]) * 1e-5, h[PD_LOCMAX] * 1e-5, h[PD_WAVEMAX] * 1e-5);
+#endif
+    return SVT_OK;
+}
+
+svt_status poa_run(svt_ctx *c, const svt_poa_params *p, const svt_locus *loci, const svt_result *refined, size_t n,
+                   int32_t cap, uint8_t *bases, svt_poa_result *res) {
+    svt_locus *d_loci = nullptr;
+    svt_result *d_ref = nullptr;
+    uint8_t *d_out = nullptr;
+    int4 *d_res = nullptr;
+    uint32_t *d_aux = nullptr;   // [0] work queue, [1 .. n] locus order, [n+1 .. 2n] cost estimates
+    int32_t *d_sup = nullptr;    // [n] supporting sequences found, then [n][max_support] their indices
+    svt_status s = SVT_OK;
+    auto chk = [&](hipError_t e, const char *what) {
+        if (e != hipSuccess && s == SVT_OK) s = fail(c, SVT_EDEVICE, what, hipGetErrorString(e));
+        return s == SVT_OK;
+    };
+    const int32_t small_cap = poa_small_cap(p);
+    if (chk(hipMalloc(&d_loci, n * sizeof(svt_locus)), "hipMalloc: %s") &&
+        chk(hipMalloc(&d_ref, n * sizeof(svt_result)), "hipMalloc: %s") &&
+        chk(hipMalloc(&d_out, std::max<size_t>(1, n * (size_t)cap)), "hipMalloc: %s") &&
+        chk(hipMalloc(&d_res, n * sizeof(int4)), "hipMalloc: %s") &&
+        chk(hipMalloc(&d_aux, (2 * n + 1) * sizeof(uint32_t)), "hipMalloc: %s") &&
+        chk(hipMalloc(&d_sup, n * (1 + (size_t)p->max_support) * sizeof(int32_t)), "hipMalloc: %s") &&
+        chk(hipMemcpy(d_loci, loci, n * sizeof(svt_locus), hipMemcpyHostToDevice), "H2D: %s") &&
+        chk(hipMemcpy(d_ref, refined, n * sizeof(svt_result), hipMemcpyHostToDevice), "H2D: %s")) {
+        const KArgs k = make_args(c, nullptr, nullptr, 0, false);
+        PoaArgs a;
+        a.pile = k.pile;
+        a.prm = k.prm;
+        a.pp = PoaParams{p->match, p->mismatch, p->gap_open, p->gap_ext, p->band_b, p->band_f_permille,
+                         p->max_seqs, p->max_len, p->max_nodes, p->support_radius, p->max_support};
+        a.loci = d_loci;
+        a.refined = d_ref;
+        a.n = (uint32_t)n;
+        a.ins_base = c->d_spoffI;
+        a.ins_off = c->d_ins_off;
+        a.ins_bases = c->d_ins_bases;
+        a.cap = cap;
+        a.out = d_out;
+        a.res = d_res;
+        a.nsupg = d_sup;
+        a.supg = d_sup + n;
+        a.est = d_aux + 1 + n;
+        a.diag = nullptr;
+        // supports + cost estimates, then the loci longest first (ties: input order)
+        hipLaunchKernelGGL(poa_support_kernel, dim3((unsigned)std::min<size_t>(n, 8192)), dim3(64), 0, nullptr, a);
+        std::vector<uint32_t> est(n), order(n);
+        if (chk(hipGetLastError(), "poa_support_kernel: %s") &&
+            chk(hipMemcpy(est.data(), a.est, n * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H: %s")) {
+            for (size_t i = 0; i < n; i++) order[i] = (uint32_t)i;
+            std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return est[x] > est[y]; });
+            chk(hipMemcpy(d_aux + 1, order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice), "H2D: %s");
+        }
+        if (s == SVT_OK)
+            s = poa_pool(c, c->poa_small, small_cap, POA_SMALL_SPILL, p, std::min<uint64_t>(n, POA_SLOTS_SMALL));
+        if (s == SVT_OK) s = poa_launch(c, a, c->poa_small, small_cap, POA_SMALL_SPILL, d_aux + 1, (uint32_t)n, d_aux);
+        if (s == SVT_OK && chk(hipMemcpy(res, d_res, n * sizeof(int4), hipMemcpyDeviceToHost), "D2H: %s")) {
+            std::vector<uint32_t> deferred;   // in the same longest-first order
+            for (size_t q = 0; q < n; q++)
+                if (res[order[q]].status == POA_DEFER) deferred.push_back(order[q]);
+            if (!deferred.empty()) {
+                const uint32_t nd = (uint32_t)deferred.size();
+                if (chk(hipMemcpy(d_aux + 1, deferred.data(), nd * sizeof(uint32_t), hipMemcpyHostToDevice), "H2D: %s"))
+                    s = poa_pool(c, c->poa_big, p->max_nodes, p->max_nodes + 2, p, std::min<uint64_t>(nd, POA_SLOTS_BIG));
+                if (s == SVT_OK) s = poa_launch(c, a, c->poa_big, p->max_nodes, p->max_nodes + 2, d_aux + 1, nd, d_aux);
+                if (s == SVT_OK) chk(hipMemcpy(res, d_res, n * sizeof(int4), hipMemcpyDeviceToHost), "D2H: %s");
+            }
+            c->poa_deferred = deferred.size();
+            if (s == SVT_OK && cap > 0) chk(hipMemcpy(bases, d_out, n * (size_t)cap, hipMemcpyDeviceToHost), "D2H: %s");
+        }
+    }
+    hfree(d_loci); hfree(d_ref); hfree(d_out); hfree(d_res); hfree(d_aux); hfree(d_sup);
+    return s;
+}
