@@ -31,6 +31,18 @@ SW_WINDOW_DTYPE = np.dtype([("candidate", "<i4"), ("support", "<i4")])          
 BGZF_BLOCK_DTYPE = np.dtype([("coff", "<u8"), ("uoff", "<u8"), ("clen", "<u4"), ("ulen", "<u4")])   # svt_bgzf_block
 RECORD_DTYPE = np.dtype([("index", "<u4"), ("start", "<u4"), ("end", "<u4"), ("pad", "<u4")])   # svt_record
 EVIDENCE_DTYPE = np.dtype([("support", "<u4"), ("depth", "<u4"), ("lo", "<u4"), ("hi", "<u4")])   # svt_evidence
+CALL_DTYPE = np.dtype([("type", "<i4"), ("chrom", "<i4"), ("pos", "<u4"), ("end", "<u4"), ("support", "<u4"),
+                       ("depth", "<u4"), ("len", "<u4"), ("len_lo", "<u4"), ("len_hi", "<u4"), ("x_lo", "<u4"),
+                       ("x_hi", "<u4"), ("pad", "<u4")])   # svt_call (48 B)
+
+
+class SvtCallParams(C.Structure):
+    _fields_ = [("link", C.c_int32), ("min_support", C.c_int32), ("types", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class SvtCallStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("events", "skipped", "clusters", "calls", "big_buckets")] + \
+        [("scan_ms", C.c_double)]
 
 
 class SvtParams(C.Structure):
@@ -129,6 +141,8 @@ ENGINE_SYMBOLS = (
 # include/svtrek_evidence.h: an extension the HIP engine exports; a backend without it (the CPU
 # restatement) still binds, and Engine.evidence raises on it
 EVIDENCE_SYMBOLS = ("svt_evidence_batch", "svt_evidence_device")
+# include/svtrek_call.h: likewise (Engine.call raises on a backend without it)
+CALL_SYMBOLS = ("svt_call_default_params", "svt_call_scan", "svt_call_fetch", "svt_call_device", "svt_call_stats_get")
 
 _engine = None
 
@@ -219,7 +233,21 @@ def bind_abi(lib: C.CDLL) -> C.CDLL:
         lib.svt_evidence_device.argtypes = [P, P, P, C.c_size_t, P, P]
         for name in EVIDENCE_SYMBOLS:
             getattr(lib, name).restype = C.c_int32
+    if has_call(lib):
+        lib.svt_call_default_params.argtypes = [P, C.POINTER(SvtCallParams)]
+        lib.svt_call_default_params.restype = None
+        lib.svt_call_scan.argtypes = [P, C.POINTER(SvtCallParams), C.POINTER(C.c_uint64)]
+        lib.svt_call_fetch.argtypes = [P, C.c_uint64, C.c_uint64, P]
+        lib.svt_call_device.argtypes = [P, C.POINTER(P), C.POINTER(C.c_uint64)]
+        lib.svt_call_stats_get.argtypes = [P, C.POINTER(SvtCallStats)]
+        for name in CALL_SYMBOLS[1:]:
+            getattr(lib, name).restype = C.c_int32
     return lib
+
+
+def has_call(lib: C.CDLL) -> bool:
+    """Does the library export include/svtrek_call.h's entry points?"""
+    return all(hasattr(lib, name) for name in CALL_SYMBOLS)
 
 
 def has_evidence(lib: C.CDLL) -> bool:

@@ -1,0 +1,346 @@
+// svt_call.inc -- discovery of DEL / INS calls from the value buckets (include/svtrek_call.h;
+// included by svt_engine.hip after svt_evidence.inc, the host side is svt_call_host.inc).
+//
+// The items of a scan are the OP_DEL events of array S and the events of array I, both filed by
+// the walk position x in 1 kb buckets per contig (svt_bucket_build.inc).  The buckets of a contig
+// are contiguous in ev and in value order, so x only has to be put in order INSIDE runs of whole
+// buckets; after that every (type, contig) stretch is sorted and a cluster is a run of neighbours.
+// No CIGAR is walked again, no host pass touches an event, nothing is sorted globally.
+//
+//   segments   (call_flag_kernel + one select, ONCE per loaded pileup: the extents never change)
+//              A bucket of more than CALL_H events is BIG and a segment by itself.  The other
+//              buckets of a (type, contig) are cut where the CALL_H-event chunk their first event
+//              lies in changes: the buckets starting in one chunk hold < 2 * CALL_H = CALL_TILE
+//              events.  Every boundary is a test of a bucket and its left neighbour alone.
+//   sort       (call_sort_kernel, one workgroup per segment) events -> 64-bit keys x << 28 | len;
+//              non-items, types not asked for and x >= 2^30 become the all-ones sentinel.  A
+//              segment of up to CALL_TILE keys is sorted in LDS, a big bucket in device memory,
+//              both by the same bitonic network whose comparators all point upwards, so that the
+//              slots past n never have to exist (an absent slot is a +inf that never moves).  Only
+//              a contig's last bucket (every value past the others, so no bound on its range of x)
+//              takes the in-memory network when it is big; any other big bucket spans 1 kb of x
+//              and is ordered by a counting sort over 1024 LDS counters (call_count_sort).
+//              The keys go to a scratch array at the events' own offsets, sentinels last in their
+//              segment; per segment {type-contig, largest valid x + 1} goes to a table.
+//   link       an exclusive max-scan of that table gives every segment the last valid x before it
+//              in its (type, contig); call_head_kernel marks the cluster heads (x - prev > link, or
+//              no prev); an inclusive sum of the marks numbers the clusters; call_accum_kernel
+//              adds every item into its cluster's record with integer atomics (exact in any
+//              order); call_pick_kernel + one select list the clusters with c >= min_support.
+//   emit       (call_emit_kernel, one wave per call) the rounded means, the depth as evidence's
+//              one-base region query (ev_depth), the 48-B record in 12 lanes' stores;
+//              call_merge_kernel then merges the DEL and the INS list, each in (chrom, pos) order
+//              as it comes, into (chrom, pos, type) order -- a binary search per call.
+// No two calls compare equal (clusters of one type and contig have disjoint x ranges, so their
+// rounded means differ), and no step depends on the order of the events inside a bucket.
+constexpr uint32_t CALL_H = 1024, CALL_TILE = 2 * CALL_H;
+constexpr int CALL_T = 256;                       // threads of the per-segment kernels
+constexpr uint64_t CALL_NONE = ~0ull;             // the sentinel key
+static_assert(sizeof(svt_call) == 48, "svt_call is copied as three 16-B words");
+
+struct CallAcc {   // 40 B, zeroed before every scan (the two minima are kept as maxima of ~v)
+    unsigned long long sx, slen;
+    uint32_t cnt, nlen_lo, len_hi, nx_lo, x_hi, seg;
+};
+
+struct CallArgs {
+    BkIndex bk;
+    DevPileup pile;
+    int32_t nt;
+    uint32_t n_s;                 // S events (the I events' keys follow them in the scratch)
+    uint64_t n_seg;
+    const uint64_t *seg;          // [n_seg] first combined bucket (array * nbk + bucket) of every segment
+    unsigned long long *keys;     // [n_s + n_i]
+    uint32_t *cid;                // [n_s + n_i] head marks, then cluster numbers (1-based, inclusive)
+    unsigned long long *tmax;     // [n_seg] (type * nt + contig) << 32 | largest valid x + 1 (0: none)
+    const unsigned long long *tprev;   // [n_seg] its exclusive max-scan
+    CallAcc *acc;
+    uint32_t *pick;               // the called clusters in cluster order, *pick_n of them
+    uint32_t *pick_n;
+    unsigned long long *stats;    // events, skipped, big buckets
+    uint32_t link, min_support, types;
+};
+
+// The contig of bucket g (cbase is ascending, cbase[0] == 0).
+__device__ __forceinline__ int call_contig(const BkIndex &B, int nt, uint64_t g) {
+    int lo = 0, hi = nt;
+    while (hi - lo > 1) {
+        const int m = (lo + hi) >> 1;
+        if (B.cbase[m] <= g) lo = m;
+        else hi = m;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void call_flag_kernel(BkIndex B, int nt, uint8_t *flag) {
+    const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (j >= 2 * B.nbk) return;
+    const uint64_t g = j >= B.nbk ? j - B.nbk : j;
+    const uint32_t *off = B.off + (uint64_t)(j >= B.nbk ? BA_I : BA_S) * (B.nbk + 1);
+    const uint32_t o0 = off[g], n = off[g + 1] - o0;
+    bool f = B.cbase[call_contig(B, nt, g)] == g || n > CALL_H;
+    if (!f) {
+        const uint32_t q0 = off[g - 1];
+        f = o0 - q0 > CALL_H || (o0 - off[0]) / CALL_H != (q0 - off[0]) / CALL_H;
+    }
+    flag[j] = f ? 1 : 0;
+}
+
+// One segment: its array, events [E0, E1), first key slot p0 and type-contig number sg.
+struct CallSeg {
+    uint32_t E0, n, p0, sg;
+    int a2;
+    bool last;   // the segment starts at its contig's last bucket (every value past the others)
+};
+__device__ __forceinline__ CallSeg call_seg(const CallArgs &a, uint64_t k) {
+    const uint64_t j0 = a.seg[k], j1 = k + 1 < a.n_seg ? a.seg[k + 1] : 2 * a.bk.nbk;
+    CallSeg s;
+    s.a2 = j0 >= a.bk.nbk ? 1 : 0;
+    const uint64_t g0 = j0 - (s.a2 ? a.bk.nbk : 0), g1 = g0 + (j1 - j0);
+    const uint32_t *off = a.bk.off + (uint64_t)(s.a2 ? BA_I : BA_S) * (a.bk.nbk + 1);
+    s.E0 = off[g0];
+    s.n = off[g1] - s.E0;
+    s.p0 = s.E0 - off[0] + (s.a2 ? a.n_s : 0u);
+    const int t = call_contig(a.bk, a.nt, g0);
+    s.sg = (uint32_t)s.a2 * (uint32_t)a.nt + (uint32_t)t;
+    s.last = g0 + 1 == a.bk.cbase[t] + a.bk.cnb[t];
+    return s;
+}
+
+// The bitonic network with every comparator pointing upwards, on n <= P = 2^k slots: a comparator
+// whose upper slot is >= n is skipped (the absent slots are +inf and never move).
+__device__ __forceinline__ void call_cmpswap(unsigned long long *k, uint32_t lo, uint32_t hi, uint32_t n) {
+    if (hi < n) {
+        const unsigned long long x = k[lo], y = k[hi];
+        if (x > y) { k[lo] = y; k[hi] = x; }
+    }
+}
+__device__ __forceinline__ void call_bitonic(unsigned long long *k, uint32_t n) {
+    uint32_t P = 1;
+    while (P < n) P <<= 1;
+    for (uint32_t w = 2; w <= P; w <<= 1) {
+        const uint32_t h = w >> 1;
+        for (uint32_t i = threadIdx.x; i < P / 2; i += CALL_T) {      // the mirror step
+            const uint32_t b = i / h, r = i % h;
+            call_cmpswap(k, b * w + r, b * w + w - 1 - r, n);
+        }
+        __syncthreads();
+        for (uint32_t d = w >> 2; d >= 1; d >>= 1) {
+            for (uint32_t i = threadIdx.x; i < P / 2; i += CALL_T) {
+                const uint32_t lo = (i / d) * 2 * d + i % d;
+                call_cmpswap(k, lo, lo + d, n);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// Keys of segment s into k (LDS, or the scratch itself for a big bucket), sorted; the sorted keys'
+// valid count into cnt[2], the items and the skipped ones into cnt[0] and cnt[1].
+template <bool BIG>
+__device__ __forceinline__ void call_sort_body(const CallArgs &a, const CallSeg &s, unsigned long long *k, uint32_t *cnt) {
+    const uint32_t want = s.a2 ? OP_INS : OP_DEL;
+    const bool asked = (a.types >> (s.a2 ? SVT_INS : SVT_DEL)) & 1u;
+    uint32_t items = 0, skipped = 0, valid = 0;
+    for (uint32_t i = threadIdx.x; i < s.n; i += CALL_T) {
+        const uint4 v = a.bk.ev[s.E0 + i];
+        const bool item = asked && (v.y & 0xfu) == want;
+        const bool sat = v.x >= IX_SAT;
+        items += item ? 1u : 0u;
+        skipped += item && sat ? 1u : 0u;
+        valid += item && !sat ? 1u : 0u;
+        k[i] = item && !sat ? ((unsigned long long)v.x << 28) | (v.y >> 4) : CALL_NONE;
+    }
+    if (items) atomicAdd(&cnt[0], items);
+    if (skipped) atomicAdd(&cnt[1], skipped);
+    if (valid) atomicAdd(&cnt[2], valid);
+    __syncthreads();
+    call_bitonic(k, s.n);
+    if (!BIG)
+        for (uint32_t i = threadIdx.x; i < s.n; i += CALL_T) a.keys[s.p0 + i] = k[i];
+}
+
+// One event of segment s as a key: the sentinel for non-items, types not asked for and x >= 2^30.
+__device__ __forceinline__ unsigned long long call_key(const CallArgs &a, const CallSeg &s, const uint4 &v) {
+    const bool asked = (a.types >> (s.a2 ? SVT_INS : SVT_DEL)) & 1u;
+    const bool ok = asked && (v.y & 0xfu) == (s.a2 ? OP_INS : OP_DEL) && v.x < IX_SAT;
+    return ok ? ((unsigned long long)v.x << 28) | (v.y >> 4) : CALL_NONE;
+}
+
+// A big bucket that is not its contig's last: every x lies in the bucket's own 1 kb, so a counting
+// sort by the x offset orders it in two passes over the events whatever their number -- a histogram
+// of 1024 LDS counters, their exclusive scan (wave 0, 16 slots a lane), then every key to the next
+// free slot of its x.  Keys of one x land in any order: nothing downstream reads it (the cluster
+// records are sums, minima and maxima).  The sentinels go behind the valid keys.
+__device__ __forceinline__ void call_count_sort(const CallArgs &a, const CallSeg &s, uint32_t *hist, uint32_t *cnt) {
+    const uint32_t want = s.a2 ? OP_INS : OP_DEL;
+    const bool asked = (a.types >> (s.a2 ? SVT_INS : SVT_DEL)) & 1u;
+    for (uint32_t i = threadIdx.x; i < CALL_H; i += CALL_T) hist[i] = 0;
+    __syncthreads();
+    uint32_t items = 0, skipped = 0, valid = 0;
+    for (uint32_t i = threadIdx.x; i < s.n; i += CALL_T) {
+        const uint4 v = a.bk.ev[s.E0 + i];
+        const bool item = asked && (v.y & 0xfu) == want;
+        const bool sat = v.x >= IX_SAT;
+        items += item ? 1u : 0u;
+        skipped += item && sat ? 1u : 0u;
+        valid += item && !sat ? 1u : 0u;
+        if (item && !sat) atomicAdd(&hist[v.x & (CALL_H - 1u)], 1u);
+    }
+    if (items) atomicAdd(&cnt[0], items);
+    if (skipped) atomicAdd(&cnt[1], skipped);
+    if (valid) atomicAdd(&cnt[2], valid);
+    __syncthreads();
+    if (threadIdx.x < WAVE) {   // counts -> first slots
+        constexpr uint32_t PER = CALL_H / WAVE;
+        uint32_t sum = 0;
+        for (uint32_t j = 0; j < PER; j++) sum += hist[threadIdx.x * PER + j];
+        uint32_t at = wave_scan_add(sum) - sum;
+        for (uint32_t j = 0; j < PER; j++) {
+            const uint32_t c = hist[threadIdx.x * PER + j];
+            hist[threadIdx.x * PER + j] = at;
+            at += c;
+        }
+    }
+    __syncthreads();
+    const uint32_t nv = cnt[2];
+    for (uint32_t i = threadIdx.x; i < s.n; i += CALL_T) {
+        const unsigned long long key = call_key(a, s, a.bk.ev[s.E0 + i]);
+        const uint32_t at = key != CALL_NONE ? atomicAdd(&hist[(uint32_t)(key >> 28) & (CALL_H - 1u)], 1u)
+                                             : nv + atomicAdd(&cnt[3], 1u);
+        if (at < s.n) a.keys[s.p0 + at] = key;   // (always: the two passes read the same events)
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(CALL_T) void call_sort_kernel(CallArgs a) {
+    __shared__ unsigned long long lk[CALL_TILE];
+    __shared__ uint32_t hist[CALL_H];
+    __shared__ uint32_t cnt[4];   // items, skipped, valid keys, sentinels placed (call_count_sort)
+    const CallSeg s = call_seg(a, blockIdx.x);
+    if (s.n == 0) {
+        if (threadIdx.x == 0) a.tmax[blockIdx.x] = (unsigned long long)s.sg << 32;
+        return;
+    }
+    if (threadIdx.x < 4) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const bool big = s.n > CALL_TILE;   // (more than CALL_H events in a segment: it is one bucket)
+    if (big && !s.last) call_count_sort(a, s, hist, cnt);
+    else if (big) call_sort_body<true>(a, s, a.keys + s.p0, cnt);
+    else call_sort_body<false>(a, s, lk, cnt);
+    if (threadIdx.x == 0) {   // (after the sort's last barrier, or -- n == 1 -- this thread's own store)
+        const uint32_t nv = cnt[2];
+        const uint32_t top = nv ? (uint32_t)((big ? a.keys[s.p0 + nv - 1] : lk[nv - 1]) >> 28) + 1u : 0u;
+        a.tmax[blockIdx.x] = (unsigned long long)s.sg << 32 | top;
+        if (cnt[0]) atomicAdd(&a.stats[0], (unsigned long long)cnt[0]);
+        if (cnt[1]) atomicAdd(&a.stats[1], (unsigned long long)cnt[1]);
+        if (big) atomicAdd(&a.stats[2], 1ull);
+    }
+}
+
+__global__ __launch_bounds__(CALL_T) void call_head_kernel(CallArgs a) {
+    const CallSeg s = call_seg(a, blockIdx.x);
+    const unsigned long long tp = a.tprev[blockIdx.x];
+    const bool have = (uint32_t)(tp >> 32) == s.sg && (uint32_t)tp != 0u;
+    for (uint32_t i = threadIdx.x; i < s.n; i += CALL_T) {
+        const unsigned long long key = a.keys[s.p0 + i];
+        bool head = false;
+        if (key != CALL_NONE) {
+            const uint32_t x = (uint32_t)(key >> 28);
+            if (i > 0) head = x - (uint32_t)(a.keys[s.p0 + i - 1] >> 28) > a.link;   // (valid: the sentinels come last)
+            else head = !have || x - ((uint32_t)tp - 1u) > a.link;
+        }
+        a.cid[s.p0 + i] = head ? 1u : 0u;
+    }
+}
+
+__global__ __launch_bounds__(CALL_T) void call_accum_kernel(CallArgs a) {
+    const CallSeg s = call_seg(a, blockIdx.x);
+    for (uint32_t i = threadIdx.x; i < s.n; i += CALL_T) {
+        const uint32_t p = s.p0 + i;
+        const unsigned long long key = a.keys[p];
+        const uint32_t c = a.cid[p];
+        if (key == CALL_NONE || c == 0u) continue;   // (c >= 1: a valid key is a head or follows one)
+        const uint32_t x = (uint32_t)(key >> 28), len = (uint32_t)key & 0xfffffffu;
+        CallAcc *q = a.acc + (c - 1u);
+        if (c != (p ? a.cid[p - 1] : 0u)) q->seg = s.sg;
+        atomicAdd(&q->cnt, 1u);
+        atomicAdd(&q->sx, (unsigned long long)x);
+        atomicAdd(&q->slen, (unsigned long long)len);
+        atomicMax(&q->nlen_lo, ~len);
+        atomicMax(&q->len_hi, len);
+        atomicMax(&q->nx_lo, ~x);
+        atomicMax(&q->x_hi, x);
+    }
+}
+
+// flag[c]: cluster c is a call; *n_del: the calls among the first n_s_clusters clusters (array S's: the
+// DEL calls), one atomic per wave.
+__global__ __launch_bounds__(256) void call_pick_kernel(CallArgs a, uint32_t n_clusters, uint32_t n_s_clusters, uint8_t *flag,
+                                                        uint32_t *n_del) {
+    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+    const bool call = c < n_clusters && a.acc[c].cnt >= a.min_support;
+    if (c < n_clusters) flag[c] = call ? 1 : 0;
+    const uint64_t m = ballot(call && c < n_s_clusters);
+    if (m && lane_id() == 0) atomicAdd(n_del, (uint32_t)__popcll(m));
+}
+
+__global__ __launch_bounds__(64 * WPB) void call_emit_kernel(CallArgs a, uint32_t n_calls, svt_call *out) {
+    const uint32_t g = blockIdx.x * WPB + (threadIdx.x >> 6);
+    if (g >= n_calls) return;
+    const CallAcc q = a.acc[(uint32_t)uniform_i((int32_t)a.pick[g])];
+    const unsigned long long c = q.cnt, h = c / 2;
+    const int ins = q.seg >= (uint32_t)a.nt ? 1 : 0, tid = (int)(q.seg - (ins ? (uint32_t)a.nt : 0u));
+    const uint32_t pos = (uint32_t)uniform_i((int32_t)(uint32_t)((q.sx + h) / c));
+    const uint32_t len = (uint32_t)((q.slen + h) / c);
+    const uint32_t end = ins ? pos + 1u : (uint32_t)((q.sx + q.slen + c + h) / c);
+    const uint32_t depth = ev_depth(a.pile, tid, pos);
+    const uint32_t w[12] = {(uint32_t)(ins ? SVT_INS : SVT_DEL), (uint32_t)(tid + 1), pos, end, q.cnt, depth, len,
+                            ~q.nlen_lo, q.len_hi, ~q.nx_lo, q.x_hi, 0u};
+    const int ln = lane_id();
+    uint32_t word = 0;
+#pragma unroll
+    for (int i = 0; i < 12; i++) word = ln == i ? w[i] : word;
+    if (ln < 12) reinterpret_cast<uint32_t *>(out + g)[ln] = word;
+}
+
+// The picked clusters are numbered in scan order: the n_del DEL calls first, then the INS calls, each
+// list in (chrom, pos) order already.  One thread per call merges the two lists: a DEL call goes behind
+// the INS calls at or before its (chrom, pos), an INS call behind the DEL calls strictly before it.
+__global__ __launch_bounds__(256) void call_merge_kernel(const svt_call *in, uint32_t n_calls, uint32_t n_del, svt_call *out) {
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= n_calls) return;
+    const bool del = g < n_del;
+    auto key = [&](uint32_t i) { return (unsigned long long)(uint32_t)in[i].chrom << 32 | in[i].pos; };
+    const unsigned long long k = key(g);
+    uint32_t lo = del ? n_del : 0u, hi = del ? n_calls : n_del;
+    const uint32_t base = lo;
+    while (lo < hi) {
+        const uint32_t m = lo + (hi - lo) / 2;
+        const unsigned long long o = key(m);
+        if (del ? o <= k : o < k) lo = m + 1;
+        else hi = m;
+    }
+    const uint32_t rank = (del ? g : g - n_del) + (lo - base);
+    const uint4 *src = reinterpret_cast<const uint4 *>(in + g);
+    uint4 *dst = reinterpret_cast<uint4 *>(out + rank);
+    dst[0] = src[0];
+    dst[1] = src[1];
+    dst[2] = src[2];
+}
+
+// A context's scan state: the segments (once per loaded pileup), the scratch, the last scan's calls.
+struct CallScratch {
+    bool ready = false;
+    uint64_t n_seg = 0;
+    uint64_t *d_seg = nullptr;
+    unsigned long long *d_keys = nullptr, *d_tmax = nullptr, *d_tprev = nullptr;
+    uint32_t *d_cid = nullptr, *d_pick = nullptr;
+    uint32_t *d_ctr = nullptr;        // [0] picked calls, [1] the DEL calls among them, [2..8) events / skipped / big buckets (64 bits each)
+    CallAcc *d_acc = nullptr;
+    uint8_t *d_tmp = nullptr;         // hipcub's temporary storage
+    uint8_t *d_flag = nullptr;        // per cluster: a call
+    svt_call *d_calls = nullptr, *d_raw = nullptr;   // in (chrom, pos, type) order / as emitted
+    uint64_t acc_cap = 0, pick_cap = 0, flag_cap = 0, tmp_cap = 0, calls_cap = 0, raw_cap = 0, n_calls = 0;
+    svt_call_stats stats{};
+};

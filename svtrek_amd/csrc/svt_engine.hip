@@ -27,6 +27,7 @@
 //                         refine_redo_kernel, sw_kernel, sw_reduce_kernel
 //   svt_lane.inc          refine_lane_kernel and its helpers
 //   svt_evidence.inc      read support, depth and value range per refined breakpoint
+//   svt_call.inc          DEL / INS discovery from the value buckets (host side: svt_call_host.inc)
 //   svt_index.inc, svt_index2.inc, svt_bucket_build.inc   the index builds (span lists, value buckets)
 //   svt_poa.inc, svt_poa_host.inc      allele consensus (POA): kernels, slot pools and poa_run
 //   svt_bam.inc, svt_inflate.inc, svt_bam_host.inc   BGZF inflate and BAM decode: kernels, svt_bam_dec_*
@@ -48,9 +49,10 @@
 
 #include "../../include/svtrek_gpu.h"
 #include "../../include/svtrek_evidence.h"
+#include "../../include/svtrek_call.h"
 #include "svt_bamrec.h"
 
-#define SVT_VERSION "svtrek_amd 0.26.0 (gfx950, value-bucketed event index filed by a lane-per-read walk with a 9-B LDS stage, band + prefix-max facts, packed span walk fed by readlane, lane vote on 64 windows a wave, BGZF inflate + BAM decode)"
+#define SVT_VERSION "svtrek_amd 0.27.0 (gfx950, value-bucketed event index filed by a lane-per-read walk with a 9-B LDS stage, band + prefix-max facts, packed span walk fed by readlane, lane vote on 64 windows a wave, BGZF inflate + BAM decode, DEL/INS discovery from the value buckets)"
 
 namespace {
 
@@ -163,6 +165,7 @@ constexpr int LV_WMAX = 1023;   // band half-width for 16-bit offsets and prefix
 #include "svt_refine.inc"
 #include "svt_lane.inc"
 #include "svt_evidence.inc"
+#include "svt_call.inc"
 #include "svt_index.inc"
 #include "svt_index2.inc"
 #include "svt_bucket_build.inc"
@@ -246,6 +249,7 @@ struct svt_ctx {
     size_t batch_cap = 0;
     svt_evidence *d_evid = nullptr;   // svt_evidence_batch's records [2 * evid_cap]
     size_t evid_cap = 0;
+    CallScratch call;                 // svt_call_scan (svt_call.inc): nothing allocated before the first scan
     // spill pool + status + work counters
     int32_t *d_pool = nullptr;
     unsigned long long pool_words = 0;
@@ -335,7 +339,15 @@ svt_status grow_pool(svt_ctx *c) {
     return SVT_OK;
 }
 
+void free_call(svt_ctx *c) {
+    CallScratch &k = c->call;
+    hfree(k.d_seg); hfree(k.d_keys); hfree(k.d_cid); hfree(k.d_tmax); hfree(k.d_tprev); hfree(k.d_acc);
+    hfree(k.d_pick); hfree(k.d_ctr); hfree(k.d_tmp); hfree(k.d_calls); hfree(k.d_raw); hfree(k.d_flag);
+    k = CallScratch{};
+}
+
 void free_pileup(svt_ctx *c) {
+    free_call(c);
     hfree(c->d_pos); hfree(c->d_emax); hfree(c->d_rec); hfree(c->d_clip8); hfree(c->d_off64);
     hfree(c->d_tid_off); hfree(c->d_bkt_off); hfree(c->d_bkt); hfree(c->d_cigar);
     hfree(c->d_ins_off); hfree(c->d_ins_bases);
@@ -1418,6 +1430,9 @@ svt_status svt_evidence_batch(svt_ctx *c, const svt_locus *loci, const svt_resul
         return evidence_1(x, loci + lo, refined + lo, hi - lo, out + 2 * lo);
     });
 }
+
+// ---- include/svtrek_call.h
+#include "svt_call_host.inc"
 
 uint64_t svt_pileup_device_bytes(const svt_ctx *c) { return c ? c->dev_bytes : 0; }
 

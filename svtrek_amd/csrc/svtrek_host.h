@@ -16,6 +16,7 @@
 
 #include "svtrek_gpu.h"
 #include "svtrek_evidence.h"
+#include "svtrek_call.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -107,6 +108,16 @@ char *svth_format_batch(const svt_locus *l, const svt_result *r, size_t n, int t
  * the "#row ..." column line first.  malloc'ed (free with svth_free), *len = its length. */
 char *svth_format_evidence(const svt_locus *l, const svt_result *r, const svt_evidence *ev, size_t n, int header,
                            int threads, size_t *len);
+/* The calls of `svtrek call` (include/svtrek_call.h) as VCF 4.2 text: with header != 0 the ##fileformat,
+ * ##source=svtrek_amd call, one ##contig=<ID=name> per names[0 .. n_names), the ##ALT / ##INFO lines and the
+ * #CHROM line; then per call
+ *   name  pos  svtrek.<TYPE>.<k>  N  <DEL>|<INS>  .  PASS
+ *   SVTYPE=T;END=e;SVLEN=[-]len;SUPPORT=c;DEPTH=d;XRANGE=x_lo,x_hi;LENRANGE=len_lo,len_hi
+ * name = names[chrom - 1] (the number itself when there is none), k the call's rank among those of its
+ * type (from 1).  SVTYPE and END come first and no key contains "END=" before them: svth_parse_line takes
+ * the first it finds.  malloc'ed (free with svth_free), *len = its length. */
+char *svth_format_calls(const svt_call *calls, size_t n, const char *const *names, size_t n_names, int header,
+                        int threads, size_t *len);
 void  svth_free(void *p);
 
 /* A11: stdout text for one refined record; returns bytes written (0 = prints nothing:

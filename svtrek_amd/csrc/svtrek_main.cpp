@@ -1,5 +1,6 @@
 // svtrek_main.cpp -- `svtrek audt -b BAM -v VCF [OPTIONS]`, drop-in for the reference CLI
-// (svtrek.c:5-22, init.c:21-147, audit.c:250-368) on MI355X.
+// (svtrek.c:5-22, init.c:21-147, audit.c:250-368) on MI355X, and `svtrek call -b BAM [OPTIONS]`:
+// DEL / INS discovery from the BAM alone (include/svtrek_call.h), written as a VCF `audt` reads.
 //
 // Same flags, defaults and stdout bytes as the reference; records are printed in VCF
 // order (the reference prints in worker completion order and drops up to 2*T trailing
@@ -31,6 +32,11 @@
 // include/svtrek_evidence.h is an extension: this file is also linked against backends that do
 // not export it, so the entry point is referenced weakly and tested before use.
 extern "C" __typeof__(svt_evidence_batch) svt_evidence_batch __attribute__((weak));
+// include/svtrek_call.h likewise
+extern "C" __typeof__(svt_call_default_params) svt_call_default_params __attribute__((weak));
+extern "C" __typeof__(svt_call_scan) svt_call_scan __attribute__((weak));
+extern "C" __typeof__(svt_call_fetch) svt_call_fetch __attribute__((weak));
+extern "C" __typeof__(svt_call_stats_get) svt_call_stats_get __attribute__((weak));
 
 namespace {
 
@@ -42,6 +48,21 @@ void usage() {
     printf("Mode:\n");
     printf("    disc    Variation discovery on graph alignment result.\n");
     printf("    audt    Audit the reported variations on VCF using BAM.\n");
+    printf("    call    Discover DEL/INS calls from the BAM alone (svtrek_amd); writes a VCF audt reads.\n");
+}
+
+void call_usage() {
+    printf("Usage: ./svtrek call [-b|--bam BAM] [OPTIONS]\n");
+    printf("Options:\n");
+    printf("    [-o|--output] <filename>          Output VCF [Default: stdout]\n");
+    printf("    -t <num>                          Thread number [Default: %d]\n", THREADS);
+    printf("    --link <num>                      Largest gap between neighbouring starts of one cluster [Default: 10]\n");
+    printf("    --min-support <num>               Fewest D > 50 / I >= 50 ops of a call [Default: %d]\n", MIN_COUNT);
+    printf("    --types <DEL,INS>                 Types to call [Default: DEL,INS]\n");
+    printf("    --device <num>                    GPU index [Default: 0]\n");
+    printf("    --inflate <auto|gpu|cpu>          BGZF decompression of the BAM: the GPU or -t host threads;\n");
+    printf("                                      auto: the GPU from 1 GiB of BAM on [Default: auto]\n");
+    printf("    --verbose                         Scan statistics and stage timings on stderr [Default: false]\n");
 }
 
 void audt_usage() {
@@ -531,6 +552,124 @@ int audit(int argc, char **argv) {
     return 0;
 }
 
+// `svtrek call`: the BAM into a pileup as audt reads it (host threads, or the device's inflate with the
+// host parse -- the ingest that keeps the reference names), svt_call_scan, the calls as VCF text.
+int call_mode(int argc, char **argv) {
+    const char *bam_path = nullptr, *out_path = nullptr;
+    int threads = THREADS, verbose = 0, device = 0, gpu_inflate = -1, link = -1, min_support = -1;
+    uint32_t types = (1u << SVT_INS) | (1u << SVT_DEL);
+    static const option opts[] = {
+        {"bam", required_argument, nullptr, 1}, {"output", required_argument, nullptr, 3},
+        {"verbose", no_argument, nullptr, 4}, {"help", no_argument, nullptr, 11},
+        {"device", required_argument, nullptr, 21}, {"inflate", required_argument, nullptr, 25},
+        {"link", required_argument, nullptr, 30}, {"min-support", required_argument, nullptr, 31},
+        {"types", required_argument, nullptr, 32}, {nullptr, 0, nullptr, 0}};
+    int opt, li;
+    while ((opt = getopt_long(argc, argv, "b:o:t:h", opts, &li)) != -1) {
+        switch (opt) {
+        case 'b': case 1: bam_path = optarg; break;
+        case 'o': case 3: out_path = optarg; break;
+        case 4: verbose = 1; break;
+        case 't': threads = atoi(optarg); break;
+        case 'h': case 11: call_usage(); exit(EXIT_SUCCESS);
+        case 21: device = atoi(optarg); break;
+        case 25:
+            if (strcmp(optarg, "gpu") && strcmp(optarg, "cpu") && strcmp(optarg, "auto")) {
+                fprintf(stderr, "[ERROR] --inflate expects auto, gpu or cpu\n");
+                exit(EXIT_FAILURE);
+            }
+            gpu_inflate = strcmp(optarg, "gpu") == 0 ? 1 : strcmp(optarg, "cpu") == 0 ? 0 : -1;
+            break;
+        case 30: link = atoi(optarg); if (link < 0) { fprintf(stderr, "[ERROR] --link must be >= 0\n"); exit(EXIT_FAILURE); } break;
+        case 31: min_support = atoi(optarg); if (min_support < 1) { fprintf(stderr, "[ERROR] --min-support must be >= 1\n"); exit(EXIT_FAILURE); } break;
+        case 32: {
+            types = 0;
+            std::string t(optarg);
+            for (size_t i = 0; i <= t.size();) {
+                const size_t e = std::min(t.find(',', i), t.size());
+                const std::string w = t.substr(i, e - i);
+                if (w == "DEL") types |= 1u << SVT_DEL;
+                else if (w == "INS") types |= 1u << SVT_INS;
+                else { fprintf(stderr, "[ERROR] --types expects DEL, INS or DEL,INS\n"); exit(EXIT_FAILURE); }
+                i = e + 1;
+            }
+            break;
+        }
+        default:
+            printf("[ERROR] Option %d is invalid.\n", opt);
+            call_usage();
+            exit(EXIT_FAILURE);
+        }
+    }
+    validate_file(bam_path, "[ERROR] BAM file is not provided.");
+    if (threads < 1) { fprintf(stderr, "[ERROR] -t must be >= 1\n"); exit(EXIT_FAILURE); }
+    if (!svt_call_scan || !svt_call_default_params || !svt_call_fetch || !svt_call_stats_get) {
+        fprintf(stderr, "[ERROR] call: not supported by this backend\n");
+        return 1;
+    }
+    if (gpu_inflate < 0) {
+        struct stat st;
+        gpu_inflate = stat(bam_path, &st) == 0 && st.st_size >= (off_t)(1ll << 30) ? 1 : 0;
+    }
+    const double t0 = now_s();
+    svt_params prm{WIDER, MEDIAN, NARROW, CI_RANGE, CI, MIN_COUNT, 0};
+    svt_ctx *ctx = nullptr;
+    int open_rc = 0;
+    std::promise<void> opened;
+    DeviceInflate dinf{opened.get_future().share(), &ctx, &open_rc};
+    std::thread ot([&] {   // the context opens beside the ingest
+        open_rc = svt_open(&prm, device, &ctx);
+        opened.set_value();
+    });
+    char err[512];
+    const svth_inflater dev_inf{device_inflate, device_host_alloc, device_host_free, &dinf, (size_t)1024 << 20};
+    svth_bam *bam = svth_bam_read_ex(bam_path, threads, -1, 0, -1, 0, gpu_inflate ? &dev_inf : nullptr, err, sizeof err);
+    ot.join();
+    auto done = [&](int rc) {
+        svth_bam_free(bam);
+        if (ctx) svt_close(ctx);
+        return rc;
+    };
+    if (!bam) { fprintf(stderr, "[ERROR] %s\n", err); return done(1); }
+    if (open_rc || !ctx) { fprintf(stderr, "[ERROR] GPU %d: svt_open failed (HIP device?) (status %d)\n", device, open_rc); return done(1); }
+    const double t_ingest = now_s();
+    svt_pileup_view view{};
+    svth_bam_view(bam, &view);
+    svt_call_params cp;
+    svt_call_default_params(ctx, &cp);
+    if (link >= 0) cp.link = link;
+    if (min_support >= 1) cp.min_support = min_support;
+    cp.types = types;
+    uint64_t n = 0;
+    svt_status s = svt_load_pileup(ctx, &view);
+    const double t_load = now_s();
+    if (!s) s = svt_call_scan(ctx, &cp, &n);
+    std::vector<svt_call> calls((size_t)n);
+    if (!s) s = svt_call_fetch(ctx, 0, n, calls.data());
+    svt_call_stats st{};
+    if (!s) s = svt_call_stats_get(ctx, &st);
+    if (s) { fprintf(stderr, "[ERROR] GPU %d: %s (status %d)\n", device, svt_last_error(ctx), (int)s); return done(1); }
+    const double t_scan = now_s();
+    std::vector<const char *> names((size_t)svth_bam_n_targets(bam));
+    for (size_t t = 0; t < names.size(); t++) names[t] = svth_bam_target_name(bam, (int32_t)t);
+    size_t olen = 0;
+    char *text = svth_format_calls(calls.data(), calls.size(), names.data(), names.size(), 1, threads, &olen);
+    if (!text) { fprintf(stderr, "[ERROR] out of host memory\n"); return done(1); }
+    FILE *of = out_path ? fopen(out_path, "wb") : stdout;
+    bool ok = of && fwrite(text, 1, olen, of) == olen;
+    if (of && out_path) ok = fclose(of) == 0 && ok;
+    else if (of) ok = fflush(of) == 0 && ok;
+    svth_free(text);
+    if (!ok) { fprintf(stderr, "[ERROR] call: cannot write %s\n", out_path ? out_path : "stdout"); return done(1); }
+    if (verbose)
+        fprintf(stderr, "[svtrek_amd] call: ingest %.3fs (%s)  load %.3fs  scan+fetch %.3fs (device scan %.3f ms)  print %.3fs  "
+                        "items %llu (skipped %llu)  clusters %llu  calls %llu  big buckets %llu  link %d  min-support %d\n",
+                t_ingest - t0, gpu_inflate ? "gpu inflate, host parse" : "cpu", t_load - t_ingest, t_scan - t_load, st.scan_ms,
+                now_s() - t_scan, (unsigned long long)st.events, (unsigned long long)st.skipped, (unsigned long long)st.clusters,
+                (unsigned long long)st.calls, (unsigned long long)st.big_buckets, cp.link, cp.min_support);
+    return done(0);
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -540,6 +679,9 @@ int main(int argc, char **argv) {
     }
     if (strcmp(argv[1], "audt") == 0) {
         return audit(argc, argv);   // 0 on success; 1 on ingest/GPU errors (the reference crashes)
+    }
+    if (strcmp(argv[1], "call") == 0) {
+        return call_mode(argc, argv);   // 0 on success; 1 on ingest/GPU errors
     }
     if (strcmp(argv[1], "disc") == 0) {
         fprintf(stderr, "[ERROR] disc mode is not part of svtrek_amd (it implements the audt path only)\n");

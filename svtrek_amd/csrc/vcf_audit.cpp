@@ -228,6 +228,66 @@ char *svth_format_evidence(const svt_locus *l, const svt_result *r, const svt_ev
     return out;
 }
 
+char *svth_format_calls(const svt_call *c, size_t n, const char *const *names, size_t n_names, int header, int threads,
+                        size_t *len) {
+    const int T = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(threads, 1), n / 16384 + 1));
+    // the ID's k: the call's rank among the calls of its type (1-based)
+    std::vector<size_t> first_k((size_t)T * 2 + 2, 0);
+    for (int t = 0; t < T; t++) {
+        size_t d = 0, i = 0;
+        for (size_t k = n * (size_t)t / (size_t)T, e = n * (size_t)(t + 1) / (size_t)T; k < e; k++) (c[k].type == SVT_DEL ? d : i)++;
+        first_k[2 * (size_t)t + 2] = first_k[2 * (size_t)t] + d;
+        first_k[2 * (size_t)t + 3] = first_k[2 * (size_t)t + 1] + i;
+    }
+    std::vector<std::string> part((size_t)T);
+    run_parts(T, [&](int t) {
+        std::string &o = part[(size_t)t];
+        const size_t b = n * (size_t)t / (size_t)T, e = n * (size_t)(t + 1) / (size_t)T;
+        o.reserve((e - b) * 160);
+        size_t rank[2] = {first_k[2 * (size_t)t], first_k[2 * (size_t)t + 1]};
+        char buf[320], num[16];
+        for (size_t k = b; k < e; k++) {
+            const svt_call &x = c[k];
+            const bool del = x.type == SVT_DEL;
+            const char *ty = del ? "DEL" : "INS";
+            const char *name = num;
+            if (x.chrom >= 1 && (size_t)x.chrom <= n_names && names && names[x.chrom - 1]) name = names[x.chrom - 1];
+            else snprintf(num, sizeof num, "%d", x.chrom);
+            o += name;
+            const int m = snprintf(buf, sizeof buf,
+                                   "\t%u\tsvtrek.%s.%zu\tN\t<%s>\t.\tPASS\tSVTYPE=%s;END=%u;SVLEN=%s%u;SUPPORT=%u;DEPTH=%u;"
+                                   "XRANGE=%u,%u;LENRANGE=%u,%u\n",
+                                   x.pos, ty, ++rank[del ? 0 : 1], ty, ty, x.end, del ? "-" : "", x.len, x.support, x.depth,
+                                   x.x_lo, x.x_hi, x.len_lo, x.len_hi);
+            o.append(buf, (size_t)m);
+        }
+    });
+    std::string head;
+    if (header) {
+        head = "##fileformat=VCFv4.2\n##source=svtrek_amd call\n";
+        for (size_t t = 0; t < n_names; t++) head += std::string("##contig=<ID=") + (names && names[t] ? names[t] : "") + ">\n";
+        head += "##ALT=<ID=DEL,Description=\"Deletion\">\n##ALT=<ID=INS,Description=\"Insertion\">\n"
+                "##INFO=<ID=SVTYPE,Number=1,Type=String,Description=\"Type of structural variant\">\n"
+                "##INFO=<ID=END,Number=1,Type=Integer,Description=\"DEL: rounded mean of the ops' walk end + 1; INS: POS + 1\">\n"
+                "##INFO=<ID=SVLEN,Number=1,Type=Integer,Description=\"Rounded mean length of the supporting ops (negative: DEL)\">\n"
+                "##INFO=<ID=SUPPORT,Number=1,Type=Integer,Description=\"CIGAR ops in the cluster\">\n"
+                "##INFO=<ID=DEPTH,Number=1,Type=Integer,Description=\"Reads covering POS\">\n"
+                "##INFO=<ID=XRANGE,Number=2,Type=Integer,Description=\"Smallest and largest start of the supporting ops\">\n"
+                "##INFO=<ID=LENRANGE,Number=2,Type=Integer,Description=\"Smallest and largest length of the supporting ops\">\n"
+                "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n";
+    }
+    size_t tot = head.size();
+    for (auto &p : part) tot += p.size();
+    char *out = (char *)malloc(tot + 1);
+    if (!out) return nullptr;
+    memcpy(out, head.data(), head.size());
+    size_t at = head.size();
+    for (auto &p : part) { memcpy(out + at, p.data(), p.size()); at += p.size(); }
+    out[tot] = 0;
+    if (len) *len = tot;
+    return out;
+}
+
 void svth_free(void *p) { free(p); }
 
 int svth_parse_line(char *line, svt_locus *l, char *err, size_t errcap) {

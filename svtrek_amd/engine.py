@@ -13,9 +13,9 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import (EVIDENCE_DTYPE, LOCUS_DTYPE, POA_RESULT_DTYPE, RESULT_DTYPE, STATUS_NAMES, SVT_EINVAL, SW_QUERY_DTYPE,
-                   SW_WINDOW_DTYPE, SvtInsseqView, SvtLoadStats, SvtParams, SvtPoaParams, SvtWork, has_evidence,
-                   load_engine, ptr)
+from ._lib import (CALL_DTYPE, EVIDENCE_DTYPE, LOCUS_DTYPE, POA_RESULT_DTYPE, RESULT_DTYPE, STATUS_NAMES, SVT_DEL,
+                   SVT_EINVAL, SVT_INS, SW_QUERY_DTYPE, SW_WINDOW_DTYPE, SvtCallParams, SvtCallStats, SvtInsseqView,
+                   SvtLoadStats, SvtParams, SvtPoaParams, SvtWork, has_call, has_evidence, load_engine, ptr)
 from .pileup import Pileup
 
 # params.h:27-32
@@ -128,6 +128,49 @@ class Engine:
         self._need_evidence()
         self._check(self.lib.svt_evidence_device(self._h, C.c_void_p(d_loci), C.c_void_p(d_refined), n,
                                                  C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
+    # ---- discovery (include/svtrek_call.h): DEL / INS calls from the loaded pileup alone
+    def _need_call(self) -> None:
+        if not has_call(self.lib):
+            raise SvtError(SVT_EINVAL, "this backend does not export svt_call_scan (include/svtrek_call.h): "
+                                       "discovery needs the HIP engine")
+
+    def call(self, link: int | None = None, min_support: int | None = None, types=("DEL", "INS")) -> np.ndarray:
+        """Cluster the pileup's D > 50 / I >= 50 ops by start (svt_call_scan): CALL_DTYPE records in
+        (chrom, pos, type) order.  link: the largest gap between neighbouring starts of one cluster
+        (default 10); min_support: the fewest ops of a call (default consensus_min_count)."""
+        self._need_call()
+        p = SvtCallParams()
+        self.lib.svt_call_default_params(self._h, C.byref(p))
+        if link is not None:
+            p.link = int(link)
+        if min_support is not None:
+            p.min_support = int(min_support)
+        p.types = call_type_bits(types)
+        n = C.c_uint64(0)
+        self._check(self.lib.svt_call_scan(self._h, C.byref(p), C.byref(n)))
+        return self.call_fetch(0, n.value)
+
+    def call_fetch(self, first: int, n: int) -> np.ndarray:
+        """Calls [first, first + n) of the last scan (svt_call_fetch)."""
+        self._need_call()
+        out = np.empty(int(n), dtype=CALL_DTYPE)
+        self._check(self.lib.svt_call_fetch(self._h, int(first), int(n), ptr(out) if n else None))
+        return out
+
+    def call_device(self) -> tuple[int, int]:
+        """(device pointer, count) of the last scan's calls: valid until the next scan / load / close."""
+        self._need_call()
+        d = C.c_void_p()
+        n = C.c_uint64(0)
+        self._check(self.lib.svt_call_device(self._h, C.byref(d), C.byref(n)))
+        return int(d.value or 0), int(n.value)
+
+    def call_stats(self) -> dict:
+        self._need_call()
+        st = SvtCallStats()
+        self._check(self.lib.svt_call_stats_get(self._h, C.byref(st)))
+        return {k: (float(getattr(st, k)) if k == "scan_ms" else int(getattr(st, k))) for k, _ in SvtCallStats._fields_}
 
     def reindex(self, stream: int | None = None) -> None:
         """Rebuild the device index of the loaded pileup on a hipStream_t handle (svt_reindex:
@@ -247,6 +290,27 @@ class Engine:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def call_type_bits(types) -> int:
+    """svt_call_params.types of DEL / INS names (a comma-separated string or a sequence)."""
+    names = types.split(",") if isinstance(types, str) else list(types)
+    code = {"DEL": SVT_DEL, "INS": SVT_INS}
+    bits = 0
+    for t in names:
+        if str(t).strip().upper() not in code:
+            raise ValueError(f"call: unknown type {t!r} (DEL, INS)")
+        bits |= 1 << code[str(t).strip().upper()]
+    return bits
+
+
+def calls_to_loci(calls: np.ndarray) -> np.ndarray:
+    """CALL_DTYPE records as the LOCUS_DTYPE loci refine / evidence / audt take."""
+    calls = np.asarray(calls, dtype=CALL_DTYPE)
+    loci = np.empty(len(calls), dtype=LOCUS_DTYPE)
+    for f in ("type", "chrom", "pos", "end"):
+        loci[f] = calls[f]
+    return loci
 
 
 def version() -> str:

@@ -44,6 +44,8 @@ def load_host() -> C.CDLL:
         L.svth_format_batch.restype = P
         L.svth_format_evidence.argtypes = [P, P, P, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
         L.svth_format_evidence.restype = P
+        L.svth_format_calls.argtypes = [P, C.c_size_t, P, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+        L.svth_format_calls.restype = P
         L.svth_free.argtypes = [P]
         L.svth_free.restype = None
         L.svth_bam_free.argtypes = [P]
@@ -254,6 +256,25 @@ def format_evidence(loci: np.ndarray, res: np.ndarray, ev: np.ndarray, header: b
                                C.byref(n))
     if not p:
         raise MemoryError("svth_format_evidence failed")
+    try:
+        return C.string_at(p, n.value).decode("latin-1")
+    finally:
+        L.svth_free(p)
+
+
+def format_calls(calls: np.ndarray, names, header: bool = True, threads: int = 4) -> str:
+    """`svtrek call`'s VCF text of CALL_DTYPE records (svth_format_calls); names: the BAM's reference
+    names, names[chrom - 1] is a call's CHROM."""
+    from ._lib import CALL_DTYPE
+    L = load_host()
+    calls = np.ascontiguousarray(calls, dtype=CALL_DTYPE)
+    enc = [str(x).encode() for x in names]
+    arr = (C.c_char_p * max(len(enc), 1))(*enc)
+    n = C.c_size_t(0)
+    p = L.svth_format_calls(calls.ctypes.data if len(calls) else None, len(calls), arr, len(enc), int(header), threads,
+                            C.byref(n))
+    if not p:
+        raise MemoryError("svth_format_calls failed")
     try:
         return C.string_at(p, n.value).decode("latin-1")
     finally:

@@ -1,0 +1,163 @@
+"""DEL / INS discovery (include/svtrek_call.h) on a BASELINE workload.
+
+Times svt_call_scan (its own HIP-event time, stats.scan_ms: the median of --repeat scans after a
+warm-up) next to the same process's svt_reindex, and prices the scan's algorithmic bytes: 16 B per
+event of the value-bucket arrays S and I read (the items and array S's trailing-S markers), 8 B per
+key of the scratch written by the sort and 8 B read back by each of the two passes over it, 48 B
+per call written.  Recall and extra calls
+against the simulator's truth are reported for context: a truth breakpoint counts as found when a
+call of its type and contig lies within --tol bp of bp1.  Prints one JSON line.
+
+    python tools/bench_call.py [--workload cfg4_1m_delins_30x_hifi] [--repeat 20]
+
+--hotspot N [--hotspot-last] times the scan on a synthetic hot spot instead: N reads with one D op
+each, all starting in one 1-kb bucket (700 distinct starts: the counting sort of a big bucket) or,
+with --hotspot-last, spread over 650 kb of the contig's last bucket (the in-memory bitonic sort).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from svtrek_amd import SVT_DEL, SVT_INS, Engine, Params, sim, version  # noqa: E402
+
+
+def recall(calls: np.ndarray, loci: np.ndarray, truth: np.ndarray, tol: int) -> dict:
+    out = {}
+    for name, ty in (("DEL", SVT_DEL), ("INS", SVT_INS)):
+        sel = loci["type"] == ty
+        mine = calls[calls["type"] == ty]
+        found = 0
+        for chrom in np.unique(loci["chrom"][sel]):
+            cp = np.sort(mine["pos"][mine["chrom"] == chrom].astype(np.int64))
+            bp = truth[sel & (loci["chrom"] == chrom), 0].astype(np.int64)
+            if len(cp) == 0:
+                continue
+            j = np.clip(np.searchsorted(cp, bp), 1, max(len(cp) - 1, 1))
+            near = np.abs(cp[np.minimum(j, len(cp) - 1)] - bp)
+            near = np.minimum(near, np.abs(cp[j - 1] - bp))
+            found += int((near <= tol).sum())
+        out[name] = {"truth": int(sel.sum()), "found": found, "calls": int(len(mine))}
+    return out
+
+
+def hotspot_pileup(n: int, last: bool):
+    """n reads at pos 499 800 with [M | H] lead, D 60 + k % 50, M 60: the D ops start at 500 000 + k % 700
+    (one regular bucket) or, behind an H op that endpos does not count, at 2 499 800 + 13 * (k % 50 000)."""
+    from svtrek_amd import Pileup
+    k = np.arange(n, dtype=np.int64)
+    lead = 2_000_000 + 13 * (k % 50_000) if last else 200 + k % 700
+    dlen = 60 + k % 50
+    cigar = np.stack([(lead << 4) | (5 if last else 0), (dlen << 4) | 2, np.full(n, (60 << 4) | 0)], axis=1)
+    pos = np.full(n, 499_800, dtype=np.int32)
+    endpos = pos + dlen + 60 + (0 if last else lead)
+    return Pileup(tid_off=np.array([0, n], dtype=np.int64), pos=pos, endpos=endpos.astype(np.int32),
+                  cig_off=(3 * np.arange(n + 1)).astype(np.uint64), cigar=cigar.reshape(-1).astype(np.uint32),
+                  clip=np.zeros(n, dtype=np.uint8))
+
+
+def hotspot(a) -> None:
+    pl = hotspot_pileup(a.hotspot, a.hotspot_last)
+    eng = Engine(Params(), device=0)
+    eng.load_pileup(pl)
+    ms = []
+    for k in range(a.warmup + a.repeat):
+        calls = eng.call(link=a.link, min_support=a.min_support)
+        if k >= a.warmup:
+            ms.append(eng.call_stats()["scan_ms"])
+    st = eng.call_stats()
+    print(json.dumps({
+        "metric": "svt_call_scan ms on one hot bucket (1 GPU)", "value": round(float(np.median(ms)), 4), "unit": "ms",
+        "bucket": "the contig's last (in-memory bitonic sort)" if a.hotspot_last else "regular (counting sort)",
+        "items": a.hotspot, "scan_ms_all": [round(x, 4) for x in ms], "events": st["events"], "clusters": st["clusters"],
+        "calls": int(len(calls)), "big_buckets": st["big_buckets"],
+        "timing": f"svt_call_stats.scan_ms, median of {a.repeat} after {a.warmup} warm-up scans", "engine_version": version(),
+    }))
+    eng.close()
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", default="cfg4_1m_delins_30x_hifi")
+    ap.add_argument("--repeat", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--link", type=int, default=None)
+    ap.add_argument("--min-support", type=int, default=None)
+    ap.add_argument("--tol", type=int, default=10)
+    ap.add_argument("--hotspot", type=int, default=0)
+    ap.add_argument("--hotspot-last", action="store_true")
+    a = ap.parse_args()
+    if a.hotspot:
+        hotspot(a)
+        return
+
+    t0 = time.perf_counter()
+    r = sim.generate(sim.WORKLOADS[a.workload])
+    t_gen = time.perf_counter() - t0
+    eng = Engine(Params(), device=0)
+    eng.load_pileup(r.pileup)
+    import torch
+    s = torch.cuda.Stream()
+
+    reindex_ms = []
+    for k in range(a.warmup + a.repeat):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(s)
+        eng.reindex(s.cuda_stream)
+        e1.record(s)
+        e1.synchronize()
+        if k >= a.warmup:
+            reindex_ms.append(e0.elapsed_time(e1))
+    scan_ms, wall_ms = [], []
+    calls = None
+    for k in range(a.warmup + a.repeat):
+        t0 = time.perf_counter()
+        calls = eng.call(link=a.link, min_support=a.min_support)
+        t1 = time.perf_counter()
+        if k >= a.warmup:
+            scan_ms.append(eng.call_stats()["scan_ms"])
+            wall_ms.append((t1 - t0) * 1e3)
+    st = eng.call_stats()
+    med = float(np.median(scan_ms))
+    # the events the scan reads: the items (D > 50 of array S, I >= 50 of array I) and the trailing-S
+    # markers array S also holds, one per read whose CIGAR ends in S
+    pl = r.pileup
+    if pl.clip is not None:
+        markers = int((pl.clip & 1).astype(bool).sum())
+    else:
+        nops = np.diff(pl.cig_off.astype(np.int64))
+        last = pl.cig_off[1:].astype(np.int64)[nops > 0] - 1
+        markers = int(((pl.cigar[last] & 15) == 4).sum())
+    keys = st["events"] + markers
+    alg = 16 * keys + 8 * keys + 2 * 8 * keys + 48 * st["calls"]
+    print(json.dumps({
+        "metric": "svt_call_scan ms (1 GPU)", "value": round(med, 4), "unit": "ms",
+        "workload": a.workload, "reads": int(r.pileup.n_reads), "cigar_ops": int(r.pileup.cig_off[-1]),
+        "scan_ms": round(med, 4), "scan_ms_all": [round(x, 4) for x in scan_ms],
+        "call_wall_ms": round(float(np.median(wall_ms)), 3),
+        "reindex_ms": round(float(np.median(reindex_ms)), 4), "reindex_ms_all": [round(x, 4) for x in reindex_ms],
+        "timing": f"scan: svt_call_stats.scan_ms (HIP events around the whole scan), median of "
+                  f"{a.repeat} after {a.warmup} warm-up scans; call_wall: Engine.call with the fetch; reindex: HIP events "
+                  "around svt_reindex on one stream",
+        "events": st["events"], "skipped": st["skipped"], "clusters": st["clusters"], "calls": st["calls"],
+        "big_buckets": st["big_buckets"], "events_read": keys,
+        "alg_bytes_per_scan": alg, "alg_gbs": round(alg / (med * 1e-3) / 1e9, 2),
+        "alg": "per event of arrays S and I (items + trailing-S markers): 16 B read + 8 B key written + 2 x 8 B key read; "
+               "48 B per call",
+        "truth": recall(calls, r.loci, r.truth, a.tol), "tol": a.tol,
+        "setup_s": {"generate": round(t_gen, 2)}, "engine_version": version(),
+    }))
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
