@@ -14,49 +14,40 @@ struct svt_bam_dec {
     int32_t n_ref = 0;
     hipStream_t st = nullptr;
     hipStream_t cst = nullptr;                // the copy stream
-    hipEvent_t cev = nullptr;                 // the latest batch's bytes are on the device
-    uint8_t *d_comp[2] = {nullptr, nullptr};  // compressed batches (alternating)
-    size_t comp_cap[2] = {0, 0};
-    svt_bgzf_block *d_blk[2] = {nullptr, nullptr};
-    size_t blk_cap[2] = {0, 0};
+    DevEvent cev;                             // the latest batch's bytes are on the device
+    DevBuf<uint8_t> d_comp[2];                // compressed batches (alternating)
+    DevBuf<svt_bgzf_block> d_blk[2];
     int ib = 0;                               // the next batch's input buffer
-    uint32_t *d_err = nullptr;                // the inflate's first bad block (this decoder's own word)
+    DevBuf<uint32_t> d_err;                   // the inflate's first bad block (this decoder's own word)
     bool pend = false;                        // a batch inflated (or inflating) but not yet decoded
     size_t pend_n = 0;
     uint64_t pend_u = 0, pend_r0 = 0;
-    uint8_t *d_buf[2] = {nullptr, nullptr};   // inflated batches: [carried tail | this batch]
-    size_t buf_cap[2] = {0, 0};
+    DevBuf<uint8_t> d_buf[2];                 // inflated batches: [carried tail | this batch]
     int cur = 0;
     uint64_t tail = 0;                        // bytes of the incomplete record at the front of d_buf[cur]
     bool first = true;
-    BdChunk *d_ch = nullptr;
-    uint32_t *d_base = nullptr;
-    size_t ch_cap = 0, base_cap = 0;
-    BdRec *d_rec = nullptr;
-    BdTot *d_pre = nullptr;
-    size_t rec_cap = 0, pre_cap = 0;
-    BdCheck *d_chk = nullptr;
-    void *d_tmp = nullptr;
-    size_t tmp_cap = 0;
-    BdCols cols{};
-    uint64_t col_cap = 0, word_cap = 0;       // capacities of the columns (reads) and the stream (words)
+    DevBuf<BdChunk> d_ch;
+    DevBuf<uint32_t> d_base;
+    DevBuf<BdRec> d_rec;
+    DevBuf<BdTot> d_pre;
+    DevBuf<BdCheck> d_chk;
+    DevBuf<uint8_t> d_tmp;                    // hipcub's temporary storage
+    // the columns (one entry per kept read, each grown by its own capacity) and the CIGAR stream:
+    // what BdCols points at (bd_cols)
+    DevBuf<int32_t> d_tid, d_pos, d_endpos;
+    DevBuf<uint32_t> d_nc;
+    DevBuf<uint64_t> d_soff;
+    DevBuf<uint32_t> d_stream;                // handed to the context by svt_bam_dec_load
     uint64_t nkept = 0, nwords = 0;
     svt_bam_dec_stats stats{};
 };
+static_assert(!std::is_copy_constructible<svt_bam_dec>::value, "a decoder owns its device memory");
 
 namespace {
-template <typename T>
-svt_status bd_grow(svt_ctx *c, T *&p, size_t &cap, size_t need, size_t keep = 0) {   // device, keeping `keep` elements
-    if (need <= cap) return SVT_OK;
-    const size_t nc = std::max(need, cap + cap / 2);
-    T *q = nullptr;
-    if (hipMalloc(&q, nc * sizeof(T)) != hipSuccess) return fail(c, SVT_ENOMEM, "%s", "device memory for the BAM decode");
-    if (keep && p) HIP_TRY(c, hipMemcpy(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice));
-    hfree(p);
-    p = q;
-    cap = nc;
-    return SVT_OK;
-}
+// A failed growth of one of the decoder's buffers (allocation or the copy of what it held).
+svt_status bd_mem(svt_ctx *c, hipError_t e) { return nomem(c, e, "device memory for the BAM decode"); }
+
+BdCols bd_cols(const svt_bam_dec *d) { return BdCols{d->d_tid, d->d_pos, d->d_endpos, d->d_nc, d->d_soff, d->d_stream}; }
 }  // namespace
 
 extern "C" {
@@ -71,8 +62,8 @@ svt_status svt_bam_dec_open(svt_ctx *c, int32_t n_targets, svt_bam_dec **out) {
     d->n_ref = n_targets;
     const bool ok = hipStreamCreateWithFlags(&d->st, hipStreamNonBlocking) == hipSuccess &&
                     hipStreamCreateWithFlags(&d->cst, hipStreamNonBlocking) == hipSuccess &&
-                    hipEventCreateWithFlags(&d->cev, hipEventDisableTiming) == hipSuccess &&
-                    hipMalloc(&d->d_chk, sizeof(BdCheck)) == hipSuccess && hipMalloc(&d->d_err, sizeof(uint32_t)) == hipSuccess;
+                    d->cev.create(hipEventDisableTiming) == hipSuccess && d->d_chk.reserve(1) == hipSuccess &&
+                    d->d_err.reserve(1) == hipSuccess;
     if (!ok) {
         svt_bam_dec_close(d);
         return fail(c, SVT_EDEVICE, "%s", "BAM decode: stream / buffers");
@@ -95,7 +86,7 @@ svt_status bd_decode(svt_bam_dec *d) {
     const uint32_t nch = (uint32_t)((span + BD_CHUNK - 1) / BD_CHUNK);
     BdCheck chk{1u, 0u, 0ull, N, 0u, 0u, 0ull};
     if (nch) {
-        if ((s = bd_grow(c, d->d_ch, d->ch_cap, nch)) || (s = bd_grow(c, d->d_base, d->base_cap, nch))) return s;
+        if ((s = bd_mem(c, d->d_ch.grow(nch))) || (s = bd_mem(c, d->d_base.grow(nch)))) return s;
         hipLaunchKernelGGL(bd_chunk_kernel, dim3(nch), dim3(WAVE), 0, d->st, buf, r0, N, nch, d->n_ref, d->d_ch);
         hipLaunchKernelGGL(bd_check_kernel, dim3(1), dim3(WAVE), 0, d->st, buf, d->d_ch, nch, r0, N, d->d_chk);
         HIP_TRY(c, hipGetLastError());
@@ -124,21 +115,21 @@ svt_status bd_decode(svt_bam_dec *d) {
     if (chk.nrec) {
         const uint64_t nrec = chk.nrec;
         if (nrec >= 0xffffffffull) return fail(c, SVT_EINVAL, "%s", "BAM decode: more than 2^32 records in one batch");
-        if ((s = bd_grow(c, d->d_rec, d->rec_cap, nrec)) || (s = bd_grow(c, d->d_pre, d->pre_cap, nrec))) return s;
+        if ((s = bd_mem(c, d->d_rec.grow(nrec))) || (s = bd_mem(c, d->d_pre.grow(nrec)))) return s;
         // the chunks' record counts -> their first record's index; the records; their kept / word prefixes
         const auto cnt = hipcub::TransformInputIterator<uint32_t, BdCntOf, const BdChunk *>(d->d_ch, BdCntOf());
         const auto tot = hipcub::TransformInputIterator<BdTot, BdTotOf, const BdRec *>(d->d_rec, BdTotOf());
         size_t need1 = 0, need2 = 0;
-        HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(nullptr, need1, cnt, d->d_base, (int)chk.nk, d->st));
-        HIP_TRY(c, hipcub::DeviceScan::ExclusiveScan(nullptr, need2, tot, d->d_pre, BdTotSum(), BdTot{0, 0, 0, 0, 0},
+        HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(nullptr, need1, cnt, d->d_base.get(), (int)chk.nk, d->st));
+        HIP_TRY(c, hipcub::DeviceScan::ExclusiveScan(nullptr, need2, tot, d->d_pre.get(), BdTotSum(), BdTot{0, 0, 0, 0, 0},
                                                      (int)nrec, d->st));
-        if ((s = bd_grow(c, reinterpret_cast<uint8_t *&>(d->d_tmp), d->tmp_cap, std::max(need1, need2)))) return s;
-        size_t t1 = d->tmp_cap, t2 = d->tmp_cap;
-        HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(d->d_tmp, t1, cnt, d->d_base, (int)chk.nk, d->st));
+        if ((s = bd_mem(c, d->d_tmp.grow(std::max(need1, need2))))) return s;
+        size_t t1 = d->d_tmp.cap(), t2 = d->d_tmp.cap();
+        HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(d->d_tmp.get(), t1, cnt, d->d_base.get(), (int)chk.nk, d->st));
         hipLaunchKernelGGL(bd_rec_kernel, dim3(chk.nk), dim3(WAVE), 0, d->st, buf, d->d_ch, d->d_base, chk.nk, d->n_ref,
                            d->d_rec);
         HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipcub::DeviceScan::ExclusiveScan(d->d_tmp, t2, tot, d->d_pre, BdTotSum(), BdTot{0, 0, 0, 0, 0},
+        HIP_TRY(c, hipcub::DeviceScan::ExclusiveScan(d->d_tmp.get(), t2, tot, d->d_pre.get(), BdTotSum(), BdTot{0, 0, 0, 0, 0},
                                                      (int)nrec, d->st));
         BdTot last{};
         BdRec lr{};
@@ -149,18 +140,12 @@ svt_status bd_decode(svt_bam_dec *d) {
         if (all.bad) return fail(c, SVT_EINVAL, "%s", "corrupt BAM record");
         // the columns and the stream (STREAM_PAD spare words), grown keeping what they hold
         const uint64_t G = d->nkept + all.keep + 1, W = d->nwords + all.words + STREAM_PAD;
-        if (G > d->col_cap) {   // every column to the same capacity
-            size_t cc;
-            cc = d->col_cap; if ((s = bd_grow(c, d->cols.tid, cc, G, d->nkept))) return s;
-            cc = d->col_cap; if ((s = bd_grow(c, d->cols.pos, cc, G, d->nkept))) return s;
-            cc = d->col_cap; if ((s = bd_grow(c, d->cols.endpos, cc, G, d->nkept))) return s;
-            cc = d->col_cap; if ((s = bd_grow(c, d->cols.nc, cc, G, d->nkept))) return s;
-            cc = d->col_cap; if ((s = bd_grow(c, d->cols.soff, cc, G, d->nkept))) return s;
-            d->col_cap = cc;
-        }
-        if ((s = bd_grow(c, d->cols.stream, d->word_cap, W, d->nwords))) return s;
+        if ((s = bd_mem(c, d->d_tid.grow(G, d->nkept))) || (s = bd_mem(c, d->d_pos.grow(G, d->nkept))) ||
+            (s = bd_mem(c, d->d_endpos.grow(G, d->nkept))) || (s = bd_mem(c, d->d_nc.grow(G, d->nkept))) ||
+            (s = bd_mem(c, d->d_soff.grow(G, d->nkept))) || (s = bd_mem(c, d->d_stream.grow(W, d->nwords))))
+            return s;
         hipLaunchKernelGGL(bd_copy_kernel, dim3((unsigned)std::min<uint64_t>((nrec + 3) / 4, 16384)), dim3(256), 0, d->st,
-                           buf, d->d_rec, d->d_pre, nrec, d->cols, d->nkept, d->nwords);
+                           buf, d->d_rec, d->d_pre, nrec, bd_cols(d), d->nkept, d->nwords);
         HIP_TRY(c, hipGetLastError());
         d->nkept += all.keep;
         d->nwords += all.words;
@@ -172,7 +157,7 @@ svt_status bd_decode(svt_bam_dec *d) {
     // the incomplete last record moves to the front of the other buffer
     const uint64_t nt = N - chk.tail;
     int nx = d->cur ^ 1;
-    if ((s = bd_grow(c, d->d_buf[nx], d->buf_cap[nx], std::max<uint64_t>(nt, 1) + 64))) return s;
+    if ((s = bd_mem(c, d->d_buf[nx].grow(std::max<uint64_t>(nt, 1) + 64)))) return s;
     if (nt) HIP_TRY(c, hipMemcpyAsync(d->d_buf[nx], buf + chk.tail, nt, hipMemcpyDeviceToDevice, d->st));
     HIP_TRY(c, hipStreamSynchronize(d->st));
     d->cur = nx;
@@ -206,8 +191,7 @@ svt_status svt_bam_dec_feed(svt_bam_dec *d, const uint8_t *comp, size_t comp_byt
     // this batch's bytes cross PCIe while the previous batch inflates (its input is the other buffer)
     const int ib = d->ib;
     d->ib ^= 1;
-    if ((s = bd_grow(c, d->d_comp[ib], d->comp_cap[ib], comp_bytes + 64)) ||
-        (s = bd_grow(c, d->d_blk[ib], d->blk_cap[ib], std::max<size_t>(n, 1))))
+    if ((s = bd_mem(c, d->d_comp[ib].grow(comp_bytes + 64))) || (s = bd_mem(c, d->d_blk[ib].grow(std::max<size_t>(n, 1)))))
         return s;
     // Once this batch's copies are queued, every return waits for them first: the header lets the
     // caller reuse `comp` / `blocks` as soon as the call returns, error returns included.
@@ -226,7 +210,7 @@ svt_status svt_bam_dec_feed(svt_bam_dec *d, const uint8_t *comp, size_t comp_byt
     // the previous batch's records: fixes the carried tail this batch's bytes follow
     if (d->pend && (s = bd_decode(d))) return s;
     const uint64_t T = d->tail, N = T + U;
-    if ((s = bd_grow(c, d->d_buf[d->cur], d->buf_cap[d->cur], N + 64, T))) return s;
+    if ((s = bd_mem(c, d->d_buf[d->cur].grow(N + 64, T)))) return s;
     if (n) {
         if ((s = order_on(c, d->st))) return s;
         HIP_TRY(c, hipMemsetAsync(d->d_err, 0xff, sizeof(uint32_t), d->st));
@@ -273,41 +257,38 @@ svt_status svt_bam_dec_load(svt_bam_dec *d) {
     const uint64_t n = d->nkept;
     svt_status s;
     // sortedness and the contig boundaries, on the device
-    int64_t *d_toff = nullptr;
-    uint32_t *d_uns = nullptr;
-    HIP_TRY(c, hipMalloc(&d_toff, ((size_t)nt + 1) * sizeof(int64_t)));
-    if (hipMalloc(&d_uns, sizeof(uint32_t)) != hipSuccess) { hfree(d_toff); return fail(c, SVT_ENOMEM, "%s", "device"); }
+    DevBuf<int64_t> d_toff;
+    DevBuf<uint32_t> d_uns;
+    HIP_TRY(c, d_toff.reserve((size_t)nt + 1));
+    if ((s = nomem(c, d_uns.reserve(1), "device"))) return s;
     std::vector<int64_t> toff((size_t)nt + 1, 0);
     uint32_t uns = 0;
-    hipError_t e = hipMemsetAsync(d_uns, 0, sizeof(uint32_t), d->st);
-    if (e == hipSuccess) e = hipMemsetAsync(d_toff, 0, ((size_t)nt + 1) * sizeof(int64_t), d->st);
-    if (e == hipSuccess) {
-        const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 256) / 256, 65536));
-        hipLaunchKernelGGL(bd_finish_kernel, dim3(g), dim3(256), 0, d->st, d->cols.tid, d->cols.pos, n, nt, d_toff, d_uns);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(toff.data(), d_toff, toff.size() * sizeof(int64_t), hipMemcpyDeviceToHost, d->st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&uns, d_uns, sizeof uns, hipMemcpyDeviceToHost, d->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(d->st);
-    hfree(d_toff);
-    hfree(d_uns);
-    if (e != hipSuccess) return fail(c, SVT_EDEVICE, "BAM decode finish: %s", hipGetErrorString(e));
+    HIP_TRY(c, hipMemsetAsync(d_uns, 0, sizeof(uint32_t), d->st));
+    HIP_TRY(c, hipMemsetAsync(d_toff, 0, ((size_t)nt + 1) * sizeof(int64_t), d->st));
+    const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 256) / 256, 65536));
+    hipLaunchKernelGGL(bd_finish_kernel, dim3(g), dim3(256), 0, d->st, d->d_tid, d->d_pos, n, nt, d_toff, d_uns);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(toff.data(), d_toff, toff.size() * sizeof(int64_t), hipMemcpyDeviceToHost, d->st));
+    HIP_TRY(c, hipMemcpyAsync(&uns, d_uns, sizeof uns, hipMemcpyDeviceToHost, d->st));
+    HIP_TRY(c, hipStreamSynchronize(d->st));
+    d_toff.reset();
+    d_uns.reset();
     // the per-read columns the host pass reads (pos, endpos, n_cigar | clip, stream offsets)
     std::vector<int32_t> pos(n), endpos(n), tid(uns ? n : 0);
     std::vector<uint32_t> nc(n);
     std::vector<uint64_t> soff(n + 1);
     if (n) {
-        HIP_TRY(c, hipMemcpy(pos.data(), d->cols.pos, n * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(endpos.data(), d->cols.endpos, n * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(nc.data(), d->cols.nc, n * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(soff.data(), d->cols.soff, n * 8, hipMemcpyDeviceToHost));
-        if (uns) HIP_TRY(c, hipMemcpy(tid.data(), d->cols.tid, n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(pos.data(), d->d_pos, n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(endpos.data(), d->d_endpos, n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(nc.data(), d->d_nc, n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(soff.data(), d->d_soff, n * 8, hipMemcpyDeviceToHost));
+        if (uns) HIP_TRY(c, hipMemcpy(tid.data(), d->d_tid, n * 4, hipMemcpyDeviceToHost));
     }
     soff[n] = d->nwords;
     const double pre = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
     if (uns) {   // not coordinate-sorted: sort on the host (stable, by tid then pos), as the host ingest does
         std::vector<uint32_t> strm(d->nwords);
-        if (d->nwords) HIP_TRY(c, hipMemcpy(strm.data(), d->cols.stream, d->nwords * 4, hipMemcpyDeviceToHost));
+        if (d->nwords) HIP_TRY(c, hipMemcpy(strm.data(), d->d_stream, d->nwords * 4, hipMemcpyDeviceToHost));
         std::vector<size_t> idx(n);
         for (size_t i = 0; i < n; i++) idx[i] = i;
         std::stable_sort(idx.begin(), idx.end(), [&](size_t x, size_t y) {
@@ -332,14 +313,10 @@ svt_status svt_bam_dec_load(svt_bam_dec *d) {
     } else {
         // the stream stays where the decode wrote it (its spare words zeroed): the context adopts it;
         // a BAM without records never allocated one, so it gets just the spare words here
-        if ((s = bd_grow(c, d->cols.stream, d->word_cap, d->nwords + STREAM_PAD, d->nwords))) return s;
-        HIP_TRY(c, hipMemset(d->cols.stream + d->nwords, 0, STREAM_PAD * 4));
-        s = load_core(c, nt, toff.data(), pos.data(), endpos.data(), nc.data(), soff.data(), nullptr, d->cols.stream,
+        if ((s = bd_mem(c, d->d_stream.grow(d->nwords + STREAM_PAD, d->nwords)))) return s;
+        HIP_TRY(c, hipMemset(d->d_stream + d->nwords, 0, STREAM_PAD * 4));
+        s = load_core(c, nt, toff.data(), pos.data(), endpos.data(), nc.data(), soff.data(), nullptr, &d->d_stream,
                       d->stats.cigar_ops, pre);
-        if (c->d_cigar == d->cols.stream) {
-            d->cols.stream = nullptr;
-            d->word_cap = 0;
-        }
     }
     c->load_stats.total_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
     return s;
@@ -354,16 +331,10 @@ void svt_bam_dec_close(svt_bam_dec *d) {
         // its work is done, so nothing later has to wait for it, and it must not be named again
         if (d->c->have_last && d->c->last_stream == d->st) d->c->have_last = false;
         if (d->cst) (void)hipStreamSynchronize(d->cst);
-        hfree(d->d_comp[0]); hfree(d->d_comp[1]); hfree(d->d_blk[0]); hfree(d->d_blk[1]); hfree(d->d_err);
-        hfree(d->d_buf[0]); hfree(d->d_buf[1]);
-        hfree(d->d_ch); hfree(d->d_base); hfree(d->d_rec); hfree(d->d_pre); hfree(d->d_chk); hfree(d->d_tmp);
-        hfree(d->cols.tid); hfree(d->cols.pos); hfree(d->cols.endpos); hfree(d->cols.nc); hfree(d->cols.soff);
-        hfree(d->cols.stream);
-        if (d->cev) (void)hipEventDestroy(d->cev);
         if (d->st) (void)hipStreamDestroy(d->st);
         if (d->cst) (void)hipStreamDestroy(d->cst);
+        delete d;   // its buffers and its event go with it, on the context's device
     }
-    delete d;
 }
 
 }  // extern "C"

@@ -328,19 +328,3 @@ __global__ __launch_bounds__(256) void call_merge_kernel(const svt_call *in, uin
     dst[1] = src[1];
     dst[2] = src[2];
 }
-
-// A context's scan state: the segments (once per loaded pileup), the scratch, the last scan's calls.
-struct CallScratch {
-    bool ready = false;
-    uint64_t n_seg = 0;
-    uint64_t *d_seg = nullptr;
-    unsigned long long *d_keys = nullptr, *d_tmax = nullptr, *d_tprev = nullptr;
-    uint32_t *d_cid = nullptr, *d_pick = nullptr;
-    uint32_t *d_ctr = nullptr;        // [0] picked calls, [1] the DEL calls among them, [2..8) events / skipped / big buckets (64 bits each)
-    CallAcc *d_acc = nullptr;
-    uint8_t *d_tmp = nullptr;         // hipcub's temporary storage
-    uint8_t *d_flag = nullptr;        // per cluster: a call
-    svt_call *d_calls = nullptr, *d_raw = nullptr;   // in (chrom, pos, type) order / as emitted
-    uint64_t acc_cap = 0, pick_cap = 0, flag_cap = 0, tmp_cap = 0, calls_cap = 0, raw_cap = 0, n_calls = 0;
-    svt_call_stats stats{};
-};

@@ -4,25 +4,7 @@
 extern "C++" {
 namespace {
 
-// p grown to n elements when cap (its present size) is smaller; call_alloc: a buffer without one.
-template <typename T>
-svt_status call_grow(svt_ctx *c, T *&p, uint64_t &cap, uint64_t n) {
-    if (n <= cap) return SVT_OK;
-    hfree(p);
-    cap = 0;
-    if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) {
-        p = nullptr;
-        return fail(c, SVT_ENOMEM, "%s", "svt_call_scan: device scratch");
-    }
-    cap = n;
-    return SVT_OK;
-}
-
-template <typename T>
-svt_status call_alloc(svt_ctx *c, T *&p, uint64_t n) {
-    uint64_t cap = 0;
-    return call_grow(c, p, cap, n);
-}
+constexpr const char *CALL_MEM = "svt_call_scan: device scratch";
 
 // The first scan of a loaded pileup: the segments (the buckets' extents are those of the load for
 // every rebuild) and the scratch that depends on the event counts alone.
@@ -31,32 +13,29 @@ svt_status call_prepare(svt_ctx *c) {
     if (k.ready) return SVT_OK;
     const uint64_t nb2 = 2 * c->bk_n, N = c->bk_events[BA_S] + c->bk_events[BA_I];
     svt_status s;
-    uint8_t *d_flag = nullptr;
-    if ((s = call_alloc(c, d_flag, nb2))) return s;
-    if ((s = call_alloc(c, k.d_seg, nb2)) || (s = call_alloc(c, k.d_ctr, 8))) {
-        hfree(d_flag);
+    DevBuf<uint8_t> d_flag;
+    if ((s = nomem(c, d_flag.reserve(nb2), CALL_MEM)) || (s = nomem(c, k.d_seg.reserve(nb2), CALL_MEM)) ||
+        (s = nomem(c, k.d_ctr.reserve(8), CALL_MEM)))
         return s;
-    }
     BkIndex B = make_args(c, nullptr, nullptr, 0, false).bk;
     hipLaunchKernelGGL(call_flag_kernel, dim3((unsigned)((nb2 + 255) / 256)), dim3(256), 0, nullptr, B, c->n_targets, d_flag);
     size_t tb = 0;
     hipcub::CountingInputIterator<uint64_t> it(0);
-    uint64_t *d_n = reinterpret_cast<uint64_t *>(k.d_ctr);
-    hipError_t e = hipcub::DeviceSelect::Flagged(nullptr, tb, it, d_flag, k.d_seg, d_n, (int)nb2, nullptr);
-    if (e == hipSuccess && (s = call_grow(c, k.d_tmp, k.tmp_cap, tb)) == SVT_OK) {
-        e = hipcub::DeviceSelect::Flagged(k.d_tmp, tb, it, d_flag, k.d_seg, d_n, (int)nb2, nullptr);
-        if (e == hipSuccess) e = hipMemcpy(&k.n_seg, d_n, 8, hipMemcpyDeviceToHost);
-    }
-    hfree(d_flag);
-    if (s) return s;
-    HIP_TRY(c, e);
-    if ((s = call_alloc(c, k.d_keys, std::max<uint64_t>(N, 1))) || (s = call_alloc(c, k.d_cid, std::max<uint64_t>(N, 1))) ||
-        (s = call_alloc(c, k.d_tmax, k.n_seg)) || (s = call_alloc(c, k.d_tprev, k.n_seg)))
+    uint64_t *d_n = reinterpret_cast<uint64_t *>(k.d_ctr.get());
+    HIP_TRY(c, hipcub::DeviceSelect::Flagged(nullptr, tb, it, d_flag.get(), k.d_seg.get(), d_n, (int)nb2, nullptr));
+    if ((s = nomem(c, k.d_tmp.reserve(tb), CALL_MEM))) return s;
+    HIP_TRY(c, hipcub::DeviceSelect::Flagged(k.d_tmp.get(), tb, it, d_flag.get(), k.d_seg.get(), d_n, (int)nb2, nullptr));
+    HIP_TRY(c, hipMemcpy(&k.n_seg, d_n, 8, hipMemcpyDeviceToHost));
+    d_flag.reset();
+    if ((s = nomem(c, k.d_keys.reserve(std::max<uint64_t>(N, 1)), CALL_MEM)) ||
+        (s = nomem(c, k.d_cid.reserve(std::max<uint64_t>(N, 1)), CALL_MEM)) ||
+        (s = nomem(c, k.d_tmax.reserve(k.n_seg), CALL_MEM)) || (s = nomem(c, k.d_tprev.reserve(k.n_seg), CALL_MEM)))
         return s;
     size_t t1 = 0, t2 = 0;
-    HIP_TRY(c, hipcub::DeviceScan::ExclusiveScan(nullptr, t1, k.d_tmax, k.d_tprev, hipcub::Max(), 0ull, (int)k.n_seg, nullptr));
-    HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(nullptr, t2, k.d_cid, k.d_cid, (int)std::max<uint64_t>(N, 1), nullptr));
-    if ((s = call_grow(c, k.d_tmp, k.tmp_cap, std::max(t1, t2)))) return s;
+    HIP_TRY(c, hipcub::DeviceScan::ExclusiveScan(nullptr, t1, k.d_tmax.get(), k.d_tprev.get(), hipcub::Max(), 0ull,
+                                                 (int)k.n_seg, nullptr));
+    HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(nullptr, t2, k.d_cid.get(), k.d_cid.get(), (int)std::max<uint64_t>(N, 1), nullptr));
+    if ((s = nomem(c, k.d_tmp.reserve(std::max(t1, t2)), CALL_MEM))) return s;
     k.ready = true;
     return SVT_OK;
 }
@@ -72,16 +51,9 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
     }
     svt_status s = order_on(c, nullptr);   // after every launch already issued (svt_reindex rebuilds the buckets)
     if (s) return s;
-    struct Ev {   // (destroys what was created, whichever step fails)
-        hipEvent_t a = nullptr, b = nullptr;
-        ~Ev() {
-            if (a) (void)hipEventDestroy(a);
-            if (b) (void)hipEventDestroy(b);
-        }
-    } evg;
-    hipEvent_t &e0 = evg.a, &e1 = evg.b;
-    HIP_TRY(c, hipEventCreate(&e0));
-    HIP_TRY(c, hipEventCreate(&e1));
+    DevEvent e0, e1;
+    HIP_TRY(c, e0.create());
+    HIP_TRY(c, e1.create());
     HIP_TRY(c, hipEventRecord(e0, nullptr));
     if ((s = call_prepare(c))) return s;
     const KArgs ka = make_args(c, nullptr, nullptr, 0, false);
@@ -104,11 +76,12 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
     const dim3 sg((unsigned)k.n_seg), sb(CALL_T);
     HIP_TRY(c, hipMemsetAsync(k.d_ctr, 0, 8 * sizeof(uint32_t), nullptr));
     hipLaunchKernelGGL(call_sort_kernel, sg, sb, 0, nullptr, a);
-    size_t tb = k.tmp_cap;
-    HIP_TRY(c, hipcub::DeviceScan::ExclusiveScan(k.d_tmp, tb, k.d_tmax, k.d_tprev, hipcub::Max(), 0ull, (int)k.n_seg, nullptr));
+    size_t tb = k.d_tmp.cap();
+    HIP_TRY(c, hipcub::DeviceScan::ExclusiveScan(k.d_tmp.get(), tb, k.d_tmax.get(), k.d_tprev.get(), hipcub::Max(), 0ull,
+                                                 (int)k.n_seg, nullptr));
     hipLaunchKernelGGL(call_head_kernel, sg, sb, 0, nullptr, a);
-    tb = k.tmp_cap;
-    HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(k.d_tmp, tb, k.d_cid, k.d_cid, (int)N, nullptr));
+    tb = k.d_tmp.cap();
+    HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(k.d_tmp.get(), tb, k.d_cid.get(), k.d_cid.get(), (int)N, nullptr));
     HIP_TRY(c, hipGetLastError());
     uint32_t ncl = 0, ncl_s = 0;   // clusters; those of array S (the DEL clusters come first)
     HIP_TRY(c, hipMemcpy(&ncl, k.d_cid + (N - 1), 4, hipMemcpyDeviceToHost));
@@ -117,9 +90,9 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
     if (ncl) {
         size_t need = 0;
         hipcub::CountingInputIterator<uint32_t> it(0);
-        HIP_TRY(c, hipcub::DeviceSelect::Flagged(nullptr, need, it, k.d_flag, k.d_pick, k.d_ctr, (int)ncl, nullptr));
-        if ((s = call_grow(c, k.d_acc, k.acc_cap, ncl)) || (s = call_grow(c, k.d_pick, k.pick_cap, ncl)) ||
-            (s = call_grow(c, k.d_flag, k.flag_cap, ncl)) || (s = call_grow(c, k.d_tmp, k.tmp_cap, need)))
+        HIP_TRY(c, hipcub::DeviceSelect::Flagged(nullptr, need, it, k.d_flag.get(), k.d_pick.get(), k.d_ctr.get(), (int)ncl, nullptr));
+        if ((s = nomem(c, k.d_acc.reserve(ncl), CALL_MEM)) || (s = nomem(c, k.d_pick.reserve(ncl), CALL_MEM)) ||
+            (s = nomem(c, k.d_flag.reserve(ncl), CALL_MEM)) || (s = nomem(c, k.d_tmp.reserve(need), CALL_MEM)))
             return s;
         a.acc = k.d_acc;
         a.pick = k.d_pick;
@@ -127,14 +100,14 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
         hipLaunchKernelGGL(call_accum_kernel, sg, sb, 0, nullptr, a);
         hipLaunchKernelGGL(call_pick_kernel, dim3((ncl + 255u) / 256u), dim3(256), 0, nullptr, a, ncl, ncl_s, k.d_flag,
                            k.d_ctr + 1);
-        tb = k.tmp_cap;
-        HIP_TRY(c, hipcub::DeviceSelect::Flagged(k.d_tmp, tb, it, k.d_flag, k.d_pick, k.d_ctr, (int)ncl, nullptr));
+        tb = k.d_tmp.cap();
+        HIP_TRY(c, hipcub::DeviceSelect::Flagged(k.d_tmp.get(), tb, it, k.d_flag.get(), k.d_pick.get(), k.d_ctr.get(), (int)ncl, nullptr));
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpy(picked, k.d_ctr, sizeof picked, hipMemcpyDeviceToHost));
     }
     const uint32_t npick = picked[0], ndel = std::min(picked[1], picked[0]);
     if (npick) {
-        if ((s = call_grow(c, k.d_calls, k.calls_cap, npick)) || (s = call_grow(c, k.d_raw, k.raw_cap, npick))) return s;
+        if ((s = nomem(c, k.d_calls.reserve(npick), CALL_MEM)) || (s = nomem(c, k.d_raw.reserve(npick), CALL_MEM))) return s;
         hipLaunchKernelGGL(call_emit_kernel, dim3((npick + WPB - 1) / WPB), dim3(64 * WPB), 0, nullptr, a, npick, k.d_raw);
         hipLaunchKernelGGL(call_merge_kernel, dim3((npick + 255u) / 256u), dim3(256), 0, nullptr, k.d_raw, npick, ndel,
                            k.d_calls);
@@ -196,7 +169,7 @@ svt_status svt_call_fetch(svt_ctx *c, uint64_t first, uint64_t n, svt_call *out)
 svt_status svt_call_device(svt_ctx *c, const svt_call **d_calls, uint64_t *n) {
     if (!c) return SVT_EINVAL;
     if (!d_calls || !n) return fail(c, SVT_EINVAL, "%s", "null d_calls/n");
-    *d_calls = c->call.n_calls ? c->call.d_calls : nullptr;
+    *d_calls = c->call.n_calls ? c->call.d_calls.get() : nullptr;
     *n = c->call.n_calls;
     return SVT_OK;
 }

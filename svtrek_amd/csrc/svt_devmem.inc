@@ -1,0 +1,92 @@
+// svt_devmem.inc -- host only: the owners of what the engine's host code allocates on the device
+// (included by svt_engine.hip after the device code and before svt_ctx), and the host-side records
+// of the side modes' scratch.  Nothing here is a kernel argument: KArgs, IxArgs, BkBuild, CallArgs,
+// PoaArgs and BdCols keep raw pointers, filled from these owners at launch.
+
+// One hipMalloc allocation and its capacity in elements.  Move-only; freed by reset() and the
+// destructor, on whatever device is current then (every entry point runs under its DevGuard).
+// Allocation returns the hipError_t; the caller turns it into its own status and message.
+template <typename T>
+class DevBuf {
+    T *p_ = nullptr;
+    size_t cap_ = 0;
+
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr, o.cap_ = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) {
+            reset();
+            p_ = o.p_, cap_ = o.cap_;
+            o.p_ = nullptr, o.cap_ = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    void reset() {
+        if (p_) (void)hipFree((void *)p_);
+        p_ = nullptr, cap_ = 0;
+    }
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
+    size_t cap() const { return cap_; }
+    // At least n elements, contents not kept: nothing when n <= cap(), else the old block is freed
+    // first and exactly n allocated (the buffer is empty when that fails).
+    hipError_t reserve(size_t n) {
+        if (n <= cap_) return hipSuccess;
+        reset();
+        const hipError_t e = hipMalloc((void **)&p_, n * sizeof(T));
+        if (e != hipSuccess) p_ = nullptr;
+        else cap_ = n;
+        return e;
+    }
+    // At least `need` elements, the first `keep` kept (the BAM decoder's buffers): a new block of
+    // max(need, 1.5 x cap()) and a device copy.  The buffer is unchanged when either fails.
+    hipError_t grow(size_t need, size_t keep = 0) {
+        if (need <= cap_) return hipSuccess;
+        DevBuf q;
+        hipError_t e = q.reserve(std::max(need, cap_ + cap_ / 2));
+        if (e == hipSuccess && keep && p_) e = hipMemcpy(q.p_, p_, keep * sizeof(T), hipMemcpyDeviceToDevice);
+        if (e == hipSuccess) *this = std::move(q);
+        return e;
+    }
+};
+
+// One HIP event, created on demand.
+struct DevEvent {
+    hipEvent_t e = nullptr;
+    DevEvent() = default;
+    DevEvent(const DevEvent &) = delete;
+    DevEvent &operator=(const DevEvent &) = delete;
+    ~DevEvent() {
+        if (e) (void)hipEventDestroy(e);
+    }
+    hipError_t create(unsigned flags = hipEventDefault) { return hipEventCreateWithFlags(&e, flags); }
+    operator hipEvent_t() const { return e; }
+};
+
+// svt_call_scan's scratch (svt_call.inc, svt_call_host.inc): nothing allocated before the first scan
+// of a loaded pileup, gone with the pileup.
+struct CallScratch {
+    bool ready = false;
+    uint64_t n_seg = 0;
+    DevBuf<uint64_t> d_seg;
+    DevBuf<unsigned long long> d_keys, d_tmax, d_tprev;
+    DevBuf<uint32_t> d_cid, d_pick;
+    DevBuf<uint32_t> d_ctr;        // [0] picked calls, [1] the DEL calls among them, [2..8) events / skipped / big buckets (64 bits each)
+    DevBuf<CallAcc> d_acc;
+    DevBuf<uint8_t> d_tmp;         // hipcub's temporary storage
+    DevBuf<uint8_t> d_flag;        // per cluster: a call
+    DevBuf<svt_call> d_calls, d_raw;   // in (chrom, pos, type) order / as emitted
+    uint64_t n_calls = 0;
+    svt_call_stats stats{};
+};
+
+// One pool of POA scratch slots (svt_poa.inc, svt_poa_host.inc).
+struct PoaPool {
+    DevBuf<uint8_t> d;
+    uint64_t slot_bytes = 0;
+    uint32_t nslots = 0;
+};

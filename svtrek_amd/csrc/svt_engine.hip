@@ -31,6 +31,8 @@
 //   svt_index.inc, svt_index2.inc, svt_bucket_build.inc   the index builds (span lists, value buckets)
 //   svt_poa.inc, svt_poa_host.inc      allele consensus (POA): kernels, slot pools and poa_run
 //   svt_bam.inc, svt_inflate.inc, svt_bam_host.inc   BGZF inflate and BAM decode: kernels, svt_bam_dec_*
+//   svt_devmem.inc        host only: DevBuf / DevEvent, the owners of every device allocation and event
+//                         the host code makes, and the side modes' scratch records (CallScratch, PoaPool)
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -45,6 +47,7 @@
 #include <atomic>
 #include <type_traits>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/svtrek_gpu.h"
@@ -173,10 +176,66 @@ constexpr int LV_WMAX = 1023;   // band half-width for 16-bit offsets and prefix
 #include "svt_bam.inc"
 #include "svt_inflate.inc"
 
+#include "svt_devmem.inc"
+
+// Everything that lives exactly as long as a loaded pileup: free_pileup is one assignment of a
+// default-constructed Pileup.
+struct Pileup {
+    int32_t n_targets = 0;
+    int64_t n_reads = 0;
+    uint64_t n_ops = 0;
+    DevBuf<int32_t> d_pos, d_emax;
+    DevBuf<uint4> d_rec;
+    DevBuf<uint8_t> d_clip8;          // per read its clip bits (rec.z >> 30) alone: the census's 1 B instead of 16
+    DevBuf<uint64_t> d_off64;         // stream offsets [n_reads + 1]
+    DevBuf<int64_t> d_tid_off, d_bkt_off;
+    DevBuf<uint2> d_bkt;
+    DevBuf<uint32_t> d_cigar;         // CIGAR stream
+    uint64_t n_ins = 0;               // I >= 50 ops in the pileup (= I-list events; d_spoffI indexes them per read)
+    // device index (svt_index.inc)
+    DevBuf<uint64_t> d_part;          // [n_ranges + 1]
+    uint32_t n_ranges = 0;
+    DevBuf<IxTot> d_agg;              // range (group) totals
+    DevBuf<IxTot> d_bsum, d_bpre;     // their sums per block of IX_BLK, the blocks' exclusive scan
+    size_t n_bsum = 0;
+    bool bsum_dirty = false;          // a build stopped between its walk (which adds into d_bsum) and the
+                                      // scan (which zeroes it again): the next build clears it first
+    DevBuf<uint4> d_scr;              // stream walk: staged events / offsets per range, overflow flags
+    DevBuf<uint2> d_scrh;
+    DevBuf<uint32_t> d_ovf;
+    DevBuf<uint2> d_cnt;              // [n_reads] lane-per-read census -> emit (svt_index2.inc)
+    uint32_t n_groups = 0;            // 64-read groups of the lane-per-read index
+    DevBuf<uint64_t> d_tot;
+    uint64_t n_evD = 0, n_evI = 0;
+    DevBuf<uint64_t> d_spoffD, d_spoffI;   // span walk
+    DevBuf<uint4> d_spD, d_spI;
+    // allele-consensus mode: the inserted sequences (svt_load_insseq)
+    DevBuf<uint64_t> d_ins_off;
+    DevBuf<uint8_t> d_ins_bases;
+    bool insseq_loaded = false;
+    // the value-bucketed event index (svt_bucket.inc, svt_bucket_build.inc)
+    bool bk_ready = false;            // built for the loaded pileup
+    uint64_t bk_n = 0;                // buckets per array (every contig's)
+    DevBuf<uint32_t> d_bkoff;         // [BA_N][bk_n + 1] extents (indices into d_bkev)
+    DevBuf<uint32_t> d_bkcur;         // [BA_N][bk_n + 1] cursors of direct builds (k * count before build k)
+    DevBuf<uint32_t> d_bkcap;         // [BA_N][bk_n + 1] cursors of captured builds (zeroed by the graph)
+    DevBuf<int32_t> d_bkpm;           // [3][bk_n + 1] prefix max of the BELOW keys
+    DevBuf<uint4> d_bkev;             // every array's events
+    uint64_t bk_events[BA_N] = {};
+    DevBuf<uint64_t> d_bkbase;        // [n_targets] first bucket of contig t
+    DevBuf<uint32_t> d_bknb;          // [n_targets] its buckets
+    DevBuf<uint32_t> d_bkmaxd;        // [n_targets] its longest D > 50 op
+    uint32_t bk_builds = 0;           // filing passes so far (the cursors' epoch)
+    uint32_t bk_nev = 0;              // d_bkev's events (every array's)
+    CallScratch call;                 // svt_call_scan
+    uint64_t dev_bytes = 0;
+    bool loaded = false;
+};
+
 }  // namespace
 
 // ====================================================================== C ABI
-struct svt_ctx {
+struct svt_ctx : Pileup {
     svt_params prm{};
     int device = 0;
     bool lane_vote = true;        // refine_lane_kernel from 64K windows up; SVTREK_GATHER=span1: refine_span_kernel always
@@ -184,91 +243,39 @@ struct svt_ctx {
                                   // at most IX_TMAX ops (and IX_RCAP reads) a range
     int lane_w = 0;               // SVTREK_LANE_W=32 forces the lane kernel at every batch size (tests)
     int lane_wide = -1;           // SVTREK_LANE_WIDE=0 / 1: 32 / 64 windows a wave at every size (-1: by window count)
-    uint32_t *d_redo = nullptr;   // lane-vote launches: left-over window list
-    size_t redo_cap = 0;
+    int ix_mode = 0;              // index build: 0 by read length, 1 lane per read (svt_index2.inc), 2 stream
+                                  // walk (svt_index.inc) -- SVTREK_IX=auto|lane|stream
+    bool bk_on = true;            // SVTREK_INDEX=lists: off (the span lists alone, rounds 1-5)
+    DevBuf<uint32_t> d_redo;      // lane-vote launches: left-over window list (grown, never shrunk)
     uint32_t lane_par = 0;        // which of the two redo counters the next lane launch uses
     char err[512] = {0};
-    // pileup
-    int32_t n_targets = 0;
-    int64_t n_reads = 0;
-    uint64_t n_ops = 0;
-    int32_t *d_pos = nullptr, *d_emax = nullptr;
-    uint4 *d_rec = nullptr;
-    uint8_t *d_clip8 = nullptr;       // per read its clip bits (rec.z >> 30) alone: the census's 1 B instead of 16
-    uint64_t *d_off64 = nullptr;      // stream offsets [n_reads + 1]
-    int64_t *d_tid_off = nullptr, *d_bkt_off = nullptr;
-    uint2 *d_bkt = nullptr;
-    uint32_t *d_cigar = nullptr;      // CIGAR stream
-    uint64_t n_ins = 0;               // I >= 50 ops in the pileup (= I-list events; d_spoffI indexes them per read)
-    // device index (svt_index.inc)
-    uint64_t *d_part = nullptr;       // [n_ranges + 1]
-    uint32_t n_ranges = 0;
-    IxTot *d_agg = nullptr;           // range (group) totals
-    IxTot *d_bsum = nullptr, *d_bpre = nullptr;   // their sums per block of IX_BLK, the blocks' exclusive scan
-    size_t n_bsum = 0;
-    bool bsum_dirty = false;          // a build stopped between its walk (which adds into d_bsum) and the
-                                      // scan (which zeroes it again): the next build clears it first
-    uint4 *d_scr = nullptr;                        // stream walk: staged events / offsets per range, overflow flags
-    uint2 *d_scrh = nullptr;
-    uint32_t *d_ovf = nullptr;
-    uint2 *d_cnt = nullptr;           // [n_reads] lane-per-read census -> emit (svt_index2.inc)
-    uint32_t n_groups = 0;            // 64-read groups of the lane-per-read index
-    int ix_mode = 0;                  // index build: 0 by read length, 1 lane per read (svt_index2.inc), 2 stream
-                                      // walk (svt_index.inc) -- SVTREK_IX=auto|lane|stream
-    uint64_t *d_tot = nullptr;
-    uint64_t n_evD = 0, n_evI = 0;
-    // allele-consensus mode (svt_load_insseq / svt_poa_consensus)
-    uint64_t *d_ins_off = nullptr;
-    uint8_t *d_ins_bases = nullptr;
-    bool insseq_loaded = false;
-    PoaPool poa_small, poa_big;       // POA scratch slots (poa_pool)
-    uint64_t poa_deferred = 0;        // loci the last svt_poa_consensus reran on full-size slots
-    uint64_t *d_spoffD = nullptr, *d_spoffI = nullptr;   // span walk
-    uint4 *d_spD = nullptr, *d_spI = nullptr;
-    // the value-bucketed event index (svt_bucket.inc, svt_bucket_build.inc)
-    bool bk_on = true;                // SVTREK_INDEX=lists: off (the span lists alone, rounds 1-5)
-    bool bk_ready = false;            // built for the loaded pileup
-    uint64_t bk_n = 0;                // buckets per array (every contig's)
-    uint32_t *d_bkoff = nullptr;      // [BA_N][bk_n + 1] extents (indices into d_bkev)
-    uint32_t *d_bkcur = nullptr;      // [BA_N][bk_n + 1] cursors of direct builds (k * count before build k)
-    uint32_t *d_bkcap = nullptr;      // [BA_N][bk_n + 1] cursors of captured builds (zeroed by the graph)
-    int32_t *d_bkpm = nullptr;        // [3][bk_n + 1] prefix max of the BELOW keys
-    uint4 *d_bkev = nullptr;          // every array's events
-    uint64_t bk_events[BA_N] = {};
-    uint64_t *d_bkbase = nullptr;     // [n_targets] first bucket of contig t
-    uint32_t *d_bknb = nullptr;       // [n_targets] its buckets
-    uint32_t *d_bkmaxd = nullptr;     // [n_targets] its longest D > 50 op
-    uint32_t bk_builds = 0;           // filing passes so far (the cursors' epoch)
-    uint32_t bk_nev = 0;              // d_bkev's events (every array's)
-    uint64_t dev_bytes = 0;
-    bool loaded = false;
-    svt_load_stats load_stats{};      // timings of the last svt_load_pileup
+    svt_load_stats load_stats{};  // timings of the last svt_load_pileup
+    // allele-consensus mode (svt_poa_consensus)
+    PoaPool poa_small, poa_big;   // POA scratch slots (poa_pool)
+    uint64_t poa_deferred = 0;    // loci the last svt_poa_consensus reran on full-size slots
     // batch scratch
-    svt_locus *d_loci = nullptr;
-    svt_result *d_out = nullptr;
-    size_t batch_cap = 0;
-    svt_evidence *d_evid = nullptr;   // svt_evidence_batch's records [2 * evid_cap]
-    size_t evid_cap = 0;
-    CallScratch call;                 // svt_call_scan (svt_call.inc): nothing allocated before the first scan
-    // spill pool + status + work counters
-    int32_t *d_pool = nullptr;
-    unsigned long long pool_words = 0;
-    unsigned char *d_ctl = nullptr;   // [0,8) pool head (epoch-tagged), [8,12) sticky status, [12,16) index
-                                      // build guard, [16,16+8*W_N) work, [CTL_REDO, +16) left-over counters
-    uint32_t epoch = 0;               // launches so far (pool epochs cycle through 1 .. 2^24-1)
+    DevBuf<svt_locus> d_loci;
+    DevBuf<svt_result> d_out;
+    DevBuf<svt_evidence> d_evid;  // svt_evidence_batch's records [2 * n]
+    // spill pool (d_pool.cap() words) + status + work counters
+    DevBuf<int32_t> d_pool;
+    DevBuf<unsigned char> d_ctl;  // [0,8) pool head (epoch-tagged), [8,12) sticky status, [12,16) index
+                                  // build guard, [16,16+8*W_N) work, [CTL_REDO, +16) left-over counters
+    uint32_t epoch = 0;           // launches so far (pool epochs cycle through 1 .. 2^24-1)
     // launches run in submission order across streams (order_on)
     hipStream_t last_stream = nullptr;
     bool have_last = false;
-    hipEvent_t order_ev = nullptr;
+    DevEvent order_ev;
     // svt_open_multi: the contexts of devices[1..] (this one drives devices[0])
     std::vector<svt_ctx *> subs;
     // BGZF inflate (svt_bgzf_inflate): device buffers grown on demand, never shrunk
-    uint8_t *d_infc = nullptr, *d_info = nullptr;
-    svt_bgzf_block *d_infb = nullptr;
-    uint32_t *d_inferr = nullptr;
-    size_t infc_cap = 0, info_cap = 0, infb_cap = 0;
-    double inf_ms = 0;                // device time of the last svt_bgzf_inflate's kernel
+    DevBuf<uint8_t> d_infc, d_info;
+    DevBuf<svt_bgzf_block> d_infb;
+    DevBuf<uint32_t> d_inferr;
+    double inf_ms = 0;            // device time of the last svt_bgzf_inflate's kernel
 };
+static_assert(!std::is_copy_constructible<svt_ctx>::value && !std::is_copy_assignable<svt_ctx>::value,
+              "a context owns its device memory");
 
 namespace {
 
@@ -283,10 +290,9 @@ svt_status fail(svt_ctx *c, svt_status code, const char *fmt, const char *detail
         if (e_ != hipSuccess) return fail((ctx), SVT_EDEVICE, #expr ": %s", hipGetErrorString(e_)); \
     } while (0)
 
-template <typename T>
-void hfree(T *&p) {
-    if (p) (void)hipFree((void *)p);
-    p = nullptr;
+// A failed device allocation as the site's status: SVT_ENOMEM with its message.
+svt_status nomem(svt_ctx *c, hipError_t e, const char *what) {
+    return e == hipSuccess ? SVT_OK : fail(c, SVT_ENOMEM, "%s", what);
 }
 
 // Every entry point runs on its context's device and gives the calling thread its current
@@ -311,7 +317,7 @@ struct DevGuard {
 // first waits for everything issued so far on that one.
 svt_status order_on(svt_ctx *c, hipStream_t st) {
     if (c->have_last && st != c->last_stream) {
-        if (!c->order_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->order_ev, hipEventDisableTiming));
+        if (!c->order_ev) HIP_TRY(c, c->order_ev.create(hipEventDisableTiming));
         HIP_TRY(c, hipEventRecord(c->order_ev, c->last_stream));
         HIP_TRY(c, hipStreamWaitEvent(st, c->order_ev, 0));
     }
@@ -328,40 +334,11 @@ svt_status grow_pool(svt_ctx *c) {
     HIP_TRY(c, hipDeviceSynchronize());
     HIP_TRY(c, hipMemcpy(&head, c->d_ctl, 8, hipMemcpyDeviceToHost));
     const uint64_t need = (uint32_t)(head >> 40) == c->epoch ? (head & ((1ull << 40) - 1ull)) : 0ull;
-    const uint64_t words = std::max<uint64_t>(need + need / 8 + 1024, 2 * c->pool_words);
-    hfree(c->d_pool);
-    c->pool_words = 0;
-    if (hipMalloc(&c->d_pool, words * 4) != hipSuccess) {
-        c->d_pool = nullptr;
-        return fail(c, SVT_ENOMEM, "%s", "growing the candidate spill pool failed");
-    }
-    c->pool_words = words;
-    return SVT_OK;
+    const uint64_t words = std::max<uint64_t>(need + need / 8 + 1024, 2 * c->d_pool.cap());
+    return nomem(c, c->d_pool.reserve(words), "growing the candidate spill pool failed");
 }
 
-void free_call(svt_ctx *c) {
-    CallScratch &k = c->call;
-    hfree(k.d_seg); hfree(k.d_keys); hfree(k.d_cid); hfree(k.d_tmax); hfree(k.d_tprev); hfree(k.d_acc);
-    hfree(k.d_pick); hfree(k.d_ctr); hfree(k.d_tmp); hfree(k.d_calls); hfree(k.d_raw); hfree(k.d_flag);
-    k = CallScratch{};
-}
-
-void free_pileup(svt_ctx *c) {
-    free_call(c);
-    hfree(c->d_pos); hfree(c->d_emax); hfree(c->d_rec); hfree(c->d_clip8); hfree(c->d_off64);
-    hfree(c->d_tid_off); hfree(c->d_bkt_off); hfree(c->d_bkt); hfree(c->d_cigar);
-    hfree(c->d_ins_off); hfree(c->d_ins_bases);
-    hfree(c->d_part); hfree(c->d_cnt); hfree(c->d_agg); hfree(c->d_bsum); hfree(c->d_bpre); hfree(c->d_tot);
-    hfree(c->d_scr); hfree(c->d_scrh); hfree(c->d_ovf);
-    hfree(c->d_spoffD); hfree(c->d_spoffI); hfree(c->d_spD); hfree(c->d_spI);
-    hfree(c->d_bkoff); hfree(c->d_bkcur); hfree(c->d_bkcap); hfree(c->d_bkev); hfree(c->d_bkpm);
-    for (int A = 0; A < BA_N; A++) c->bk_events[A] = 0;
-    hfree(c->d_bkbase); hfree(c->d_bknb); hfree(c->d_bkmaxd);
-    c->bk_ready = false; c->bk_n = 0; c->bk_builds = 0; c->bk_nev = 0;
-    c->insseq_loaded = false; c->n_ins = 0; c->n_ranges = 0;
-    c->n_evD = c->n_evI = 0;
-    c->loaded = false; c->dev_bytes = 0; c->n_reads = 0; c->n_ops = 0; c->n_targets = 0;
-}
+void free_pileup(svt_ctx *c) { static_cast<Pileup &>(*c) = Pileup{}; }
 
 KArgs make_args(svt_ctx *c, const svt_locus *d_loci, svt_result *d_out, uint32_t n, bool count) {
     KArgs a;
@@ -377,8 +354,8 @@ KArgs make_args(svt_ctx *c, const svt_locus *d_loci, svt_result *d_out, uint32_t
     a.out = d_out;
     a.n = n;
     a.pool = c->d_pool;
-    a.pool_head = (unsigned long long *)c->d_ctl;
-    a.pool_words = c->pool_words;
+    a.pool_head = (unsigned long long *)c->d_ctl.get();
+    a.pool_words = c->d_pool.cap();
     a.epoch = c->epoch;
     a.status = (int32_t *)(c->d_ctl + 8);
     a.work = count ? (unsigned long long *)(c->d_ctl + 16) : nullptr;
@@ -432,12 +409,7 @@ svt_status launch(svt_ctx *c, const svt_locus *d_loci, svt_result *d_out, size_t
         // one-wave-per-window span kernel is as fast or faster (fewer, longer waves leave the
         // chip underfilled: cfg2 20K windows 33 us span vs 76 us lane<8>, 107 us lane<32>;
         // cfg3 100K windows 111 vs 109 us; cfg4 2M windows 2.23 ms vs 0.905 ms)
-        if (c->redo_cap < 2 * n) {   // window list of the wave-wide left-overs (grown, never shrunk)
-            hfree(c->d_redo);
-            c->redo_cap = 0;
-            HIP_TRY(c, hipMalloc(&c->d_redo, 2 * n * sizeof(uint32_t)));
-            c->redo_cap = 2 * n;
-        }
+        HIP_TRY(c, c->d_redo.reserve(2 * n));   // window list of the wave-wide left-overs
         // Two left-over counters alternate between direct lane launches: this launch appends to
         // ctr[par]; its redo kernel reads that and zeroes ctr[par ^ 1] for the next one.  The
         // parity advances on direct lane launches only (counting and span launches in between leave
@@ -479,19 +451,15 @@ svt_status launch(svt_ctx *c, const svt_locus *d_loci, svt_result *d_out, size_t
 }
 
 svt_status ensure_batch(svt_ctx *c, size_t n) {
-    if (n <= c->batch_cap) return SVT_OK;
-    hfree(c->d_loci); hfree(c->d_out);
-    c->batch_cap = 0;
-    HIP_TRY(c, hipMalloc(&c->d_loci, n * sizeof(svt_locus)));
-    HIP_TRY(c, hipMalloc(&c->d_out, n * sizeof(svt_result)));
-    c->batch_cap = n;
+    HIP_TRY(c, c->d_loci.reserve(n));
+    HIP_TRY(c, c->d_out.reserve(n));
     return SVT_OK;
 }
 
 template <typename T>
-svt_status upload(svt_ctx *c, T *&dst, const T *src, size_t n, size_t pad_elems = 0) {
+svt_status upload(svt_ctx *c, DevBuf<T> &dst, const T *src, size_t n, size_t pad_elems = 0) {
     size_t bytes = (n + pad_elems) * sizeof(T);
-    HIP_TRY(c, hipMalloc(&dst, bytes ? bytes : sizeof(T)));
+    HIP_TRY(c, dst.reserve(std::max<size_t>(n + pad_elems, 1)));
     if (n) HIP_TRY(c, hipMemcpy(dst, src, n * sizeof(T), hipMemcpyHostToDevice));
     if (pad_elems) HIP_TRY(c, hipMemset(dst + n, 0, pad_elems * sizeof(T)));
     c->dev_bytes += bytes;
@@ -536,9 +504,7 @@ svt_status svt_open(const svt_params *params, int device, svt_ctx **out) {
     DevGuard dg(c->device);
     if (!dg.ok) { delete c; return SVT_EDEVICE; }
     uint64_t pool_bytes = params->spill_bytes ? params->spill_bytes : (64ull << 20);
-    c->pool_words = pool_bytes / 4;
-    if (hipMalloc(&c->d_pool, c->pool_words * 4) != hipSuccess || hipMalloc(&c->d_ctl, CTL_BYTES) != hipSuccess) {
-        hfree(c->d_pool);
+    if (c->d_pool.reserve(pool_bytes / 4) != hipSuccess || c->d_ctl.reserve(CTL_BYTES) != hipSuccess) {
         delete c;
         return SVT_ENOMEM;
     }
@@ -632,24 +598,18 @@ IxArgs ix_args(const svt_ctx *c) {
 
 svt_status build_index(svt_ctx *c, hipStream_t st, bool first, double *ms) {
     IxArgs a = ix_args(c);
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    DevEvent ev[4];
     if (ms)
-        for (auto &e : ev) HIP_TRY(c, hipEventCreate(&e));
-    auto done = [&](svt_status r) {
-        for (auto &e : ev)
-            if (e) (void)hipEventDestroy(e);
-        return r;
-    };
+        for (auto &e : ev) HIP_TRY(c, e.create());
     const bool lane = index_lane(c, c->n_ops, (uint64_t)c->n_reads);
     c->load_stats.index_kind = lane ? 1u : 2u;
     const uint32_t nparts = lane ? c->n_groups : c->n_ranges;   // what the scan runs over
     Ix2Args a2{a, c->d_cnt, (uint64_t)c->n_reads, c->n_groups};
     const dim3 grid2((unsigned)((c->n_groups + IX2_WPB - 1) / IX2_WPB)), block2(64 * IX2_WPB);
     const dim3 grid1((unsigned)((c->n_ranges + IX_WPB - 1) / IX_WPB)), block1(64 * IX_WPB);
-    if (ms && hipEventRecord(ev[0], st) != hipSuccess) return done(fail(c, SVT_EDEVICE, "%s", "hipEventRecord"));
+    if (ms) HIP_TRY(c, hipEventRecord(ev[0], st));
     if (c->bsum_dirty) {
-        if (hipMemsetAsync(c->d_bsum, 0, c->n_bsum * sizeof(IxTot), st) != hipSuccess)
-            return done(fail(c, SVT_EDEVICE, "%s", "index block sums: hipMemsetAsync"));
+        HIP_TRY(c, hipMemsetAsync(c->d_bsum, 0, c->n_bsum * sizeof(IxTot), st));
         c->bsum_dirty = false;
     }
     c->bsum_dirty = true;
@@ -663,41 +623,41 @@ svt_status build_index(svt_ctx *c, hipStream_t st, bool first, double *ms) {
                            (nparts + IX_BLK - 1) / IX_BLK, c->d_tot, c->d_spoffD, c->d_spoffI, (uint64_t)c->n_reads);
         e = hipGetLastError();
     }
-    if (e != hipSuccess) return done(fail(c, SVT_EDEVICE, "index census: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(c, SVT_EDEVICE, "index census: %s", hipGetErrorString(e));
     c->bsum_dirty = false;   // the scan launched: it zeroes the block sums behind itself
-    if (ms && hipEventRecord(ev[1], st) != hipSuccess) return done(fail(c, SVT_EDEVICE, "%s", "hipEventRecord"));
+    if (ms) HIP_TRY(c, hipEventRecord(ev[1], st));
     if (first) {
         uint64_t t[IX_NTOT];
         e = hipMemcpyAsync(t, c->d_tot, sizeof t, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return done(fail(c, SVT_EDEVICE, "index totals: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(c, SVT_EDEVICE, "index totals: %s", hipGetErrorString(e));
         c->n_evD = t[IX_D];
         c->n_evI = t[IX_I];
         c->n_ins = t[IX_I];
         svt_status s;
-        if ((s = upload<uint4>(c, c->d_spD, nullptr, 0, std::max<uint64_t>(c->n_evD, 1)))) return done(s);
-        if ((s = upload<uint4>(c, c->d_spI, nullptr, 0, std::max<uint64_t>(c->n_evI, 1)))) return done(s);
+        if ((s = upload<uint4>(c, c->d_spD, nullptr, 0, std::max<uint64_t>(c->n_evD, 1)))) return s;
+        if ((s = upload<uint4>(c, c->d_spI, nullptr, 0, std::max<uint64_t>(c->n_evI, 1)))) return s;
         a.spD = c->d_spD;
         a.spI = c->d_spI;
         a.capD = c->n_evD;
         a.capI = c->n_evI;
         a2.a = a;
     }
-    if (ms && hipEventRecord(ev[2], st) != hipSuccess) return done(fail(c, SVT_EDEVICE, "%s", "hipEventRecord"));
+    if (ms) HIP_TRY(c, hipEventRecord(ev[2], st));
     if (lane) hipLaunchKernelGGL(ix2_emit_kernel, grid2, block2, 0, st, a2);
     else hipLaunchKernelGGL(ix_copy_kernel, grid1, block1, 0, st, a);
     e = hipGetLastError();
-    if (e != hipSuccess) return done(fail(c, SVT_EDEVICE, "index emit: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(c, SVT_EDEVICE, "index emit: %s", hipGetErrorString(e));
     if (ms) {
         float t0 = 0.f, t1 = 0.f;
         e = hipEventRecord(ev[3], st);
         if (e == hipSuccess) e = hipEventSynchronize(ev[3]);
         if (e == hipSuccess) e = hipEventElapsedTime(&t0, ev[0], ev[1]);
         if (e == hipSuccess) e = hipEventElapsedTime(&t1, ev[2], ev[3]);
-        if (e != hipSuccess) return done(fail(c, SVT_EDEVICE, "index timing: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(c, SVT_EDEVICE, "index timing: %s", hipGetErrorString(e));
         *ms = (double)t0 + (double)t1;
     }
-    return done(SVT_OK);
+    return SVT_OK;
 }
 
 // ---- the value-bucketed event index (svt_bucket_build.inc): launch arguments, one pass, the
@@ -820,11 +780,11 @@ svt_status bk_load(svt_ctx *c, const std::vector<int64_t> &vtop) {
 // The pileup of a context from per-read columns in host memory -- nc[r] = n_cigar | clip << 30,
 // soff[0..nr] the reads' offsets in the CIGAR stream (a read without ops owns one 0M word) --
 // and the stream itself, in host memory (stream_h) or already on the device (stream_d, with
-// STREAM_PAD zero words after its end: adopted, the context frees it).  The host pass
+// STREAM_PAD zero words after its end: moved from once validation has passed, else left alone).  The host pass
 // validates and builds the prefix-max endpos, the records, the read buckets, the index ranges;
 // then the uploads and the first device index build.
 static svt_status load_core(svt_ctx *c, int32_t nt, const int64_t *tid_off, const int32_t *pos, const int32_t *endpos,
-                            const uint32_t *nc, const uint64_t *soff, const uint32_t *stream_h, uint32_t *stream_d,
+                            const uint32_t *nc, const uint64_t *soff, const uint32_t *stream_h, DevBuf<uint32_t> *stream_d,
                             uint64_t nops, double t_pre_ms) {
     using clk = std::chrono::steady_clock;
     auto ms_since = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
@@ -871,7 +831,7 @@ static svt_status load_core(svt_ctx *c, int32_t nt, const int64_t *tid_off, cons
     });
     for (int32_t t = 0; t < nt; t++)
         if (bad[(size_t)t]) return fail(c, SVT_EINVAL, "pileup: %s", bad[(size_t)t]);
-    if (stream_d) c->d_cigar = stream_d;   // the context owns it from here on (freed with the pileup)
+    if (stream_d) c->d_cigar = std::move(*stream_d);   // the context owns it from here on (freed with the pileup)
     std::vector<int64_t> bkt_off((size_t)nt + 1, 0);
     for (int32_t t = 0; t < nt; t++) bkt_off[(size_t)t + 1] = bkt_off[(size_t)t] + (int64_t)bk[(size_t)t].size();
     std::vector<uint2> bkt((size_t)bkt_off[(size_t)nt]);
@@ -1115,7 +1075,7 @@ svt_status svt_reindex(svt_ctx *c, void *stream) {
     {   // (the buffer is allocated in whole uint4s: upload's size below rounds it up)
         const uint64_t n4 = (BA_N * (c->bk_n + 1) + 3) / 4;
         hipLaunchKernelGGL(bk_zero_kernel, dim3((unsigned)std::min<uint64_t>((n4 + 255) / 256, 4096)), dim3(256), 0, st,
-                           reinterpret_cast<uint4 *>(c->d_bkcap), n4);
+                           reinterpret_cast<uint4 *>(c->d_bkcap.get()), n4);
         HIP_TRY(c, hipGetLastError());
     }
     if ((s = bk_pass(c, st, false, captured))) return s;
@@ -1290,45 +1250,34 @@ static svt_status sw_1(svt_ctx *c, const svt_sw_query *q, size_t n, int32_t wind
     DEV_GUARD(c);
     svt_status so = order_on(c, nullptr);
     if (so) return so;
-    uint4 *d_sub = nullptr;
-    int2 *d_res = nullptr;
-    uint64_t *d_off = nullptr;
-    int32_t *d_best = nullptr;
-    svt_status s = SVT_OK;
-    auto cleanup = [&]() { hfree(d_sub); hfree(d_res); hfree(d_off); hfree(d_best); };
-    auto chk = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && s == SVT_OK) s = fail(c, SVT_EDEVICE, what, hipGetErrorString(e));
-        return s == SVT_OK;
-    };
-    if (chk(hipMalloc(&d_sub, std::max<size_t>(1, (size_t)ns) * sizeof(uint4)), "hipMalloc: %s") &&
-        chk(hipMalloc(&d_res, std::max<size_t>(1, (size_t)ns) * sizeof(int2)), "hipMalloc: %s") &&
-        chk(hipMalloc(&d_off, (n + 1) * sizeof(uint64_t)), "hipMalloc: %s") &&
-        chk(hipMalloc(&d_best, n * sizeof(int32_t)), "hipMalloc: %s") &&
-        (ns == 0 || chk(hipMemcpy(d_sub, subs.data(), (size_t)ns * sizeof(uint4), hipMemcpyHostToDevice), "H2D: %s")) &&
-        chk(hipMemcpy(d_off, off.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice), "H2D: %s") &&
-        chk(hipMemsetAsync(c->d_ctl, 0, CTL_BYTES, nullptr), "hipMemset: %s")) {
-        if (ns) {
-            KArgs a = make_args(c, nullptr, nullptr, (uint32_t)ns, false);
-            a.prm.sw_window = window_size;
-            a.prm.sw_slide = slide_size;
-            a.sw_sub = d_sub;
-            a.sw_out = d_res;
-            const dim3 grid((unsigned)((ns + WPB - 1) / WPB)), block(64 * WPB);
-            hipLaunchKernelGGL(sw_kernel, grid, block, 0, nullptr, a);
-            chk(hipGetLastError(), "sw_kernel: %s");
-        }
-        if (s == SVT_OK) {
-            hipLaunchKernelGGL(sw_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, d_res,
-                               d_off, (uint32_t)n, d_best);
-            chk(hipGetLastError(), "sw_reduce_kernel: %s");
-        }
-        if (s == SVT_OK) s = svt_sync(c, nullptr);
-        if (s == SVT_OK) chk(hipMemcpy(best, d_best, n * sizeof(int32_t), hipMemcpyDeviceToHost), "D2H: %s");
-        if (s == SVT_OK && sub && ns)
-            chk(hipMemcpy(sub, d_res, (size_t)ns * sizeof(int2), hipMemcpyDeviceToHost), "D2H: %s");
+    DevBuf<uint4> d_sub;
+    DevBuf<int2> d_res;
+    DevBuf<uint64_t> d_off;
+    DevBuf<int32_t> d_best;
+    HIP_TRY(c, d_sub.reserve(std::max<size_t>(1, (size_t)ns)));
+    HIP_TRY(c, d_res.reserve(std::max<size_t>(1, (size_t)ns)));
+    HIP_TRY(c, d_off.reserve(n + 1));
+    HIP_TRY(c, d_best.reserve(n));
+    if (ns) HIP_TRY(c, hipMemcpy(d_sub, subs.data(), (size_t)ns * sizeof(uint4), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_off, off.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemsetAsync(c->d_ctl, 0, CTL_BYTES, nullptr));
+    if (ns) {
+        KArgs a = make_args(c, nullptr, nullptr, (uint32_t)ns, false);
+        a.prm.sw_window = window_size;
+        a.prm.sw_slide = slide_size;
+        a.sw_sub = d_sub;
+        a.sw_out = d_res;
+        const dim3 grid((unsigned)((ns + WPB - 1) / WPB)), block(64 * WPB);
+        hipLaunchKernelGGL(sw_kernel, grid, block, 0, nullptr, a);
+        HIP_TRY(c, hipGetLastError());
     }
-    cleanup();
-    return s;
+    hipLaunchKernelGGL(sw_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, d_res, d_off, (uint32_t)n,
+                       d_best);
+    HIP_TRY(c, hipGetLastError());
+    if (svt_status s = svt_sync(c, nullptr)) return s;
+    HIP_TRY(c, hipMemcpy(best, d_best, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (sub && ns) HIP_TRY(c, hipMemcpy(sub, d_res, (size_t)ns * sizeof(int2), hipMemcpyDeviceToHost));
+    return SVT_OK;
 }
 
 // ---- allele-consensus mode (POA; no reference behaviour, see svt_poa.inc)
@@ -1348,8 +1297,8 @@ svt_status svt_load_insseq(svt_ctx *c, const svt_insseq_view *v) {
     for (uint64_t k = 0; k < v->n_ins; k++)
         if (v->off[k + 1] < v->off[k]) return fail(c, SVT_EINVAL, "insseq: %s", "off not monotone");
     DEV_GUARD(c);
-    hfree(c->d_ins_off);
-    hfree(c->d_ins_bases);
+    c->d_ins_off.reset();
+    c->d_ins_bases.reset();
     c->insseq_loaded = false;
     const uint64_t nb = v->n_ins ? v->off[v->n_ins] : 0;
     svt_status s;
@@ -1407,12 +1356,7 @@ static svt_status evidence_1(svt_ctx *c, const svt_locus *loci, const svt_result
     DEV_GUARD(c);
     svt_status s = ensure_batch(c, n);   // d_out holds the refined results here
     if (s) return s;
-    if (n > c->evid_cap) {
-        hfree(c->d_evid);
-        c->evid_cap = 0;
-        HIP_TRY(c, hipMalloc(&c->d_evid, 2 * n * sizeof(svt_evidence)));
-        c->evid_cap = n;
-    }
+    HIP_TRY(c, c->d_evid.reserve(2 * n));
     HIP_TRY(c, hipMemcpy(c->d_loci, loci, n * sizeof(svt_locus), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->d_out, refined, n * sizeof(svt_result), hipMemcpyHostToDevice));
     if ((s = evidence_launch(c, c->d_loci, c->d_out, n, c->d_evid, nullptr))) return s;
@@ -1447,7 +1391,7 @@ svt_status svt_bgzf_inflate_device(svt_ctx *c, const uint8_t *d_comp, const svt_
     DEV_GUARD(c);
     const hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)std::min<size_t>(n, (size_t)INF_GRID);
-    if (!c->d_inferr) HIP_TRY(c, hipMalloc(&c->d_inferr, sizeof(uint32_t)));
+    HIP_TRY(c, c->d_inferr.reserve(1));
     // the scratch slots and the error word are per context: calls on different streams run in
     // submission order (like every other launch of the context)
     if (svt_status s = order_on(c, st)) return s;
@@ -1489,22 +1433,14 @@ svt_status svt_bgzf_inflate(svt_ctx *c, const uint8_t *comp, size_t comp_bytes, 
     DEV_GUARD(c);
     svt_status s = order_on(c, nullptr);
     if (s) return s;
-    auto grow = [&](auto *&p, size_t &cap, size_t bytes) -> svt_status {
-        if (bytes <= cap) return SVT_OK;
-        hfree(p);
-        cap = 0;
-        HIP_TRY(c, hipMalloc(&p, bytes));
-        cap = bytes;
-        return SVT_OK;
-    };
-    if ((s = grow(c->d_infc, c->infc_cap, comp_bytes + 64)) || (s = grow(c->d_info, c->info_cap, std::max<size_t>(out_bytes, 1))) ||
-        (s = grow(c->d_infb, c->infb_cap, n * sizeof(svt_bgzf_block))))
-        return s;
+    HIP_TRY(c, c->d_infc.reserve(comp_bytes + 64));
+    HIP_TRY(c, c->d_info.reserve(std::max<size_t>(out_bytes, 1)));
+    HIP_TRY(c, c->d_infb.reserve(n));
     HIP_TRY(c, hipMemcpy(c->d_infc, comp, comp_bytes, hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->d_infb, blocks, n * sizeof(svt_bgzf_block), hipMemcpyHostToDevice));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIP_TRY(c, hipEventCreate(&e0));
-    HIP_TRY(c, hipEventCreate(&e1));
+    DevEvent e0, e1;
+    HIP_TRY(c, e0.create());
+    HIP_TRY(c, e1.create());
     (void)hipEventRecord(e0, nullptr);
     s = svt_bgzf_inflate_device(c, c->d_infc, c->d_infb, n, c->d_info, nullptr);
     (void)hipEventRecord(e1, nullptr);
@@ -1512,8 +1448,6 @@ svt_status svt_bgzf_inflate(svt_ctx *c, const uint8_t *comp, size_t comp_bytes, 
     if (s == SVT_OK) s = svt_bgzf_inflate_status(c, nullptr, &bad);
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) c->inf_ms = ms;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     if (s) return s;
     HIP_TRY(c, hipMemcpy(out, c->d_info, out_bytes, hipMemcpyDeviceToHost));
     return SVT_OK;
@@ -1548,11 +1482,7 @@ void svt_close(svt_ctx *c) {
     for (svt_ctx *d : c->subs) svt_close(d);
     c->subs.clear();
     DevGuard dg(c->device);
-    if (c->order_ev) (void)hipEventDestroy(c->order_ev);
-    free_pileup(c);
-    hfree(c->d_infc); hfree(c->d_info); hfree(c->d_infb); hfree(c->d_inferr);
-    hfree(c->d_loci); hfree(c->d_out); hfree(c->d_evid); hfree(c->d_pool); hfree(c->d_ctl); hfree(c->d_redo); hfree(c->poa_small.d); hfree(c->poa_big.d);
-    delete c;
+    delete c;   // its buffers and its event go with it, on its own device
 }
 
 }  // extern "C"

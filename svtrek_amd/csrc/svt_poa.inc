@@ -67,12 +67,6 @@ struct PoaArgs {
     int4 *res;                  // [n] {len, n_support, n_used, status}
 };
 
-struct PoaPool {                // host-side record of one pool of scratch slots
-    uint8_t *d = nullptr;
-    uint64_t slot_bytes = 0;
-    uint32_t nslots = 0;
-};
-
 __host__ __device__ inline uint64_t poa_round(uint64_t b) { return (b + 255) & ~255ull; }
 
 // Bytes of one slot; poa_slot carves them in this order.

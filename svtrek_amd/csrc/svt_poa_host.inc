@@ -19,12 +19,9 @@ svt_status poa_pool(svt_ctx *c, PoaPool &pl, int32_t node_cap, int32_t spill_cap
                     uint64_t want) {
     const uint64_t sb = poa_slot_bytes(node_cap, spill_cap, p->max_len);
     if (pl.d && pl.slot_bytes == sb && pl.nslots >= want) return SVT_OK;
-    hfree(pl.d);
+    pl.d.reset();   // (not reserve: fewer, larger slots may need fewer bytes, and get their own block)
     pl.nslots = 0;
-    if (hipMalloc(&pl.d, want * sb) != hipSuccess) {
-        pl.d = nullptr;
-        return fail(c, SVT_ENOMEM, "%s", "poa scratch (lower max_nodes / max_len)");
-    }
+    if (svt_status s = nomem(c, pl.d.reserve(want * sb), "poa scratch (lower max_nodes / max_len)")) return s;
     pl.slot_bytes = sb;
     pl.nslots = (uint32_t)want;
     return SVT_OK;
@@ -50,7 +47,9 @@ svt_status poa_launch(svt_ctx *c, PoaArgs a, const PoaPool &pl, int32_t node_cap
     a.diag = nullptr;
     HIP_TRY(c, hipMemset(d_queue, 0, sizeof(uint32_t)));
 #if SVT_POA_DIAG
-    HIP_TRY(c, hipMalloc(&a.diag, PD_N * sizeof(unsigned long long)));
+    DevBuf<unsigned long long> diag;
+    HIP_TRY(c, diag.reserve(PD_N));
+    a.diag = diag;
     HIP_TRY(c, hipMemset(a.diag, 0, PD_N * sizeof(unsigned long long)));
     HIP_TRY(c, hipMemset(a.diag + PD_T0, 0xff, sizeof(unsigned long long)));
 #endif
@@ -61,7 +60,6 @@ svt_status poa_launch(svt_ctx *c, PoaArgs a, const PoaPool &pl, int32_t node_cap
 #if SVT_POA_DIAG
     unsigned long long h[PD_N];
     HIP_TRY(c, hipMemcpy(h, a.diag, sizeof h, hipMemcpyDeviceToHost));
-    (void)hipFree(a.diag);
     fprintf(stderr, "poa_diag node_cap=%d grid=%u loci=%u wave-ms: support %.1f load %.1f rows %.1f trace %.1f "
             "fuse %.1f cons %.1f | rows %llu steps %llu seqs %llu far %llu\n", node_cap, grid, n, h[PD_SUPPORT] * 1e-5,
             h[PD_LOAD] * 1e-5, h[PD_ROWS] * 1e-5, h[PD_TRACE] * 1e-5, h[PD_FUSE] * 1e-5, h[PD_CONS] * 1e-5,
@@ -74,72 +72,63 @@ svt_status poa_launch(svt_ctx *c, PoaArgs a, const PoaPool &pl, int32_t node_cap
 
 svt_status poa_run(svt_ctx *c, const svt_poa_params *p, const svt_locus *loci, const svt_result *refined, size_t n,
                    int32_t cap, uint8_t *bases, svt_poa_result *res) {
-    svt_locus *d_loci = nullptr;
-    svt_result *d_ref = nullptr;
-    uint8_t *d_out = nullptr;
-    int4 *d_res = nullptr;
-    uint32_t *d_aux = nullptr;   // [0] work queue, [1 .. n] locus order, [n+1 .. 2n] cost estimates
-    int32_t *d_sup = nullptr;    // [n] supporting sequences found, then [n][max_support] their indices
-    svt_status s = SVT_OK;
-    auto chk = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && s == SVT_OK) s = fail(c, SVT_EDEVICE, what, hipGetErrorString(e));
-        return s == SVT_OK;
-    };
+    DevBuf<svt_locus> d_loci;
+    DevBuf<svt_result> d_ref;
+    DevBuf<uint8_t> d_out;
+    DevBuf<int4> d_res;
+    DevBuf<uint32_t> d_aux;   // [0] work queue, [1 .. n] locus order, [n+1 .. 2n] cost estimates
+    DevBuf<int32_t> d_sup;    // [n] supporting sequences found, then [n][max_support] their indices
+    svt_status s;
     const int32_t small_cap = poa_small_cap(p);
-    if (chk(hipMalloc(&d_loci, n * sizeof(svt_locus)), "hipMalloc: %s") &&
-        chk(hipMalloc(&d_ref, n * sizeof(svt_result)), "hipMalloc: %s") &&
-        chk(hipMalloc(&d_out, std::max<size_t>(1, n * (size_t)cap)), "hipMalloc: %s") &&
-        chk(hipMalloc(&d_res, n * sizeof(int4)), "hipMalloc: %s") &&
-        chk(hipMalloc(&d_aux, (2 * n + 1) * sizeof(uint32_t)), "hipMalloc: %s") &&
-        chk(hipMalloc(&d_sup, n * (1 + (size_t)p->max_support) * sizeof(int32_t)), "hipMalloc: %s") &&
-        chk(hipMemcpy(d_loci, loci, n * sizeof(svt_locus), hipMemcpyHostToDevice), "H2D: %s") &&
-        chk(hipMemcpy(d_ref, refined, n * sizeof(svt_result), hipMemcpyHostToDevice), "H2D: %s")) {
-        const KArgs k = make_args(c, nullptr, nullptr, 0, false);
-        PoaArgs a;
-        a.pile = k.pile;
-        a.prm = k.prm;
-        a.pp = PoaParams{p->match, p->mismatch, p->gap_open, p->gap_ext, p->band_b, p->band_f_permille,
-                         p->max_seqs, p->max_len, p->max_nodes, p->support_radius, p->max_support};
-        a.loci = d_loci;
-        a.refined = d_ref;
-        a.n = (uint32_t)n;
-        a.ins_base = c->d_spoffI;
-        a.ins_off = c->d_ins_off;
-        a.ins_bases = c->d_ins_bases;
-        a.cap = cap;
-        a.out = d_out;
-        a.res = d_res;
-        a.nsupg = d_sup;
-        a.supg = d_sup + n;
-        a.est = d_aux + 1 + n;
-        a.diag = nullptr;
-        // supports + cost estimates, then the loci longest first (ties: input order)
-        hipLaunchKernelGGL(poa_support_kernel, dim3((unsigned)std::min<size_t>(n, 8192)), dim3(64), 0, nullptr, a);
-        std::vector<uint32_t> est(n), order(n);
-        if (chk(hipGetLastError(), "poa_support_kernel: %s") &&
-            chk(hipMemcpy(est.data(), a.est, n * sizeof(uint32_t), hipMemcpyDeviceToHost), "D2H: %s")) {
-            for (size_t i = 0; i < n; i++) order[i] = (uint32_t)i;
-            std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return est[x] > est[y]; });
-            chk(hipMemcpy(d_aux + 1, order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice), "H2D: %s");
-        }
-        if (s == SVT_OK)
-            s = poa_pool(c, c->poa_small, small_cap, POA_SMALL_SPILL, p, std::min<uint64_t>(n, POA_SLOTS_SMALL));
-        if (s == SVT_OK) s = poa_launch(c, a, c->poa_small, small_cap, POA_SMALL_SPILL, d_aux + 1, (uint32_t)n, d_aux);
-        if (s == SVT_OK && chk(hipMemcpy(res, d_res, n * sizeof(int4), hipMemcpyDeviceToHost), "D2H: %s")) {
-            std::vector<uint32_t> deferred;   // in the same longest-first order
-            for (size_t q = 0; q < n; q++)
-                if (res[order[q]].status == POA_DEFER) deferred.push_back(order[q]);
-            if (!deferred.empty()) {
-                const uint32_t nd = (uint32_t)deferred.size();
-                if (chk(hipMemcpy(d_aux + 1, deferred.data(), nd * sizeof(uint32_t), hipMemcpyHostToDevice), "H2D: %s"))
-                    s = poa_pool(c, c->poa_big, p->max_nodes, p->max_nodes + 2, p, std::min<uint64_t>(nd, POA_SLOTS_BIG));
-                if (s == SVT_OK) s = poa_launch(c, a, c->poa_big, p->max_nodes, p->max_nodes + 2, d_aux + 1, nd, d_aux);
-                if (s == SVT_OK) chk(hipMemcpy(res, d_res, n * sizeof(int4), hipMemcpyDeviceToHost), "D2H: %s");
-            }
-            c->poa_deferred = deferred.size();
-            if (s == SVT_OK && cap > 0) chk(hipMemcpy(bases, d_out, n * (size_t)cap, hipMemcpyDeviceToHost), "D2H: %s");
-        }
+    HIP_TRY(c, d_loci.reserve(n));
+    HIP_TRY(c, d_ref.reserve(n));
+    HIP_TRY(c, d_out.reserve(std::max<size_t>(1, n * (size_t)cap)));
+    HIP_TRY(c, d_res.reserve(n));
+    HIP_TRY(c, d_aux.reserve(2 * n + 1));
+    HIP_TRY(c, d_sup.reserve(n * (1 + (size_t)p->max_support)));
+    HIP_TRY(c, hipMemcpy(d_loci, loci, n * sizeof(svt_locus), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_ref, refined, n * sizeof(svt_result), hipMemcpyHostToDevice));
+    const KArgs k = make_args(c, nullptr, nullptr, 0, false);
+    PoaArgs a;
+    a.pile = k.pile;
+    a.prm = k.prm;
+    a.pp = PoaParams{p->match, p->mismatch, p->gap_open, p->gap_ext, p->band_b, p->band_f_permille,
+                     p->max_seqs, p->max_len, p->max_nodes, p->support_radius, p->max_support};
+    a.loci = d_loci;
+    a.refined = d_ref;
+    a.n = (uint32_t)n;
+    a.ins_base = c->d_spoffI;
+    a.ins_off = c->d_ins_off;
+    a.ins_bases = c->d_ins_bases;
+    a.cap = cap;
+    a.out = d_out;
+    a.res = d_res;
+    a.nsupg = d_sup;
+    a.supg = d_sup + n;
+    a.est = d_aux + 1 + n;
+    a.diag = nullptr;
+    // supports + cost estimates, then the loci longest first (ties: input order)
+    hipLaunchKernelGGL(poa_support_kernel, dim3((unsigned)std::min<size_t>(n, 8192)), dim3(64), 0, nullptr, a);
+    std::vector<uint32_t> est(n), order(n);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpy(est.data(), a.est, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) order[i] = (uint32_t)i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return est[x] > est[y]; });
+    HIP_TRY(c, hipMemcpy(d_aux + 1, order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if ((s = poa_pool(c, c->poa_small, small_cap, POA_SMALL_SPILL, p, std::min<uint64_t>(n, POA_SLOTS_SMALL)))) return s;
+    if ((s = poa_launch(c, a, c->poa_small, small_cap, POA_SMALL_SPILL, d_aux + 1, (uint32_t)n, d_aux))) return s;
+    HIP_TRY(c, hipMemcpy(res, d_res, n * sizeof(int4), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> deferred;   // in the same longest-first order
+    for (size_t q = 0; q < n; q++)
+        if (res[order[q]].status == POA_DEFER) deferred.push_back(order[q]);
+    c->poa_deferred = deferred.size();
+    if (!deferred.empty()) {
+        const uint32_t nd = (uint32_t)deferred.size();
+        HIP_TRY(c, hipMemcpy(d_aux + 1, deferred.data(), nd * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if ((s = poa_pool(c, c->poa_big, p->max_nodes, p->max_nodes + 2, p, std::min<uint64_t>(nd, POA_SLOTS_BIG)))) return s;
+        if ((s = poa_launch(c, a, c->poa_big, p->max_nodes, p->max_nodes + 2, d_aux + 1, nd, d_aux))) return s;
+        HIP_TRY(c, hipMemcpy(res, d_res, n * sizeof(int4), hipMemcpyDeviceToHost));
     }
-    hfree(d_loci); hfree(d_ref); hfree(d_out); hfree(d_res); hfree(d_aux); hfree(d_sup);
-    return s;
+    if (cap > 0) HIP_TRY(c, hipMemcpy(bases, d_out, n * (size_t)cap, hipMemcpyDeviceToHost));
+    return SVT_OK;
 }

@@ -1,13 +1,16 @@
 """C-ABI contract details through the HIP engine (include/svtrek_gpu.h): gather records,
 launch ordering across streams, multi-device contexts, device selection, and the event
 walk's work counters (the roofline's algorithmic bytes)."""
+import dataclasses
+import functools
+
 import numpy as np
 import oracle_ffi as O
 import pytest
 import torch
 
-from svtrek_amd import Engine, Params, sim
-from svtrek_amd._lib import LOCUS_DTYPE, RECORD_DTYPE, RESULT_DTYPE
+from svtrek_amd import Engine, Params, SvtError, sim
+from svtrek_amd._lib import LOCUS_DTYPE, RECORD_DTYPE, RESULT_DTYPE, SVT_EINVAL, SVT_ESTATE
 
 pytestmark = pytest.mark.gpu
 
@@ -249,3 +252,90 @@ def test_graph_replays_between_direct_lane_launches(engine_factory):
 
     for f in (direct, replay, direct, direct, replay, replay, direct):
         f()
+
+
+# ---- what a loaded pileup owns on the device goes with it: reloads, failed loads, the side modes'
+# scratch.  Pileup A, and B (another seed, a sixth of the loci) into which every buffer shrinks.
+@functools.lru_cache(maxsize=None)
+def _pileups():
+    a = sim.generate(sim.SimConfig(seed=61, n_targets=2, n_loci=3000, del_frac=0.5, coverage=25.0), keep_handle=True)
+    b = sim.generate(sim.SimConfig(seed=73, n_targets=2, n_loci=500, del_frac=0.5, coverage=25.0))
+    return a, b
+
+
+def _observe(eng, r):
+    """Everything a caller can read off a loaded pileup (timings aside)."""
+    refined = eng.refine(r.loci)
+    stats = {k: v for k, v in eng.load_stats().items() if not k.endswith("_ms")}
+    return {"refine": refined, "evidence": eng.evidence(r.loci, refined), "call": eng.call(),
+            "device_bytes": eng.device_bytes, "load_stats": stats}
+
+
+def _same_observed(got, want):
+    for k in ("refine", "evidence", "call"):
+        assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, k
+        assert got[k].tobytes() == want[k].tobytes(), k
+    assert got["device_bytes"] == want["device_bytes"]
+    assert got["load_stats"] == want["load_stats"]
+
+
+@pytest.mark.parametrize("gather,env", [("span", None), ("span1", None), ("span", {"SVTREK_IX": "stream"})],
+                         ids=["lane", "span1", "stream_index"])
+def test_reload_resets_everything_a_pileup_owns(engine_factory, gather, env):
+    """A, B, A on one engine: B's results, device bytes and load statistics are those of an engine
+    that only ever loaded B, and the second A repeats the first exactly (SVTREK_IX=stream: the
+    stream walk's scratch is part of what a reload drops)."""
+    a, b = _pileups()
+    eng = engine_factory(gather=gather, env=env)
+    eng.load_pileup(a.pileup)
+    first_a = _observe(eng, a)
+    eng.count_work(a.loci)
+    assert len(first_a["call"]) > 0 and (first_a["refine"]["start"] != 0xFFFFFFFF).any()
+    fresh = engine_factory(gather=gather, env=env)
+    fresh.load_pileup(b.pileup)
+    want_b = _observe(fresh, b)
+    assert want_b["device_bytes"] < first_a["device_bytes"]
+    eng.load_pileup(b.pileup)
+    _same_observed(_observe(eng, b), want_b)
+    eng.load_pileup(a.pileup)
+    _same_observed(_observe(eng, a), first_a)
+
+
+def test_failed_load_leaves_the_context_usable(engine_factory):
+    """A pileup whose reads are not sorted is refused (SVT_EINVAL) after the old pileup has gone:
+    refine then reports SVT_ESTATE, and loading the good pileup again gives the first results."""
+    a, _ = _pileups()
+    eng = engine_factory()
+    eng.load_pileup(a.pileup)
+    first = _observe(eng, a)
+    with pytest.raises(SvtError) as ei:
+        eng.load_pileup(dataclasses.replace(a.pileup, pos=a.pileup.pos[::-1].copy()))
+    assert ei.value.code == SVT_EINVAL
+    with pytest.raises(SvtError) as ei:
+        eng.refine(a.loci)
+    assert ei.value.code == SVT_ESTATE
+    eng.load_pileup(a.pileup)
+    _same_observed(_observe(eng, a), first)
+
+
+def test_poa_and_call_scratch_across_a_reload(engine_factory):
+    """The inserted sequences and the call scratch belong to the pileup: after a reload
+    poa_consensus needs svt_load_insseq again, and call() is a fresh engine's."""
+    a, b = _pileups()
+    off, bases = sim.insertion_sequences(a, sim.SimConfig(seed=61, n_targets=2, n_loci=3000, del_frac=0.5, coverage=25.0))
+    eng = engine_factory()
+    eng.load_pileup(a.pileup)
+    eng.load_insseq(off, bases)
+    ins = a.loci[a.loci["type"] == 1][:48]
+    res, _ = eng.poa_consensus(ins, eng.refine(ins))
+    assert len(ins) == 48 and (res["len"] > 0).any()
+    assert len(eng.call()) > 0
+    eng.load_pileup(b.pileup)
+    ins_b = b.loci[b.loci["type"] == 1][:48]
+    with pytest.raises(SvtError, match="svt_load_insseq not called") as ei:
+        eng.poa_consensus(ins_b, eng.refine(ins_b))
+    assert ei.value.code == SVT_ESTATE
+    fresh = engine_factory()
+    fresh.load_pileup(b.pileup)
+    got, want = eng.call(), fresh.call()
+    assert got.dtype == want.dtype and got.tobytes() == want.tobytes() and len(want) > 0

@@ -65,16 +65,40 @@ def test_long_cigars_from_cg_tags(engine_factory, tmp_path):
     assert st["cg_restored"] == int((np.diff(r.pileup.cig_off.astype(np.int64)) > 65535).sum()) > 0
 
 
-def test_unsorted_bam_is_sorted(engine_factory, tmp_path):
+def _write_unsorted(path):
     raw, recs = bamfix.make_bam(seed=7, n_reads=800, unplaced=5)
     # swap two records of contig 1: the file is no longer coordinate-sorted
     hdr_len = len(raw) - sum(len(r["raw"]) for r in recs)
     body = [r["raw"] for r in recs]
     body[10], body[500] = body[500], body[10]
-    path = str(tmp_path / "u.bam")
     with open(path, "wb") as f:
         f.write(bamfix.bgzf_blocks(raw[:hdr_len] + b"".join(body)))
+
+
+def test_unsorted_bam_is_sorted(engine_factory, tmp_path):
+    path = str(tmp_path / "u.bam")
+    _write_unsorted(path)
     _same_as_host(engine_factory, path, _loci(np.random.default_rng(7), 3))
+
+
+def test_stream_adoption(engine_factory, tmp_path):
+    """The decoder's CIGAR stream becomes the context's when a sorted BAM loads (the decoder is
+    closed inside load_bam_device, the results still stand), and stays the decoder's -- freed with
+    it -- when the unsorted file is re-sorted on the host.  One engine takes a sorted BAM, another
+    one, the unsorted one and the first again, each through a new decoder."""
+    paths = [str(tmp_path / f"{k}.bam") for k in ("a", "b", "u")]
+    n_ref = [bamfix.write(paths[0], seed=51)[1], bamfix.write(paths[1], seed=52)[1], 3]
+    _write_unsorted(paths[2])
+    dev = engine_factory()
+    for k in (0, 1, 2, 0):
+        pl, _ = host.read_bam(paths[k], threads=2)
+        st = host.load_bam_device(dev, paths[k], threads=2)
+        assert st["reads"] == len(pl.pos) > 0
+        ref = engine_factory()
+        ref.load_pileup(pl)
+        loci = _loci(np.random.default_rng(50 + k), n_ref[k])
+        np.testing.assert_array_equal(dev.refine(loci), ref.refine(loci))
+        assert dev.device_bytes == ref.device_bytes
 
 
 def test_corrupt_and_truncated(engine_factory, tmp_path):
