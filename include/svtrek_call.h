@@ -26,8 +26,8 @@
  * a bucket (it differs from rebuild to rebuild): a scan of the same pileup gives the same records.
  *
  * LIMITATION: items are clustered by their start alone.  Two deletions of different length at one
- * start become ONE call, whose len is their mean; len_lo / len_hi show it.  Splitting by length or
- * genotype is out of scope.
+ * start become ONE call, whose len is their mean; len_lo / len_hi show it.  Splitting by length is
+ * out of scope; svtrek_genotype.h genotypes the calls (or any site with a length range of its own).
  *
  * Status codes: svt_call_scan is SVT_ESTATE before svt_load_pileup and when the value buckets are
  * not built (SVTREK_INDEX=lists, or a pileup too large for them); SVT_EINVAL on NULL arguments,

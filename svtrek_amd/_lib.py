@@ -34,6 +34,14 @@ EVIDENCE_DTYPE = np.dtype([("support", "<u4"), ("depth", "<u4"), ("lo", "<u4"), 
 CALL_DTYPE = np.dtype([("type", "<i4"), ("chrom", "<i4"), ("pos", "<u4"), ("end", "<u4"), ("support", "<u4"),
                        ("depth", "<u4"), ("len", "<u4"), ("len_lo", "<u4"), ("len_hi", "<u4"), ("x_lo", "<u4"),
                        ("x_hi", "<u4"), ("pad", "<u4")])   # svt_call (48 B)
+GT_SITE_DTYPE = np.dtype([("type", "<i4"), ("chrom", "<i4"), ("pos", "<u4"), ("end", "<u4"), ("x_lo", "<u4"),
+                          ("x_hi", "<u4"), ("len_lo", "<u4"), ("len_hi", "<u4")])   # svt_gt_site (32 B)
+GT_DTYPE = np.dtype([("alt", "<u4"), ("ref", "<u4"), ("span", "<u4"), ("alt_all", "<u4"), ("gt", "<i4"), ("gq", "<u4"),
+                     ("pl", "<u2", (3,)), ("pad", "<u2")])   # svt_gt (32 B)
+
+
+class SvtGtParams(C.Structure):
+    _fields_ = [("flank", C.c_int32), ("pad", C.c_int32), ("ref_cost", C.c_uint32 * 3), ("alt_cost", C.c_uint32 * 3)]
 
 
 class SvtCallParams(C.Structure):
@@ -143,6 +151,8 @@ ENGINE_SYMBOLS = (
 EVIDENCE_SYMBOLS = ("svt_evidence_batch", "svt_evidence_device")
 # include/svtrek_call.h: likewise (Engine.call raises on a backend without it)
 CALL_SYMBOLS = ("svt_call_default_params", "svt_call_scan", "svt_call_fetch", "svt_call_device", "svt_call_stats_get")
+# include/svtrek_genotype.h: likewise (Engine.genotype raises on a backend without it)
+GENOTYPE_SYMBOLS = ("svt_genotype_default_params", "svt_genotype_batch", "svt_genotype_device", "svt_genotype_calls")
 
 _engine = None
 
@@ -242,7 +252,20 @@ def bind_abi(lib: C.CDLL) -> C.CDLL:
         lib.svt_call_stats_get.argtypes = [P, C.POINTER(SvtCallStats)]
         for name in CALL_SYMBOLS[1:]:
             getattr(lib, name).restype = C.c_int32
+    if has_genotype(lib):
+        lib.svt_genotype_default_params.argtypes = [P, C.POINTER(SvtGtParams)]
+        lib.svt_genotype_default_params.restype = None
+        lib.svt_genotype_batch.argtypes = [P, C.POINTER(SvtGtParams), P, C.c_size_t, P]
+        lib.svt_genotype_device.argtypes = [P, C.POINTER(SvtGtParams), P, C.c_size_t, P, P]
+        lib.svt_genotype_calls.argtypes = [P, C.POINTER(SvtGtParams), P, C.c_uint64]
+        for name in GENOTYPE_SYMBOLS[1:]:
+            getattr(lib, name).restype = C.c_int32
     return lib
+
+
+def has_genotype(lib: C.CDLL) -> bool:
+    """Does the library export include/svtrek_genotype.h's entry points?"""
+    return all(hasattr(lib, name) for name in GENOTYPE_SYMBOLS)
 
 
 def has_call(lib: C.CDLL) -> bool:

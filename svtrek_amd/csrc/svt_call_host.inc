@@ -43,6 +43,7 @@ svt_status call_prepare(svt_ctx *c) {
 svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) {
     CallScratch &k = c->call;
     k.n_calls = 0;
+    k.scanned = true;
     k.stats = svt_call_stats{};
     const uint64_t N = c->bk_events[BA_S] + c->bk_events[BA_I];
     if (c->n_reads == 0 || N == 0) {

@@ -71,6 +71,7 @@ struct DevEvent {
 // of a loaded pileup, gone with the pileup.
 struct CallScratch {
     bool ready = false;
+    bool scanned = false;          // svt_call_scan ran on this pileup (svt_genotype_calls)
     uint64_t n_seg = 0;
     DevBuf<uint64_t> d_seg;
     DevBuf<unsigned long long> d_keys, d_tmax, d_tprev;

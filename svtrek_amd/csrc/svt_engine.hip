@@ -28,6 +28,7 @@
 //   svt_lane.inc          refine_lane_kernel and its helpers
 //   svt_evidence.inc      read support, depth and value range per refined breakpoint
 //   svt_call.inc          DEL / INS discovery from the value buckets (host side: svt_call_host.inc)
+//   svt_genotype.inc      genotypes of DEL / INS sites (host side: svt_genotype_host.inc)
 //   svt_index.inc, svt_index2.inc, svt_bucket_build.inc   the index builds (span lists, value buckets)
 //   svt_poa.inc, svt_poa_host.inc      allele consensus (POA): kernels, slot pools and poa_run
 //   svt_bam.inc, svt_inflate.inc, svt_bam_host.inc   BGZF inflate and BAM decode: kernels, svt_bam_dec_*
@@ -53,9 +54,10 @@
 #include "../../include/svtrek_gpu.h"
 #include "../../include/svtrek_evidence.h"
 #include "../../include/svtrek_call.h"
+#include "../../include/svtrek_genotype.h"
 #include "svt_bamrec.h"
 
-#define SVT_VERSION "svtrek_amd 0.27.0 (gfx950, value-bucketed event index filed by a lane-per-read walk with a 9-B LDS stage, band + prefix-max facts, packed span walk fed by readlane, lane vote on 64 windows a wave, BGZF inflate + BAM decode, DEL/INS discovery from the value buckets)"
+#define SVT_VERSION "svtrek_amd 0.28.0 (gfx950, value-bucketed event index filed by a lane-per-read walk with a 9-B LDS stage, band + prefix-max facts, packed span walk fed by readlane, lane vote on 64 windows a wave, BGZF inflate + BAM decode, DEL/INS discovery from the value buckets, genotypes from the events' own read extents)"
 
 namespace {
 
@@ -169,6 +171,7 @@ constexpr int LV_WMAX = 1023;   // band half-width for 16-bit offsets and prefix
 #include "svt_lane.inc"
 #include "svt_evidence.inc"
 #include "svt_call.inc"
+#include "svt_genotype.inc"
 #include "svt_index.inc"
 #include "svt_index2.inc"
 #include "svt_bucket_build.inc"
@@ -257,6 +260,8 @@ struct svt_ctx : Pileup {
     DevBuf<svt_locus> d_loci;
     DevBuf<svt_result> d_out;
     DevBuf<svt_evidence> d_evid;  // svt_evidence_batch's records [2 * n]
+    DevBuf<svt_gt_site> d_gtsite; // svt_genotype_batch's sites
+    DevBuf<svt_gt> d_gt;          // svt_genotype_batch's / svt_genotype_calls' records
     // spill pool (d_pool.cap() words) + status + work counters
     DevBuf<int32_t> d_pool;
     DevBuf<unsigned char> d_ctl;  // [0,8) pool head (epoch-tagged), [8,12) sticky status, [12,16) index
@@ -1377,6 +1382,9 @@ svt_status svt_evidence_batch(svt_ctx *c, const svt_locus *loci, const svt_resul
 
 // ---- include/svtrek_call.h
 #include "svt_call_host.inc"
+
+// ---- include/svtrek_genotype.h
+#include "svt_genotype_host.inc"
 
 uint64_t svt_pileup_device_bytes(const svt_ctx *c) { return c ? c->dev_bytes : 0; }
 

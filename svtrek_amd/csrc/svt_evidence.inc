@@ -100,18 +100,24 @@ __device__ __forceinline__ void ev_support(const KArgs &a, int chrom, uint32_t s
     else ev_span<KIND>(a.pile, chrom - 1, s, e, sk);
 }
 
-// Reads of contig tid with pos <= R < endpos.
-__device__ __forceinline__ uint32_t ev_depth(const DevPileup &P, int tid, uint32_t R) {
+// Reads of contig tid with pos <= a and endpos > b (a, b >= 0): the region query [b, max(a, b) + 1) yields
+// every read with pos <= max(a, b) that ends past b, then both bounds are tested, 64 reads a trip.
+__device__ __forceinline__ uint32_t span_reads(const DevPileup &P, int tid, int64_t a, int64_t b) {
     int64_t lo, hi;
-    if (!read_range(P, tid, (int64_t)R, (int64_t)R + 1, lo, hi)) return 0u;
+    if (!read_range(P, tid, b, max(a, b) + 1, lo, hi)) return 0u;
     const int ln = lane_id();
     uint32_t cnt = 0;
     for (int64_t base = lo; base < hi; base += WAVE) {
         const int64_t r = base + ln;
-        const int32_t endpos = r < hi ? (int32_t)reinterpret_cast<const uint32_t *>(P.rec + r)[1] : 0;
-        cnt += (uint32_t)__popcll(ballot(r < hi && (int64_t)endpos > (int64_t)R));
+        const uint2 pe = r < hi ? *reinterpret_cast<const uint2 *>(P.rec + r) : make_uint2(0u, 0u);   // {pos, endpos}
+        cnt += (uint32_t)__popcll(ballot(r < hi && (int64_t)(int32_t)pe.x <= a && (int64_t)(int32_t)pe.y > b));
     }
     return cnt;
+}
+
+// Reads of contig tid with pos <= R < endpos.
+__device__ __forceinline__ uint32_t ev_depth(const DevPileup &P, int tid, uint32_t R) {
+    return span_reads(P, tid, (int64_t)R, (int64_t)R);
 }
 
 __global__ __launch_bounds__(64 * WPB) void evidence_kernel(KArgs a, const svt_result *refined, svt_evidence *out) {

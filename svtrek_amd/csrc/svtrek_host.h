@@ -17,6 +17,7 @@
 #include "svtrek_gpu.h"
 #include "svtrek_evidence.h"
 #include "svtrek_call.h"
+#include "svtrek_genotype.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -118,6 +119,14 @@ char *svth_format_evidence(const svt_locus *l, const svt_result *r, const svt_ev
  * the first it finds.  malloc'ed (free with svth_free), *len = its length. */
 char *svth_format_calls(const svt_call *calls, size_t n, const char *const *names, size_t n_names, int header,
                         int threads, size_t *len);
+/* The same with genotypes (include/svtrek_genotype.h), gts[k] call k's record: the header gains the ##FORMAT
+ * lines of GT, GQ, DR, DV and PL and its column line "\tFORMAT\t<sample>" (sample NULL or "": SAMPLE); every
+ * record gains
+ *   GT:GQ:DR:DV:PL   0/0|0/1|1/1:gq:ref:alt:pl0,pl1,pl2        (a no call: ./.:0:0:0:0,0,0)
+ * INFO is unchanged and svth_parse_line reads the first 8 fields, so `svtrek audt` takes the file as it
+ * takes the sites-only one.  gts == NULL: svth_format_calls, byte for byte. */
+char *svth_format_calls_gt(const svt_call *calls, const svt_gt *gts, size_t n, const char *const *names, size_t n_names,
+                           const char *sample, int header, int threads, size_t *len);
 void  svth_free(void *p);
 
 /* A11: stdout text for one refined record; returns bytes written (0 = prints nothing:

@@ -37,6 +37,9 @@ extern "C" __typeof__(svt_call_default_params) svt_call_default_params __attribu
 extern "C" __typeof__(svt_call_scan) svt_call_scan __attribute__((weak));
 extern "C" __typeof__(svt_call_fetch) svt_call_fetch __attribute__((weak));
 extern "C" __typeof__(svt_call_stats_get) svt_call_stats_get __attribute__((weak));
+// include/svtrek_genotype.h likewise (`svtrek call --genotype`)
+extern "C" __typeof__(svt_genotype_default_params) svt_genotype_default_params __attribute__((weak));
+extern "C" __typeof__(svt_genotype_calls) svt_genotype_calls __attribute__((weak));
 
 namespace {
 
@@ -59,6 +62,10 @@ void call_usage() {
     printf("    --link <num>                      Largest gap between neighbouring starts of one cluster [Default: 10]\n");
     printf("    --min-support <num>               Fewest D > 50 / I >= 50 ops of a call [Default: %d]\n", MIN_COUNT);
     printf("    --types <DEL,INS>                 Types to call [Default: DEL,INS]\n");
+    printf("    --genotype                        Genotype every call: a FORMAT and a sample column with GT:GQ:DR:DV:PL\n");
+    printf("                                      [Default: a sites-only VCF]\n");
+    printf("    --flank <num>                     Bases a read must cover on both sides of a call to count [Default: 50]\n");
+    printf("    --sample <name>                   The sample column's name [Default: SAMPLE]\n");
     printf("    --device <num>                    GPU index [Default: 0]\n");
     printf("    --inflate <auto|gpu|cpu>          BGZF decompression of the BAM: the GPU or -t host threads;\n");
     printf("                                      auto: the GPU from 1 GiB of BAM on [Default: auto]\n");
@@ -555,15 +562,16 @@ int audit(int argc, char **argv) {
 // `svtrek call`: the BAM into a pileup as audt reads it (host threads, or the device's inflate with the
 // host parse -- the ingest that keeps the reference names), svt_call_scan, the calls as VCF text.
 int call_mode(int argc, char **argv) {
-    const char *bam_path = nullptr, *out_path = nullptr;
-    int threads = THREADS, verbose = 0, device = 0, gpu_inflate = -1, link = -1, min_support = -1;
+    const char *bam_path = nullptr, *out_path = nullptr, *sample = "SAMPLE";
+    int threads = THREADS, verbose = 0, device = 0, gpu_inflate = -1, link = -1, min_support = -1, genotype = 0, flank = -1;
     uint32_t types = (1u << SVT_INS) | (1u << SVT_DEL);
     static const option opts[] = {
         {"bam", required_argument, nullptr, 1}, {"output", required_argument, nullptr, 3},
         {"verbose", no_argument, nullptr, 4}, {"help", no_argument, nullptr, 11},
         {"device", required_argument, nullptr, 21}, {"inflate", required_argument, nullptr, 25},
         {"link", required_argument, nullptr, 30}, {"min-support", required_argument, nullptr, 31},
-        {"types", required_argument, nullptr, 32}, {nullptr, 0, nullptr, 0}};
+        {"types", required_argument, nullptr, 32}, {"genotype", no_argument, nullptr, 33},
+        {"flank", required_argument, nullptr, 34}, {"sample", required_argument, nullptr, 35}, {nullptr, 0, nullptr, 0}};
     int opt, li;
     while ((opt = getopt_long(argc, argv, "b:o:t:h", opts, &li)) != -1) {
         switch (opt) {
@@ -595,6 +603,9 @@ int call_mode(int argc, char **argv) {
             }
             break;
         }
+        case 33: genotype = 1; break;
+        case 34: flank = atoi(optarg); if (flank < 0 || flank > (1 << 20)) { fprintf(stderr, "[ERROR] --flank must be in [0, 1048576]\n"); exit(EXIT_FAILURE); } break;
+        case 35: sample = optarg; break;
         default:
             printf("[ERROR] Option %d is invalid.\n", opt);
             call_usage();
@@ -603,6 +614,10 @@ int call_mode(int argc, char **argv) {
     }
     validate_file(bam_path, "[ERROR] BAM file is not provided.");
     if (threads < 1) { fprintf(stderr, "[ERROR] -t must be >= 1\n"); exit(EXIT_FAILURE); }
+    if (genotype && (!svt_genotype_calls || !svt_genotype_default_params)) {
+        fprintf(stderr, "[ERROR] genotype: not supported by this backend\n");
+        return 1;
+    }
     if (!svt_call_scan || !svt_call_default_params || !svt_call_fetch || !svt_call_stats_get) {
         fprintf(stderr, "[ERROR] call: not supported by this backend\n");
         return 1;
@@ -648,12 +663,23 @@ int call_mode(int argc, char **argv) {
     if (!s) s = svt_call_fetch(ctx, 0, n, calls.data());
     svt_call_stats st{};
     if (!s) s = svt_call_stats_get(ctx, &st);
-    if (s) { fprintf(stderr, "[ERROR] GPU %d: %s (status %d)\n", device, svt_last_error(ctx), (int)s); return done(1); }
     const double t_scan = now_s();
+    std::vector<svt_gt> gts;
+    if (!s && genotype) {
+        svt_gt_params gp;
+        svt_genotype_default_params(ctx, &gp);
+        if (flank >= 0) gp.flank = flank;
+        gts.resize((size_t)n);
+        s = svt_genotype_calls(ctx, &gp, gts.data(), n);
+    }
+    if (s) { fprintf(stderr, "[ERROR] GPU %d: %s (status %d)\n", device, svt_last_error(ctx), (int)s); return done(1); }
+    const double t_gt = now_s();
     std::vector<const char *> names((size_t)svth_bam_n_targets(bam));
     for (size_t t = 0; t < names.size(); t++) names[t] = svth_bam_target_name(bam, (int32_t)t);
     size_t olen = 0;
-    char *text = svth_format_calls(calls.data(), calls.size(), names.data(), names.size(), 1, threads, &olen);
+    static const svt_gt no_gt{};   // (no calls: the header still has to say FORMAT)
+    char *text = svth_format_calls_gt(calls.data(), genotype ? (gts.empty() ? &no_gt : gts.data()) : nullptr, calls.size(),
+                                      names.data(), names.size(), sample, 1, threads, &olen);
     if (!text) { fprintf(stderr, "[ERROR] out of host memory\n"); return done(1); }
     FILE *of = out_path ? fopen(out_path, "wb") : stdout;
     bool ok = of && fwrite(text, 1, olen, of) == olen;
@@ -661,11 +687,12 @@ int call_mode(int argc, char **argv) {
     else if (of) ok = fflush(of) == 0 && ok;
     svth_free(text);
     if (!ok) { fprintf(stderr, "[ERROR] call: cannot write %s\n", out_path ? out_path : "stdout"); return done(1); }
+    if (verbose && genotype) fprintf(stderr, "[svtrek_amd] call: genotype %.3fs\n", t_gt - t_scan);
     if (verbose)
         fprintf(stderr, "[svtrek_amd] call: ingest %.3fs (%s)  load %.3fs  scan+fetch %.3fs (device scan %.3f ms)  print %.3fs  "
                         "items %llu (skipped %llu)  clusters %llu  calls %llu  big buckets %llu  link %d  min-support %d\n",
                 t_ingest - t0, gpu_inflate ? "gpu inflate, host parse" : "cpu", t_load - t_ingest, t_scan - t_load, st.scan_ms,
-                now_s() - t_scan, (unsigned long long)st.events, (unsigned long long)st.skipped, (unsigned long long)st.clusters,
+                now_s() - t_gt, (unsigned long long)st.events, (unsigned long long)st.skipped, (unsigned long long)st.clusters,
                 (unsigned long long)st.calls, (unsigned long long)st.big_buckets, cp.link, cp.min_support);
     return done(0);
 }

@@ -230,6 +230,11 @@ char *svth_format_evidence(const svt_locus *l, const svt_result *r, const svt_ev
 
 char *svth_format_calls(const svt_call *c, size_t n, const char *const *names, size_t n_names, int header, int threads,
                         size_t *len) {
+    return svth_format_calls_gt(c, nullptr, n, names, n_names, nullptr, header, threads, len);
+}
+
+char *svth_format_calls_gt(const svt_call *c, const svt_gt *gts, size_t n, const char *const *names, size_t n_names,
+                           const char *sample, int header, int threads, size_t *len) {
     const int T = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(threads, 1), n / 16384 + 1));
     // the ID's k: the call's rank among the calls of its type (1-based)
     std::vector<size_t> first_k((size_t)T * 2 + 2, 0);
@@ -256,10 +261,20 @@ char *svth_format_calls(const svt_call *c, size_t n, const char *const *names, s
             o += name;
             const int m = snprintf(buf, sizeof buf,
                                    "\t%u\tsvtrek.%s.%zu\tN\t<%s>\t.\tPASS\tSVTYPE=%s;END=%u;SVLEN=%s%u;SUPPORT=%u;DEPTH=%u;"
-                                   "XRANGE=%u,%u;LENRANGE=%u,%u\n",
+                                   "XRANGE=%u,%u;LENRANGE=%u,%u",
                                    x.pos, ty, ++rank[del ? 0 : 1], ty, ty, x.end, del ? "-" : "", x.len, x.support, x.depth,
                                    x.x_lo, x.x_hi, x.len_lo, x.len_hi);
             o.append(buf, (size_t)m);
+            if (gts) {
+                const svt_gt &g = gts[k];
+                static const char *const GT[3] = {"0/0", "0/1", "1/1"};
+                const int q = g.gt < 0 || g.gt > 2
+                                  ? snprintf(buf, sizeof buf, "\tGT:GQ:DR:DV:PL\t./.:0:0:0:0,0,0")
+                                  : snprintf(buf, sizeof buf, "\tGT:GQ:DR:DV:PL\t%s:%u:%u:%u:%u,%u,%u", GT[g.gt], g.gq, g.ref, g.alt,
+                                             (unsigned)g.pl[0], (unsigned)g.pl[1], (unsigned)g.pl[2]);
+                o.append(buf, (size_t)q);
+            }
+            o += '\n';
         }
     });
     std::string head;
@@ -273,8 +288,16 @@ char *svth_format_calls(const svt_call *c, size_t n, const char *const *names, s
                 "##INFO=<ID=SUPPORT,Number=1,Type=Integer,Description=\"CIGAR ops in the cluster\">\n"
                 "##INFO=<ID=DEPTH,Number=1,Type=Integer,Description=\"Reads covering POS\">\n"
                 "##INFO=<ID=XRANGE,Number=2,Type=Integer,Description=\"Smallest and largest start of the supporting ops\">\n"
-                "##INFO=<ID=LENRANGE,Number=2,Type=Integer,Description=\"Smallest and largest length of the supporting ops\">\n"
-                "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n";
+                "##INFO=<ID=LENRANGE,Number=2,Type=Integer,Description=\"Smallest and largest length of the supporting ops\">\n";
+        if (gts)
+            head += "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
+                    "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: the smaller PL of the other two genotypes, at most 99\">\n"
+                    "##FORMAT=<ID=DR,Number=1,Type=Integer,Description=\"Spanning reads without a supporting op\">\n"
+                    "##FORMAT=<ID=DV,Number=1,Type=Integer,Description=\"Spanning reads' supporting ops\">\n"
+                    "##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"Phred-scaled genotype likelihoods, rounded\">\n";
+        head += "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO";
+        if (gts) head += std::string("\tFORMAT\t") + (sample && sample[0] ? sample : "SAMPLE");
+        head += '\n';
     }
     size_t tot = head.size();
     for (auto &p : part) tot += p.size();

@@ -13,9 +13,10 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import (CALL_DTYPE, EVIDENCE_DTYPE, LOCUS_DTYPE, POA_RESULT_DTYPE, RESULT_DTYPE, STATUS_NAMES, SVT_DEL,
-                   SVT_EINVAL, SVT_INS, SW_QUERY_DTYPE, SW_WINDOW_DTYPE, SvtCallParams, SvtCallStats, SvtInsseqView,
-                   SvtLoadStats, SvtParams, SvtPoaParams, SvtWork, has_call, has_evidence, load_engine, ptr)
+from ._lib import (CALL_DTYPE, EVIDENCE_DTYPE, GT_DTYPE, GT_SITE_DTYPE, LOCUS_DTYPE, POA_RESULT_DTYPE, RESULT_DTYPE,
+                   STATUS_NAMES, SVT_DEL, SVT_EINVAL, SVT_INS, SVT_NA, SW_QUERY_DTYPE, SW_WINDOW_DTYPE, SvtCallParams,
+                   SvtCallStats, SvtGtParams, SvtInsseqView, SvtLoadStats, SvtParams, SvtPoaParams, SvtWork, has_call,
+                   has_evidence, has_genotype, load_engine, ptr)
 from .pileup import Pileup
 
 # params.h:27-32
@@ -172,6 +173,49 @@ class Engine:
         self._check(self.lib.svt_call_stats_get(self._h, C.byref(st)))
         return {k: (float(getattr(st, k)) if k == "scan_ms" else int(getattr(st, k))) for k, _ in SvtCallStats._fields_}
 
+    # ---- genotypes (include/svtrek_genotype.h): alt / ref / spanning reads and GT, GQ, PL per site
+    def gt_params(self, flank: int | None = None, costs=None) -> SvtGtParams:
+        """svt_genotype_default_params with `flank` and `costs` = (ref_cost, alt_cost), three
+        milli-phred values each (gt_costs(err) makes them), where given."""
+        if not has_genotype(self.lib):
+            raise SvtError(SVT_EINVAL, "this backend does not export svt_genotype_batch (include/svtrek_genotype.h): "
+                                       "genotypes need the HIP engine")
+        p = SvtGtParams()
+        self.lib.svt_genotype_default_params(self._h, C.byref(p))
+        if flank is not None:
+            p.flank = int(flank)
+        if costs is not None:
+            ref_cost, alt_cost = costs
+            for g in range(3):
+                p.ref_cost[g], p.alt_cost[g] = int(ref_cost[g]), int(alt_cost[g])
+        return p
+
+    def genotype(self, sites: np.ndarray, flank: int | None = None, costs=None) -> np.ndarray:
+        """GT_DTYPE records of GT_SITE_DTYPE sites (svt_genotype_batch); calls_to_sites and
+        sites_from_loci make sites."""
+        p = self.gt_params(flank, costs)
+        sites = np.ascontiguousarray(sites, dtype=GT_SITE_DTYPE)
+        out = np.empty(len(sites), dtype=GT_DTYPE)
+        self._check(self.lib.svt_genotype_batch(self._h, C.byref(p), ptr(sites) if len(sites) else None, len(sites),
+                                                ptr(out) if len(sites) else None))
+        return out
+
+    def genotype_device(self, d_sites: int, n: int, d_out: int, flank: int | None = None, costs=None,
+                        stream: int | None = None) -> None:
+        """svt_genotype_device on device pointers: n GT_SITE_DTYPE sites in, n GT_DTYPE records out."""
+        p = self.gt_params(flank, costs)
+        self._check(self.lib.svt_genotype_device(self._h, C.byref(p), C.c_void_p(d_sites), n, C.c_void_p(d_out),
+                                                 C.c_void_p(stream or 0)))
+
+    def genotype_calls(self, flank: int | None = None, costs=None) -> np.ndarray:
+        """GT_DTYPE records of the last call()'s calls, genotyped where they lie on the device
+        (svt_genotype_calls); record k belongs to call k."""
+        p = self.gt_params(flank, costs)
+        n = self.call_device()[1]
+        out = np.empty(n, dtype=GT_DTYPE)
+        self._check(self.lib.svt_genotype_calls(self._h, C.byref(p), ptr(out) if n else None, n))
+        return out
+
     def reindex(self, stream: int | None = None) -> None:
         """Rebuild the device index of the loaded pileup on a hipStream_t handle (svt_reindex:
         asynchronous, no host work, results unchanged)."""
@@ -311,6 +355,55 @@ def calls_to_loci(calls: np.ndarray) -> np.ndarray:
     for f in ("type", "chrom", "pos", "end"):
         loci[f] = calls[f]
     return loci
+
+
+def calls_to_sites(calls: np.ndarray) -> np.ndarray:
+    """CALL_DTYPE records as GT_SITE_DTYPE sites: the fields of the same names."""
+    calls = np.asarray(calls, dtype=CALL_DTYPE)
+    sites = np.empty(len(calls), dtype=GT_SITE_DTYPE)
+    for f in GT_SITE_DTYPE.names:
+        sites[f] = calls[f]
+    return sites
+
+
+def sites_from_loci(loci: np.ndarray, refined: np.ndarray, radius: int = 10, len_tol: int | None = None) -> np.ndarray:
+    """GT_SITE_DTYPE sites of an audited VCF's loci and their refined results.  The site spans
+    [refined start, refined end] (INS: [start, start + 1]) and takes the items starting within
+    `radius` of the refined start; a DEL's of a length within `len_tol` of end - start - 1 (any
+    length when len_tol is None), an INS's of any length.  A locus of another type, or one whose
+    refined start (DEL: or end) is NA, becomes an invalid site (type 0)."""
+    loci = np.asarray(loci, dtype=LOCUS_DTYPE)
+    refined = np.asarray(refined)
+    if len(refined) != len(loci):
+        raise ValueError(f"sites_from_loci: {len(loci)} loci but {len(refined)} refined results")
+    start, end = refined["start"].astype(np.int64), refined["end"].astype(np.int64)
+    is_del, is_ins = loci["type"] == SVT_DEL, loci["type"] == SVT_INS
+    ok = (start != SVT_NA) & (is_ins | (is_del & (end != SVT_NA) & (end > start)))
+    sites = np.zeros(len(loci), dtype=GT_SITE_DTYPE)
+    sites["type"] = np.where(ok, loci["type"], 0)
+    sites["chrom"] = loci["chrom"]
+    sites["pos"] = np.where(ok, start, 0)
+    sites["end"] = np.where(ok, np.where(is_del, end, start + 1), 0)
+    sites["x_lo"] = np.where(ok, np.maximum(start - radius, 0), 1)   # (invalid besides: x_lo > x_hi)
+    sites["x_hi"] = np.where(ok, start + radius, 0)
+    dlen = end - start - 1
+    if len_tol is None:
+        lo, hi = np.zeros(len(loci), dtype=np.int64), np.full(len(loci), 0xFFFFFFFF, dtype=np.int64)
+    else:
+        lo, hi = np.maximum(dlen - len_tol, 0), np.minimum(dlen + len_tol, 0xFFFFFFFF)
+    sites["len_lo"] = np.where(ok & is_del, lo, 0)
+    sites["len_hi"] = np.where(ok & is_del, hi, 0xFFFFFFFF)
+    return sites
+
+
+def gt_costs(err: float = 0.05):
+    """(ref_cost, alt_cost) of a per-read error rate: round(-10000 * log10 p) milli-phred per read under
+    0/0, 0/1, 1/1, p = 1 - err, 0.5, err for a ref read and the reverse for an alt read."""
+    import math
+    if not 0.0 < err < 1.0:
+        raise ValueError("gt_costs: err must lie in (0, 1)")
+    ref = tuple(int(round(-10000.0 * math.log10(p))) for p in (1.0 - err, 0.5, err))
+    return ref, ref[::-1]
 
 
 def version() -> str:

@@ -46,6 +46,9 @@ def load_host() -> C.CDLL:
         L.svth_format_evidence.restype = P
         L.svth_format_calls.argtypes = [P, C.c_size_t, P, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
         L.svth_format_calls.restype = P
+        L.svth_format_calls_gt.argtypes = [P, P, C.c_size_t, P, C.c_size_t, C.c_char_p, C.c_int, C.c_int,
+                                           C.POINTER(C.c_size_t)]
+        L.svth_format_calls_gt.restype = P
         L.svth_free.argtypes = [P]
         L.svth_free.restype = None
         L.svth_bam_free.argtypes = [P]
@@ -262,19 +265,26 @@ def format_evidence(loci: np.ndarray, res: np.ndarray, ev: np.ndarray, header: b
         L.svth_free(p)
 
 
-def format_calls(calls: np.ndarray, names, header: bool = True, threads: int = 4) -> str:
-    """`svtrek call`'s VCF text of CALL_DTYPE records (svth_format_calls); names: the BAM's reference
-    names, names[chrom - 1] is a call's CHROM."""
-    from ._lib import CALL_DTYPE
+def format_calls(calls: np.ndarray, names, genotypes: np.ndarray | None = None, sample: str = "SAMPLE",
+                 header: bool = True, threads: int = 4) -> str:
+    """`svtrek call`'s VCF text of CALL_DTYPE records (svth_format_calls_gt); names: the BAM's reference
+    names, names[chrom - 1] is a call's CHROM.  genotypes: one GT_DTYPE record per call
+    (`svtrek call --genotype`: FORMAT and a column named `sample`), or None for the sites-only VCF."""
+    from ._lib import CALL_DTYPE, GT_DTYPE
     L = load_host()
     calls = np.ascontiguousarray(calls, dtype=CALL_DTYPE)
     enc = [str(x).encode() for x in names]
     arr = (C.c_char_p * max(len(enc), 1))(*enc)
+    gts = None
+    if genotypes is not None:
+        if len(genotypes) != len(calls):
+            raise ValueError(f"format_calls: {len(calls)} calls but {len(genotypes)} genotypes")
+        gts = np.ascontiguousarray(genotypes, dtype=GT_DTYPE) if len(calls) else np.zeros(1, dtype=GT_DTYPE)
     n = C.c_size_t(0)
-    p = L.svth_format_calls(calls.ctypes.data if len(calls) else None, len(calls), arr, len(enc), int(header), threads,
-                            C.byref(n))
+    p = L.svth_format_calls_gt(calls.ctypes.data if len(calls) else None, None if gts is None else gts.ctypes.data,
+                               len(calls), arr, len(enc), str(sample).encode(), int(header), threads, C.byref(n))
     if not p:
-        raise MemoryError("svth_format_calls failed")
+        raise MemoryError("svth_format_calls_gt failed")
     try:
         return C.string_at(p, n.value).decode("latin-1")
     finally:
