@@ -25,18 +25,35 @@
  * Calls are ordered by (chrom, pos, type code).  Nothing depends on the order of the events inside
  * a bucket (it differs from rebuild to rebuild): a scan of the same pileup gives the same records.
  *
- * LIMITATION: items are clustered by their start alone.  Two deletions of different length at one
- * start become ONE call, whose len is their mean; len_lo / len_hi show it.  Splitting by length is
- * out of scope; svtrek_genotype.h genotypes the calls (or any site with a length range of its own).
+ * SPLITTING BY LENGTH (svt_call_params.len_permille = P).  With P = 0, the default, items are
+ * clustered by their start alone: two deletions of different length at one start become ONE call,
+ * whose len is their mean (len_lo / len_hi show it).  With P in 1 .. 1000 the start clusters are
+ * formed exactly as above and each is then cut into ALLELE GROUPS: its items are sorted by len, and
+ * between sorted neighbours lo <= hi there is a cut iff hi - lo > max(link, lo * P / 1000) (integer
+ * division, 64-bit product).  A group is a maximal run without a cut -- single linkage: lengths
+ * 300, 320, 340, 360 at P = 100 stay one group.  A group of c >= min_support items is a call, and
+ * its record is the record above computed over the group's items only (support = c, the same
+ * rounded means, the group's own x_lo / x_hi / len_lo / len_hi, depth at the group's pos).
+ * min_support applies per group: a start cluster of 5 items cut 3 + 2 at min_support = 3 gives one
+ * call, cut 2 + 2 + 1 none.  Calls are then ordered by (chrom, pos, type code, len): the groups of one
+ * start cluster have disjoint len ranges more than link apart, so their rounded mean len differ and
+ * still no two calls compare equal; they may come in any order of pos, equal pos included, while
+ * groups of different start clusters keep the clusters' order.  stats.clusters still counts the start
+ * clusters, stats.calls the calls.  svt_call_split_stats describes the split: a start cluster is a
+ * CANDIDATE iff it has >= min_support items and len_hi - len_lo > max(link, len_lo * P / 1000) -- no
+ * other cluster can contain a cut (the gap allowed does not decrease with lo) or give a call from a
+ * part.  After a scan with P = 0 every field is zero, and such a scan launches, allocates and reads
+ * back exactly what it did before the split existed, whatever was scanned before it.
  *
  * Status codes: svt_call_scan is SVT_ESTATE before svt_load_pileup and when the value buckets are
  * not built (SVTREK_INDEX=lists, or a pileup too large for them); SVT_EINVAL on NULL arguments,
- * link < 0, link > 2^20, min_support < 1, or no known type bit.  svt_call_fetch is SVT_EINVAL for a
+ * link < 0, link > 2^20, min_support < 1, len_permille > 1000, or no known type bit.  svt_call_fetch is SVT_EINVAL for a
  * range past the scanned count (n == 0 is SVT_OK).  svt_call_scan is ordered after every launch the
  * context has issued (svt_reindex included), selects / restores the device as the other entry
  * points do, acts on the first device of an svt_open_multi context, synchronises, and must not be
  * captured into a HIP graph.  Its scratch is allocated by the first scan: a context that never
- * scans pays nothing.
+ * scans pays nothing.  The scratch of the split is allocated by the first scan with
+ * len_permille > 0 and freed with the pileup, like the rest.
  */
 #ifndef SVTREK_CALL_H
 #define SVTREK_CALL_H
@@ -54,7 +71,8 @@ typedef struct svt_call {            /* 48 B */
 
 typedef struct svt_call_params {
     int32_t link, min_support;
-    uint32_t types, pad;             /* bit SVT_INS | bit SVT_DEL: (1u << SVT_INS) | (1u << SVT_DEL) */
+    uint32_t types;                  /* bit SVT_INS | bit SVT_DEL: (1u << SVT_INS) | (1u << SVT_DEL) */
+    uint32_t len_permille;           /* 0: clusters by start alone; 1 .. 1000: split by length (above) */
 } svt_call_params;
 
 typedef struct svt_call_stats {
@@ -65,7 +83,14 @@ typedef struct svt_call_stats {
     double scan_ms;                  /* HIP-event time around the scan's device work */
 } svt_call_stats;
 
-/* link 10, min_support = the context's consensus_min_count (at least 1), both types */
+typedef struct svt_call_split_stats {   /* all zero after a scan with len_permille = 0 */
+    uint64_t candidates;             /* start clusters that could hold a cut (above) */
+    uint64_t split;                  /* candidates cut into more than one group */
+    uint64_t groups;                 /* groups of all candidates, at any support */
+    uint64_t big;                    /* candidates of more items than the tile sort holds (sorted in device memory) */
+} svt_call_split_stats;
+
+/* link 10, min_support = the context's consensus_min_count (at least 1), both types, len_permille 0 */
 void svt_call_default_params(const svt_ctx *ctx, svt_call_params *out);
 
 /* Synchronous; the calls stay on the device. */
@@ -78,6 +103,9 @@ svt_status svt_call_fetch(svt_ctx *ctx, uint64_t first, uint64_t n, svt_call *ou
 svt_status svt_call_device(svt_ctx *ctx, const svt_call **d_calls, uint64_t *n);
 
 svt_status svt_call_stats_get(const svt_ctx *ctx, svt_call_stats *out);
+
+/* The last scan's split by length. */
+svt_status svt_call_split_stats_get(const svt_ctx *ctx, svt_call_split_stats *out);
 
 #ifdef __cplusplus
 }

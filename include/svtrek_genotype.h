@@ -17,8 +17,13 @@
  *   ref       span - alt, saturating at 0
  * A read with two matching items counts twice in alt (only possible for ranges wider than 50; ref
  * then saturates).  A spanning read that carries an op outside the site's length range counts as
- * ref: calls are not split by length (svtrek_call.h's LIMITATION), so two alleles at one start are
- * told apart only by the length range the caller passes.
+ * ref: two alleles at one start are told apart by the site's length range.  The calls of a scan
+ * with len_permille > 0 (svtrek_call.h, SPLITTING BY LENGTH) bring that range with them: a split
+ * call's [x_lo, x_hi] x [len_lo, len_hi] holds exactly its own items, so alt_all == support for
+ * every call, and the reads that carry a sibling allele span the site without a matching item and
+ * count as ref (DR) -- a 300 / 500 heterozygote becomes two 0/1 records.  (A joint multi-allelic
+ * genotype, 1/2, is not made.)  A call of a scan with len_permille = 0 covers every length at its
+ * start, and its genotype counts either allele as alt.
  *
  * The genotype, in integers:
  *   L[g]   = ref * ref_cost[g] + alt * alt_cost[g]   (uint64; g = 0: 0/0, 1: 0/1, 2: 1/1)

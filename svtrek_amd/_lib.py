@@ -45,7 +45,11 @@ class SvtGtParams(C.Structure):
 
 
 class SvtCallParams(C.Structure):
-    _fields_ = [("link", C.c_int32), ("min_support", C.c_int32), ("types", C.c_uint32), ("pad", C.c_uint32)]
+    _fields_ = [("link", C.c_int32), ("min_support", C.c_int32), ("types", C.c_uint32), ("len_permille", C.c_uint32)]
+
+
+class SvtCallSplitStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("candidates", "split", "groups", "big")]
 
 
 class SvtCallStats(C.Structure):
@@ -151,6 +155,8 @@ ENGINE_SYMBOLS = (
 EVIDENCE_SYMBOLS = ("svt_evidence_batch", "svt_evidence_device")
 # include/svtrek_call.h: likewise (Engine.call raises on a backend without it)
 CALL_SYMBOLS = ("svt_call_default_params", "svt_call_scan", "svt_call_fetch", "svt_call_device", "svt_call_stats_get")
+# its split statistics, added later: an engine without the getter still calls (Engine.call_split_stats raises)
+CALL_SPLIT_SYMBOLS = ("svt_call_split_stats_get",)
 # include/svtrek_genotype.h: likewise (Engine.genotype raises on a backend without it)
 GENOTYPE_SYMBOLS = ("svt_genotype_default_params", "svt_genotype_batch", "svt_genotype_device", "svt_genotype_calls")
 
@@ -252,6 +258,9 @@ def bind_abi(lib: C.CDLL) -> C.CDLL:
         lib.svt_call_stats_get.argtypes = [P, C.POINTER(SvtCallStats)]
         for name in CALL_SYMBOLS[1:]:
             getattr(lib, name).restype = C.c_int32
+    if has_call_split(lib):
+        lib.svt_call_split_stats_get.argtypes = [P, C.POINTER(SvtCallSplitStats)]
+        lib.svt_call_split_stats_get.restype = C.c_int32
     if has_genotype(lib):
         lib.svt_genotype_default_params.argtypes = [P, C.POINTER(SvtGtParams)]
         lib.svt_genotype_default_params.restype = None
@@ -266,6 +275,11 @@ def bind_abi(lib: C.CDLL) -> C.CDLL:
 def has_genotype(lib: C.CDLL) -> bool:
     """Does the library export include/svtrek_genotype.h's entry points?"""
     return all(hasattr(lib, name) for name in GENOTYPE_SYMBOLS)
+
+
+def has_call_split(lib: C.CDLL) -> bool:
+    """Does the library export svt_call_split_stats_get (svt_call_params.len_permille)?"""
+    return has_call(lib) and all(hasattr(lib, name) for name in CALL_SPLIT_SYMBOLS)
 
 
 def has_call(lib: C.CDLL) -> bool:

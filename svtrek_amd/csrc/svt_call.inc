@@ -33,6 +33,9 @@
 //              as it comes, into (chrom, pos, type) order -- a binary search per call.
 // No two calls compare equal (clusters of one type and contig have disjoint x ranges, so their
 // rounded means differ), and no step depends on the order of the events inside a bucket.
+//   split      (len_permille > 0 only: the kernels at the end of this file, between accum and pick)
+//              the clusters that can hold a cut by length are sorted by len and cut into groups, one
+//              call per group of >= min_support items, in (chrom, pos, type, len) order.
 constexpr uint32_t CALL_H = 1024, CALL_TILE = 2 * CALL_H;
 constexpr int CALL_T = 256;                       // threads of the per-segment kernels
 constexpr uint64_t CALL_NONE = ~0ull;             // the sentinel key
@@ -59,6 +62,8 @@ struct CallArgs {
     uint32_t *pick_n;
     unsigned long long *stats;    // events, skipped, big buckets
     uint32_t link, min_support, types;
+    uint32_t permille;            // svt_call_params.len_permille
+    uint32_t *first;              // [clusters] every cluster's first key slot; NULL unless the scan splits by length
 };
 
 // The contig of bucket g (cbase is ascending, cbase[0] == 0).
@@ -263,7 +268,10 @@ __global__ __launch_bounds__(CALL_T) void call_accum_kernel(CallArgs a) {
         if (key == CALL_NONE || c == 0u) continue;   // (c >= 1: a valid key is a head or follows one)
         const uint32_t x = (uint32_t)(key >> 28), len = (uint32_t)key & 0xfffffffu;
         CallAcc *q = a.acc + (c - 1u);
-        if (c != (p ? a.cid[p - 1] : 0u)) q->seg = s.sg;
+        if (c != (p ? a.cid[p - 1] : 0u)) {
+            q->seg = s.sg;
+            if (a.first) a.first[c - 1u] = p;
+        }
         atomicAdd(&q->cnt, 1u);
         atomicAdd(&q->sx, (unsigned long long)x);
         atomicAdd(&q->slen, (unsigned long long)len);
@@ -327,4 +335,173 @@ __global__ __launch_bounds__(256) void call_merge_kernel(const svt_call *in, uin
     dst[0] = src[0];
     dst[1] = src[1];
     dst[2] = src[2];
+}
+
+// ---- splitting the start clusters by length (svt_call_params.len_permille = P > 0) ----------------
+// Between call_accum_kernel and call_pick_kernel.  A cluster whose own len range cannot hold a cut,
+// or with fewer than min_support items, stays as it is; the others are the CANDIDATES:
+//   cand       (call_cand_kernel + one select + one sum) the candidates from their CallAcc records,
+//              their item counts summed into the offsets of a scratch for their sorted keys.
+//   split      (call_split_kernel, one workgroup per candidate) the candidate's items are the valid
+//              keys of its cluster number from its first slot on (the sentinels of the segments it
+//              runs over are skipped), gathered as len << 30 | x and sorted by call_bitonic -- in LDS
+//              up to CALL_TILE keys, else in the scratch itself.  A key whose len is more than
+//              max(link, lo * P / 1000) past its left neighbour's heads a GROUP; the groups are counted.
+//   units      every cluster is 1 unit, a candidate as many as it has groups; an inclusive sum over
+//              the clusters numbers the units in cluster order.
+//   group      (call_group_kernel, one workgroup per candidate) a segmented reduction over the sorted
+//              keys: a thread keeps the sums of the group it is in and adds them to the group's
+//              record when its next key belongs to another group -- a candidate of two alleles costs
+//              a few atomics a thread, whatever its size.
+//   order      (call_order_kernel, one workgroup per candidate) the groups come in len order; their
+//              keys pos << 32 | group go through the same network and the records to the candidate's
+//              units in (pos, len) order.  call_unit_kernel copies the other clusters' records.
+// call_pick_kernel, call_emit_kernel and call_merge_kernel then run on the units as they do on the
+// clusters: units of different clusters keep the clusters' order, so both lists are in (chrom, pos,
+// len) order and the merge gives (chrom, pos, type, len).  Groups of one cluster have disjoint len
+// ranges more than link apart, so their rounded mean len differ: no two calls compare equal.
+struct CallSplit {
+    const uint8_t *cflag;         // [clusters] 1: a candidate
+    const uint32_t *cand;         // the candidates in cluster order (one workgroup each)
+    const uint32_t *kend;         // [clusters] inclusive sum of the candidates' item counts: where a candidate's sorted keys end
+    unsigned long long *skeys;    // the candidates' keys len << 30 | x, sorted; then call_order_kernel's scratch
+    uint32_t *unit;               // [clusters] units of every cluster, then their inclusive sum
+    CallAcc *gacc;                // [units] a candidate's groups in len order at its units (zeroed)
+    CallAcc *uacc;                // [units] every unit's record, a candidate's in (pos, len) order
+    unsigned long long *stats;    // split, groups, big
+    uint32_t n_keys;              // key slots (n_s + n_i)
+};
+
+// Is there a cut between the sorted neighbours lo <= hi?  (lo < 2^28 and P <= 1000: the quotient fits.)
+__device__ __forceinline__ bool call_len_cut(uint32_t lo, uint32_t hi, uint32_t link, uint32_t permille) {
+    const uint32_t rel = (uint32_t)((unsigned long long)lo * permille / 1000u);
+    return hi - lo > max(link, rel);
+}
+
+__global__ __launch_bounds__(256) void call_cand_kernel(CallArgs a, uint32_t n_clusters, uint8_t *cflag, uint32_t *kcnt,
+                                                        uint32_t *unit) {
+    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+    if (c >= n_clusters) return;
+    const CallAcc *q = a.acc + c;
+    const uint32_t cnt = q->cnt;
+    const bool cand = cnt >= a.min_support && call_len_cut(~q->nlen_lo, q->len_hi, a.link, a.permille);
+    cflag[c] = cand ? 1 : 0;
+    kcnt[c] = cand ? cnt : 0u;
+    unit[c] = 1u;
+}
+
+__global__ __launch_bounds__(CALL_T) void call_split_kernel(CallArgs a, CallSplit sp) {
+    __shared__ unsigned long long lk[CALL_TILE];
+    __shared__ uint32_t got, ng;
+    const uint32_t c = sp.cand[blockIdx.x], cnt = a.acc[c].cnt, off = sp.kend[c] - cnt;
+    const bool big = cnt > CALL_TILE;
+    unsigned long long *k = big ? sp.skeys + off : lk;
+    if (threadIdx.x == 0) got = 0, ng = 0;
+    __syncthreads();
+    const int ln = lane_id();
+    for (uint32_t base = a.first[c]; base < sp.n_keys; base += CALL_T) {   // (ends at cnt keys: the cluster has them)
+        const uint32_t p = base + threadIdx.x;
+        unsigned long long key = CALL_NONE;
+        if (p < sp.n_keys && a.cid[p] == c + 1u) key = a.keys[p];
+        const uint64_t m = ballot(key != CALL_NONE);
+        uint32_t at = 0;
+        if (m && ln == 0) at = atomicAdd(&got, (uint32_t)__popcll(m));
+        at = rdlane(at, 0) + (uint32_t)__popcll(m & ((1ull << ln) - 1ull));
+        if (key != CALL_NONE && at < cnt) k[at] = (key & 0xfffffffull) << 30 | key >> 28;
+        __syncthreads();
+        const uint32_t have = got;
+        __syncthreads();
+        if (have >= cnt) break;
+    }
+    call_bitonic(k, cnt);
+    uint32_t heads = 0;
+    for (uint32_t i = threadIdx.x; i < cnt; i += CALL_T) {
+        const unsigned long long key = k[i];
+        heads += i == 0 || call_len_cut((uint32_t)(k[i - 1] >> 30), (uint32_t)(key >> 30), a.link, a.permille) ? 1u : 0u;
+        if (!big) sp.skeys[off + i] = key;
+    }
+    if (heads) atomicAdd(&ng, heads);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        sp.unit[c] = ng;
+        if (ng > 1) atomicAdd(&sp.stats[0], 1ull);
+        atomicAdd(&sp.stats[1], (unsigned long long)ng);
+        if (big) atomicAdd(&sp.stats[2], 1ull);
+    }
+}
+
+__global__ __launch_bounds__(CALL_T) void call_group_kernel(CallArgs a, CallSplit sp) {
+    __shared__ uint32_t wsum[CALL_T / WAVE];
+    const uint32_t c = sp.cand[blockIdx.x], cnt = a.acc[c].cnt, seg = a.acc[c].seg;
+    const unsigned long long *k = sp.skeys + (sp.kend[c] - cnt);
+    CallAcc *g = sp.gacc + (c ? sp.unit[c - 1] : 0u);
+    const int ln = lane_id(), w = threadIdx.x / WAVE;
+    uint32_t carry = 0;                                   // groups before this round's keys
+    uint32_t mine = 0, n = 0, len_lo = 0, len_hi = 0, x_lo = 0, x_hi = 0;   // the group this thread is in, its sums so far
+    unsigned long long sx = 0, slen = 0;
+    auto flush = [&]() {
+        if (n == 0) return;
+        CallAcc *q = g + mine;
+        atomicAdd(&q->cnt, n);
+        atomicAdd(&q->sx, sx);
+        atomicAdd(&q->slen, slen);
+        atomicMax(&q->nlen_lo, ~len_lo);
+        atomicMax(&q->len_hi, len_hi);
+        atomicMax(&q->nx_lo, ~x_lo);
+        atomicMax(&q->x_hi, x_hi);
+        n = 0, sx = 0, slen = 0;
+    };
+    for (uint32_t base = 0; base < cnt; base += CALL_T) {
+        const uint32_t i = base + threadIdx.x;
+        const bool in = i < cnt;
+        const unsigned long long key = in ? k[i] : 0ull;
+        const uint32_t len = (uint32_t)(key >> 30), x = (uint32_t)key & 0x3fffffffu;
+        const bool head = in && (i == 0 || call_len_cut((uint32_t)(k[i - 1] >> 30), len, a.link, a.permille));
+        const uint64_t m = ballot(head);
+        if (ln == 0) wsum[w] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t before = carry;
+        for (int v = 0; v < CALL_T / WAVE; v++) {
+            const uint32_t t = wsum[v];
+            carry += t;
+            before += v < w ? t : 0u;
+        }
+        __syncthreads();
+        if (!in) continue;   // (every round but the last is full, and the last ends the loop)
+        const uint32_t gi = before + (uint32_t)__popcll(m & ((2ull << ln) - 1ull)) - 1u;   // (key 0 is a head)
+        if (n == 0 || gi != mine) {
+            flush();
+            mine = gi, len_lo = len, x_lo = x_hi = x;
+        }
+        n++, sx += x, slen += len;
+        len_hi = len;                                     // (the keys ascend by len)
+        x_lo = min(x_lo, x), x_hi = max(x_hi, x);
+        if (head) g[gi].seg = seg;
+    }
+    flush();
+}
+
+__global__ __launch_bounds__(256) void call_unit_kernel(CallArgs a, CallSplit sp, uint32_t n_clusters) {
+    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+    if (c >= n_clusters || sp.cflag[c]) return;
+    sp.uacc[c ? sp.unit[c - 1] : 0u] = a.acc[c];
+}
+
+__global__ __launch_bounds__(CALL_T) void call_order_kernel(CallArgs a, CallSplit sp) {
+    __shared__ unsigned long long lk[CALL_TILE];
+    const uint32_t c = sp.cand[blockIdx.x], ub = c ? sp.unit[c - 1] : 0u, ng = sp.unit[c] - ub;
+    const CallAcc *g = sp.gacc + ub;
+    CallAcc *u = sp.uacc + ub;
+    if (ng == 1) {
+        if (threadIdx.x == 0) u[0] = g[0];
+        return;
+    }
+    unsigned long long *k = ng > CALL_TILE ? sp.skeys + (sp.kend[c] - a.acc[c].cnt) : lk;   // (ng <= cnt keys: the sorted keys are spent)
+    for (uint32_t i = threadIdx.x; i < ng; i += CALL_T) {
+        const unsigned long long n = g[i].cnt;
+        k[i] = (g[i].sx + n / 2) / n << 32 | i;
+    }
+    __syncthreads();
+    call_bitonic(k, ng);
+    for (uint32_t i = threadIdx.x; i < ng; i += CALL_T) u[i] = g[(uint32_t)k[i]];
 }

@@ -40,11 +40,75 @@ svt_status call_prepare(svt_ctx *c) {
     return SVT_OK;
 }
 
+// The split by length of a scan with len_permille > 0 (svt_call.inc), after call_accum_kernel: the
+// units' records into k.d_uacc in the order the calls take, their number and that of array S's into
+// *nu / *nu_s.  Its scratch is allocated here, by the first such scan, and freed with the pileup.
+svt_status call_split_1(svt_ctx *c, const CallArgs &a, uint32_t ncl, uint32_t ncl_s, uint32_t *nu, uint32_t *nu_s) {
+    CallScratch &k = c->call;
+    svt_status s;
+    if ((s = nomem(c, k.d_cflag.reserve(ncl), CALL_MEM)) || (s = nomem(c, k.d_cand.reserve(ncl), CALL_MEM)) ||
+        (s = nomem(c, k.d_kend.reserve(ncl), CALL_MEM)) || (s = nomem(c, k.d_unit.reserve(ncl), CALL_MEM)) ||
+        (s = nomem(c, k.d_sctr.reserve(4), CALL_MEM)))
+        return s;
+    uint32_t *d_ncand = reinterpret_cast<uint32_t *>(k.d_sctr + 3);
+    hipcub::CountingInputIterator<uint32_t> it(0);
+    size_t t1 = 0, t2 = 0;
+    HIP_TRY(c, hipcub::DeviceSelect::Flagged(nullptr, t1, it, k.d_cflag.get(), k.d_cand.get(), d_ncand, (int)ncl, nullptr));
+    HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(nullptr, t2, k.d_kend.get(), k.d_kend.get(), (int)ncl, nullptr));
+    if ((s = nomem(c, k.d_tmp.reserve(std::max(t1, t2)), CALL_MEM))) return s;
+    HIP_TRY(c, hipMemsetAsync(k.d_sctr, 0, 4 * sizeof(unsigned long long), nullptr));
+    const dim3 cg((ncl + 255u) / 256u), cb(256);
+    hipLaunchKernelGGL(call_cand_kernel, cg, cb, 0, nullptr, a, ncl, k.d_cflag, k.d_kend, k.d_unit);
+    size_t tb = k.d_tmp.cap();
+    HIP_TRY(c, hipcub::DeviceSelect::Flagged(k.d_tmp.get(), tb, it, k.d_cflag.get(), k.d_cand.get(), d_ncand, (int)ncl, nullptr));
+    tb = k.d_tmp.cap();
+    HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(k.d_tmp.get(), tb, k.d_kend.get(), k.d_kend.get(), (int)ncl, nullptr));
+    HIP_TRY(c, hipGetLastError());
+    uint32_t ncand = 0, nkeys = 0;   // candidates; their items (at most the events: 32 bits hold them)
+    HIP_TRY(c, hipMemcpy(&ncand, d_ncand, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(&nkeys, k.d_kend + (ncl - 1), 4, hipMemcpyDeviceToHost));
+    CallSplit sp{};
+    sp.cflag = k.d_cflag;
+    sp.cand = k.d_cand;
+    sp.kend = k.d_kend;
+    sp.unit = k.d_unit;
+    sp.stats = k.d_sctr;
+    sp.n_keys = (uint32_t)(c->bk_events[BA_S] + c->bk_events[BA_I]);
+    const dim3 sg(ncand), sb(CALL_T);
+    if (ncand) {
+        if ((s = nomem(c, k.d_skeys.reserve(nkeys), CALL_MEM))) return s;
+        sp.skeys = k.d_skeys;
+        hipLaunchKernelGGL(call_split_kernel, sg, sb, 0, nullptr, a, sp);
+    }
+    tb = k.d_tmp.cap();
+    HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(k.d_tmp.get(), tb, k.d_unit.get(), k.d_unit.get(), (int)ncl, nullptr));
+    HIP_TRY(c, hipGetLastError());
+    *nu = *nu_s = 0;
+    HIP_TRY(c, hipMemcpy(nu, k.d_unit + (ncl - 1), 4, hipMemcpyDeviceToHost));
+    if (ncl_s) HIP_TRY(c, hipMemcpy(nu_s, k.d_unit + (ncl_s - 1), 4, hipMemcpyDeviceToHost));
+    if (*nu < ncl || *nu >= 0x7fffffffu)   // (at most one unit an item)
+        return fail(c, SVT_ESTATE, "%s", "svt_call_scan: the split's unit count is out of range");
+    if ((s = nomem(c, k.d_uacc.reserve(*nu), CALL_MEM))) return s;
+    sp.uacc = k.d_uacc;
+    if (ncand) {
+        if ((s = nomem(c, k.d_gacc.reserve(*nu), CALL_MEM))) return s;
+        sp.gacc = k.d_gacc;
+        HIP_TRY(c, hipMemsetAsync(k.d_gacc, 0, (size_t)*nu * sizeof(CallAcc), nullptr));
+        hipLaunchKernelGGL(call_group_kernel, sg, sb, 0, nullptr, a, sp);
+    }
+    hipLaunchKernelGGL(call_unit_kernel, cg, cb, 0, nullptr, a, sp, ncl);
+    if (ncand) hipLaunchKernelGGL(call_order_kernel, sg, sb, 0, nullptr, a, sp);
+    HIP_TRY(c, hipGetLastError());
+    k.split.candidates = ncand;
+    return SVT_OK;
+}
+
 svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) {
     CallScratch &k = c->call;
     k.n_calls = 0;
     k.scanned = true;
     k.stats = svt_call_stats{};
+    k.split = svt_call_split_stats{};
     const uint64_t N = c->bk_events[BA_S] + c->bk_events[BA_I];
     if (c->n_reads == 0 || N == 0) {
         *n_calls = 0;
@@ -74,6 +138,7 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
     a.link = (uint32_t)p->link;
     a.min_support = (uint32_t)p->min_support;
     a.types = p->types;
+    a.permille = p->len_permille;
     const dim3 sg((unsigned)k.n_seg), sb(CALL_T);
     HIP_TRY(c, hipMemsetAsync(k.d_ctr, 0, 8 * sizeof(uint32_t), nullptr));
     hipLaunchKernelGGL(call_sort_kernel, sg, sb, 0, nullptr, a);
@@ -95,14 +160,27 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
         if ((s = nomem(c, k.d_acc.reserve(ncl), CALL_MEM)) || (s = nomem(c, k.d_pick.reserve(ncl), CALL_MEM)) ||
             (s = nomem(c, k.d_flag.reserve(ncl), CALL_MEM)) || (s = nomem(c, k.d_tmp.reserve(need), CALL_MEM)))
             return s;
+        if (a.permille && (s = nomem(c, k.d_first.reserve(ncl), CALL_MEM))) return s;
         a.acc = k.d_acc;
         a.pick = k.d_pick;
+        a.first = a.permille ? k.d_first.get() : nullptr;
         HIP_TRY(c, hipMemsetAsync(k.d_acc, 0, (size_t)ncl * sizeof(CallAcc), nullptr));
         hipLaunchKernelGGL(call_accum_kernel, sg, sb, 0, nullptr, a);
-        hipLaunchKernelGGL(call_pick_kernel, dim3((ncl + 255u) / 256u), dim3(256), 0, nullptr, a, ncl, ncl_s, k.d_flag,
+        uint32_t nu = ncl, nu_s = ncl_s;   // what is picked from: the clusters, or the units of a split scan
+        if (a.permille) {
+            if ((s = call_split_1(c, a, ncl, ncl_s, &nu, &nu_s))) return s;
+            need = 0;
+            HIP_TRY(c, hipcub::DeviceSelect::Flagged(nullptr, need, it, k.d_flag.get(), k.d_pick.get(), k.d_ctr.get(), (int)nu, nullptr));
+            if ((s = nomem(c, k.d_pick.reserve(nu), CALL_MEM)) || (s = nomem(c, k.d_flag.reserve(nu), CALL_MEM)) ||
+                (s = nomem(c, k.d_tmp.reserve(need), CALL_MEM)))
+                return s;
+            a.acc = k.d_uacc;
+            a.pick = k.d_pick;
+        }
+        hipLaunchKernelGGL(call_pick_kernel, dim3((nu + 255u) / 256u), dim3(256), 0, nullptr, a, nu, nu_s, k.d_flag,
                            k.d_ctr + 1);
         tb = k.d_tmp.cap();
-        HIP_TRY(c, hipcub::DeviceSelect::Flagged(k.d_tmp.get(), tb, it, k.d_flag.get(), k.d_pick.get(), k.d_ctr.get(), (int)ncl, nullptr));
+        HIP_TRY(c, hipcub::DeviceSelect::Flagged(k.d_tmp.get(), tb, it, k.d_flag.get(), k.d_pick.get(), k.d_ctr.get(), (int)nu, nullptr));
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpy(picked, k.d_ctr, sizeof picked, hipMemcpyDeviceToHost));
     }
@@ -118,6 +196,13 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
     HIP_TRY(c, hipEventSynchronize(e1));
     unsigned long long st[3] = {};
     HIP_TRY(c, hipMemcpy(st, k.d_ctr + 2, sizeof st, hipMemcpyDeviceToHost));
+    if (a.permille && ncl) {
+        unsigned long long ss[3] = {};
+        HIP_TRY(c, hipMemcpy(ss, k.d_sctr, sizeof ss, hipMemcpyDeviceToHost));
+        k.split.split = ss[0];
+        k.split.groups = ss[1];
+        k.split.big = ss[2];
+    }
     float ms = 0.f;
     HIP_TRY(c, hipEventElapsedTime(&ms, e0, e1));
     k.stats.events = st[0];
@@ -139,7 +224,7 @@ void svt_call_default_params(const svt_ctx *c, svt_call_params *out) {
     out->link = 10;
     out->min_support = c ? std::max(c->prm.consensus_min_count, 1) : 3;
     out->types = (1u << SVT_INS) | (1u << SVT_DEL);
-    out->pad = 0;
+    out->len_permille = 0;
 }
 
 svt_status svt_call_scan(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) {
@@ -147,6 +232,7 @@ svt_status svt_call_scan(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls
     if (!p || !n_calls) return fail(c, SVT_EINVAL, "%s", "null params/n_calls");
     if (p->link < 0 || p->link > (1 << 20) || p->min_support < 1 || !(p->types & ((1u << SVT_INS) | (1u << SVT_DEL))))
         return fail(c, SVT_EINVAL, "%s", "svt_call_scan: link in [0, 2^20], min_support >= 1 and a type bit of DEL / INS");
+    if (p->len_permille > 1000u) return fail(c, SVT_EINVAL, "%s", "svt_call_scan: len_permille in [0, 1000]");
     if (!c->loaded) return fail(c, SVT_ESTATE, "%s", "svt_load_pileup not called");
     if (c->n_reads != 0 && !c->bk_ready)
         return fail(c, SVT_ESTATE, "%s",
@@ -178,5 +264,11 @@ svt_status svt_call_device(svt_ctx *c, const svt_call **d_calls, uint64_t *n) {
 svt_status svt_call_stats_get(const svt_ctx *c, svt_call_stats *out) {
     if (!c || !out) return SVT_EINVAL;
     *out = c->call.stats;
+    return SVT_OK;
+}
+
+svt_status svt_call_split_stats_get(const svt_ctx *c, svt_call_split_stats *out) {
+    if (!c || !out) return SVT_EINVAL;
+    *out = c->call.split;
     return SVT_OK;
 }

@@ -83,6 +83,13 @@ struct CallScratch {
     DevBuf<svt_call> d_calls, d_raw;   // in (chrom, pos, type) order / as emitted
     uint64_t n_calls = 0;
     svt_call_stats stats{};
+    // the split by length (len_permille > 0): nothing allocated before the first such scan
+    DevBuf<uint32_t> d_first, d_cand, d_kend, d_unit;   // per cluster: first key slot / candidates / their keys' ends / units
+    DevBuf<uint8_t> d_cflag;       // per cluster: a candidate
+    DevBuf<unsigned long long> d_skeys;   // the candidates' sorted keys
+    DevBuf<unsigned long long> d_sctr;    // [0..3) split / groups / big, [3] the candidates (32 bits)
+    DevBuf<CallAcc> d_gacc, d_uacc;       // per unit: the groups as accumulated / every unit in order
+    svt_call_split_stats split{};
 };
 
 // One pool of POA scratch slots (svt_poa.inc, svt_poa_host.inc).

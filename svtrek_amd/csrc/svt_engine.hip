@@ -57,7 +57,7 @@
 #include "../../include/svtrek_genotype.h"
 #include "svt_bamrec.h"
 
-#define SVT_VERSION "svtrek_amd 0.28.0 (gfx950, value-bucketed event index filed by a lane-per-read walk with a 9-B LDS stage, band + prefix-max facts, packed span walk fed by readlane, lane vote on 64 windows a wave, BGZF inflate + BAM decode, DEL/INS discovery from the value buckets, genotypes from the events' own read extents)"
+#define SVT_VERSION "svtrek_amd 0.29.0 (gfx950, value-bucketed event index filed by a lane-per-read walk with a 9-B LDS stage, band + prefix-max facts, packed span walk fed by readlane, lane vote on 64 windows a wave, BGZF inflate + BAM decode, DEL/INS discovery from the value buckets, genotypes from the events' own read extents)"
 
 namespace {
 

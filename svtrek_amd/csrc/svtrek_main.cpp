@@ -37,6 +37,7 @@ extern "C" __typeof__(svt_call_default_params) svt_call_default_params __attribu
 extern "C" __typeof__(svt_call_scan) svt_call_scan __attribute__((weak));
 extern "C" __typeof__(svt_call_fetch) svt_call_fetch __attribute__((weak));
 extern "C" __typeof__(svt_call_stats_get) svt_call_stats_get __attribute__((weak));
+extern "C" __typeof__(svt_call_split_stats_get) svt_call_split_stats_get __attribute__((weak));
 // include/svtrek_genotype.h likewise (`svtrek call --genotype`)
 extern "C" __typeof__(svt_genotype_default_params) svt_genotype_default_params __attribute__((weak));
 extern "C" __typeof__(svt_genotype_calls) svt_genotype_calls __attribute__((weak));
@@ -62,6 +63,9 @@ void call_usage() {
     printf("    --link <num>                      Largest gap between neighbouring starts of one cluster [Default: 10]\n");
     printf("    --min-support <num>               Fewest D > 50 / I >= 50 ops of a call [Default: %d]\n", MIN_COUNT);
     printf("    --types <DEL,INS>                 Types to call [Default: DEL,INS]\n");
+    printf("    --len-permille <num>              Split the calls of one start by length: a new allele where the sorted\n");
+    printf("                                      lengths step by more than max(link, num/1000 of the shorter); 0: no split\n");
+    printf("                                      [Default: 0]\n");
     printf("    --genotype                        Genotype every call: a FORMAT and a sample column with GT:GQ:DR:DV:PL\n");
     printf("                                      [Default: a sites-only VCF]\n");
     printf("    --flank <num>                     Bases a read must cover on both sides of a call to count [Default: 50]\n");
@@ -563,7 +567,7 @@ int audit(int argc, char **argv) {
 // host parse -- the ingest that keeps the reference names), svt_call_scan, the calls as VCF text.
 int call_mode(int argc, char **argv) {
     const char *bam_path = nullptr, *out_path = nullptr, *sample = "SAMPLE";
-    int threads = THREADS, verbose = 0, device = 0, gpu_inflate = -1, link = -1, min_support = -1, genotype = 0, flank = -1;
+    int threads = THREADS, verbose = 0, device = 0, gpu_inflate = -1, link = -1, min_support = -1, genotype = 0, flank = -1, len_permille = 0;
     uint32_t types = (1u << SVT_INS) | (1u << SVT_DEL);
     static const option opts[] = {
         {"bam", required_argument, nullptr, 1}, {"output", required_argument, nullptr, 3},
@@ -571,7 +575,8 @@ int call_mode(int argc, char **argv) {
         {"device", required_argument, nullptr, 21}, {"inflate", required_argument, nullptr, 25},
         {"link", required_argument, nullptr, 30}, {"min-support", required_argument, nullptr, 31},
         {"types", required_argument, nullptr, 32}, {"genotype", no_argument, nullptr, 33},
-        {"flank", required_argument, nullptr, 34}, {"sample", required_argument, nullptr, 35}, {nullptr, 0, nullptr, 0}};
+        {"flank", required_argument, nullptr, 34}, {"sample", required_argument, nullptr, 35},
+        {"len-permille", required_argument, nullptr, 36}, {nullptr, 0, nullptr, 0}};
     int opt, li;
     while ((opt = getopt_long(argc, argv, "b:o:t:h", opts, &li)) != -1) {
         switch (opt) {
@@ -606,6 +611,7 @@ int call_mode(int argc, char **argv) {
         case 33: genotype = 1; break;
         case 34: flank = atoi(optarg); if (flank < 0 || flank > (1 << 20)) { fprintf(stderr, "[ERROR] --flank must be in [0, 1048576]\n"); exit(EXIT_FAILURE); } break;
         case 35: sample = optarg; break;
+        case 36: len_permille = atoi(optarg); if (len_permille < 0 || len_permille > 1000) { fprintf(stderr, "[ERROR] --len-permille must be in [0, 1000]\n"); exit(EXIT_FAILURE); } break;
         default:
             printf("[ERROR] Option %d is invalid.\n", opt);
             call_usage();
@@ -655,6 +661,7 @@ int call_mode(int argc, char **argv) {
     if (link >= 0) cp.link = link;
     if (min_support >= 1) cp.min_support = min_support;
     cp.types = types;
+    cp.len_permille = (uint32_t)len_permille;
     uint64_t n = 0;
     svt_status s = svt_load_pileup(ctx, &view);
     const double t_load = now_s();
@@ -694,6 +701,11 @@ int call_mode(int argc, char **argv) {
                 t_ingest - t0, gpu_inflate ? "gpu inflate, host parse" : "cpu", t_load - t_ingest, t_scan - t_load, st.scan_ms,
                 now_s() - t_gt, (unsigned long long)st.events, (unsigned long long)st.skipped, (unsigned long long)st.clusters,
                 (unsigned long long)st.calls, (unsigned long long)st.big_buckets, cp.link, cp.min_support);
+    svt_call_split_stats ss{};
+    if (verbose && len_permille && svt_call_split_stats_get && !svt_call_split_stats_get(ctx, &ss))
+        fprintf(stderr, "[svtrek_amd] call: len-permille %d  candidates %llu  split %llu  groups %llu  big %llu\n", len_permille,
+                (unsigned long long)ss.candidates, (unsigned long long)ss.split, (unsigned long long)ss.groups,
+                (unsigned long long)ss.big);
     return done(0);
 }
 

@@ -15,8 +15,8 @@ import numpy as np
 
 from ._lib import (CALL_DTYPE, EVIDENCE_DTYPE, GT_DTYPE, GT_SITE_DTYPE, LOCUS_DTYPE, POA_RESULT_DTYPE, RESULT_DTYPE,
                    STATUS_NAMES, SVT_DEL, SVT_EINVAL, SVT_INS, SVT_NA, SW_QUERY_DTYPE, SW_WINDOW_DTYPE, SvtCallParams,
-                   SvtCallStats, SvtGtParams, SvtInsseqView, SvtLoadStats, SvtParams, SvtPoaParams, SvtWork, has_call,
-                   has_evidence, has_genotype, load_engine, ptr)
+                   SvtCallSplitStats, SvtCallStats, SvtGtParams, SvtInsseqView, SvtLoadStats, SvtParams, SvtPoaParams,
+                   SvtWork, has_call, has_call_split, has_evidence, has_genotype, load_engine, ptr)
 from .pileup import Pileup
 
 # params.h:27-32
@@ -136,11 +136,22 @@ class Engine:
             raise SvtError(SVT_EINVAL, "this backend does not export svt_call_scan (include/svtrek_call.h): "
                                        "discovery needs the HIP engine")
 
-    def call(self, link: int | None = None, min_support: int | None = None, types=("DEL", "INS")) -> np.ndarray:
-        """Cluster the pileup's D > 50 / I >= 50 ops by start (svt_call_scan): CALL_DTYPE records in
-        (chrom, pos, type) order.  link: the largest gap between neighbouring starts of one cluster
-        (default 10); min_support: the fewest ops of a call (default consensus_min_count)."""
+    def _need_call_split(self) -> None:
         self._need_call()
+        if not has_call_split(self.lib):
+            raise SvtError(SVT_EINVAL, "this backend does not export svt_call_split_stats_get: splitting calls by "
+                                       "length (len_permille) needs engine 0.29.0 or later")
+
+    def call(self, link: int | None = None, min_support: int | None = None, types=("DEL", "INS"),
+             len_permille: int | None = None) -> np.ndarray:
+        """Cluster the pileup's D > 50 / I >= 50 ops by start (svt_call_scan): CALL_DTYPE records in
+        (chrom, pos, type, len) order.  link: the largest gap between neighbouring starts of one
+        cluster (default 10); min_support: the fewest ops of a call (default consensus_min_count);
+        len_permille: 1 .. 1000 cuts every start cluster where its sorted lengths step by more than
+        max(link, len * len_permille / 1000), one call per allele (default 0: no split)."""
+        self._need_call()
+        if len_permille:
+            self._need_call_split()
         p = SvtCallParams()
         self.lib.svt_call_default_params(self._h, C.byref(p))
         if link is not None:
@@ -148,6 +159,10 @@ class Engine:
         if min_support is not None:
             p.min_support = int(min_support)
         p.types = call_type_bits(types)
+        if len_permille is not None:
+            if not 0 <= int(len_permille) <= 0xffffffff:
+                raise SvtError(SVT_EINVAL, "call: len_permille in [0, 1000]")
+            p.len_permille = int(len_permille)
         n = C.c_uint64(0)
         self._check(self.lib.svt_call_scan(self._h, C.byref(p), C.byref(n)))
         return self.call_fetch(0, n.value)
@@ -172,6 +187,13 @@ class Engine:
         st = SvtCallStats()
         self._check(self.lib.svt_call_stats_get(self._h, C.byref(st)))
         return {k: (float(getattr(st, k)) if k == "scan_ms" else int(getattr(st, k))) for k, _ in SvtCallStats._fields_}
+
+    def call_split_stats(self) -> dict:
+        """{candidates, split, groups, big} of the last call(): all zero without len_permille."""
+        self._need_call_split()
+        st = SvtCallSplitStats()
+        self._check(self.lib.svt_call_split_stats_get(self._h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in SvtCallSplitStats._fields_}
 
     # ---- genotypes (include/svtrek_genotype.h): alt / ref / spanning reads and GT, GQ, PL per site
     def gt_params(self, flank: int | None = None, costs=None) -> SvtGtParams:

@@ -13,6 +13,11 @@ call of its type and contig lies within --tol bp of bp1.  Prints one JSON line.
 --hotspot N [--hotspot-last] times the scan on a synthetic hot spot instead: N reads with one D op
 each, all starting in one 1-kb bucket (700 distinct starts: the counting sort of a big bucket) or,
 with --hotspot-last, spread over 650 kb of the contig's last bucket (the in-memory bitonic sort).
+
+--len-permille N scans with svt_call_params.len_permille = N (the start clusters split by length) and
+adds the split statistics; the hot spot then gives every start two alternating lengths (D 60 + k % 50
+and ten times that): the regular bucket's 700 neighbouring starts are one candidate holding every
+item, the last bucket's starts, 13 apart, are one with --link 13 and 50 000 candidates without.
 """
 from __future__ import annotations
 
@@ -50,13 +55,15 @@ def recall(calls: np.ndarray, loci: np.ndarray, truth: np.ndarray, tol: int) -> 
     return out
 
 
-def hotspot_pileup(n: int, last: bool):
+def hotspot_pileup(n: int, last: bool, two_lengths: bool = False):
     """n reads at pos 499 800 with [M | H] lead, D 60 + k % 50, M 60: the D ops start at 500 000 + k % 700
     (one regular bucket) or, behind an H op that endpos does not count, at 2 499 800 + 13 * (k % 50 000)."""
     from svtrek_amd import Pileup
     k = np.arange(n, dtype=np.int64)
     lead = 2_000_000 + 13 * (k % 50_000) if last else 200 + k % 700
     dlen = 60 + k % 50
+    if two_lengths:   # the visits of one start alternate (700, 50 000 and 50 are even)
+        dlen = np.where((k // (50_000 if last else 700)) % 2 == 1, 10 * dlen, dlen)
     cigar = np.stack([(lead << 4) | (5 if last else 0), (dlen << 4) | 2, np.full(n, (60 << 4) | 0)], axis=1)
     pos = np.full(n, 499_800, dtype=np.int32)
     endpos = pos + dlen + 60 + (0 if last else lead)
@@ -66,12 +73,12 @@ def hotspot_pileup(n: int, last: bool):
 
 
 def hotspot(a) -> None:
-    pl = hotspot_pileup(a.hotspot, a.hotspot_last)
+    pl = hotspot_pileup(a.hotspot, a.hotspot_last, bool(a.len_permille))
     eng = Engine(Params(), device=0)
     eng.load_pileup(pl)
     ms = []
     for k in range(a.warmup + a.repeat):
-        calls = eng.call(link=a.link, min_support=a.min_support)
+        calls = eng.call(link=a.link, min_support=a.min_support, **split_kw(a))
         if k >= a.warmup:
             ms.append(eng.call_stats()["scan_ms"])
     st = eng.call_stats()
@@ -79,10 +86,19 @@ def hotspot(a) -> None:
         "metric": "svt_call_scan ms on one hot bucket (1 GPU)", "value": round(float(np.median(ms)), 4), "unit": "ms",
         "bucket": "the contig's last (in-memory bitonic sort)" if a.hotspot_last else "regular (counting sort)",
         "items": a.hotspot, "scan_ms_all": [round(x, 4) for x in ms], "events": st["events"], "clusters": st["clusters"],
-        "calls": int(len(calls)), "big_buckets": st["big_buckets"],
+        "calls": int(len(calls)), "big_buckets": st["big_buckets"], **split_out(a, eng),
         "timing": f"svt_call_stats.scan_ms, median of {a.repeat} after {a.warmup} warm-up scans", "engine_version": version(),
     }))
     eng.close()
+
+
+def split_kw(a) -> dict:
+    """Engine.call's extra argument: none without --len-permille (an engine from before the split runs too)."""
+    return {"len_permille": a.len_permille} if a.len_permille else {}
+
+
+def split_out(a, eng) -> dict:
+    return {"len_permille": a.len_permille, "split_stats": eng.call_split_stats()} if a.len_permille else {}
 
 
 def main() -> None:
@@ -93,6 +109,7 @@ def main() -> None:
     ap.add_argument("--link", type=int, default=None)
     ap.add_argument("--min-support", type=int, default=None)
     ap.add_argument("--tol", type=int, default=10)
+    ap.add_argument("--len-permille", type=int, default=0)
     ap.add_argument("--hotspot", type=int, default=0)
     ap.add_argument("--hotspot-last", action="store_true")
     a = ap.parse_args()
@@ -121,7 +138,7 @@ def main() -> None:
     calls = None
     for k in range(a.warmup + a.repeat):
         t0 = time.perf_counter()
-        calls = eng.call(link=a.link, min_support=a.min_support)
+        calls = eng.call(link=a.link, min_support=a.min_support, **split_kw(a))
         t1 = time.perf_counter()
         if k >= a.warmup:
             scan_ms.append(eng.call_stats()["scan_ms"])
@@ -149,7 +166,7 @@ def main() -> None:
                   f"{a.repeat} after {a.warmup} warm-up scans; call_wall: Engine.call with the fetch; reindex: HIP events "
                   "around svt_reindex on one stream",
         "events": st["events"], "skipped": st["skipped"], "clusters": st["clusters"], "calls": st["calls"],
-        "big_buckets": st["big_buckets"], "events_read": keys,
+        "big_buckets": st["big_buckets"], **split_out(a, eng), "events_read": keys,
         "alg_bytes_per_scan": alg, "alg_gbs": round(alg / (med * 1e-3) / 1e9, 2),
         "alg": "per event of arrays S and I (items + trailing-S markers): 16 B read + 8 B key written + 2 x 8 B key read; "
                "48 B per call",
