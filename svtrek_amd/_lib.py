@@ -57,6 +57,11 @@ class SvtCallStats(C.Structure):
         [("scan_ms", C.c_double)]
 
 
+class SvtCallConsensusStats(C.Structure):   # svt_call_consensus_stats
+    _fields_ = [(n, C.c_uint64) for n in ("items", "reach", "ins_calls", "window_items", "window_max", "deferred")] + \
+        [(n, C.c_double) for n in ("table_ms", "gather_ms", "poa_ms")]
+
+
 class SvtParams(C.Structure):
     _fields_ = [
         ("wider_interval", C.c_int32),
@@ -159,6 +164,8 @@ CALL_SYMBOLS = ("svt_call_default_params", "svt_call_scan", "svt_call_fetch", "s
 CALL_SPLIT_SYMBOLS = ("svt_call_split_stats_get",)
 # include/svtrek_genotype.h: likewise (Engine.genotype raises on a backend without it)
 GENOTYPE_SYMBOLS = ("svt_genotype_default_params", "svt_genotype_batch", "svt_genotype_device", "svt_genotype_calls")
+# include/svtrek_callseq.h: likewise (Engine.call_consensus raises on a backend without it)
+CALLSEQ_SYMBOLS = ("svt_call_consensus", "svt_call_consensus_stats_get")
 
 _engine = None
 
@@ -269,7 +276,17 @@ def bind_abi(lib: C.CDLL) -> C.CDLL:
         lib.svt_genotype_calls.argtypes = [P, C.POINTER(SvtGtParams), P, C.c_uint64]
         for name in GENOTYPE_SYMBOLS[1:]:
             getattr(lib, name).restype = C.c_int32
+    if has_callseq(lib):
+        lib.svt_call_consensus.argtypes = [P, C.POINTER(SvtPoaParams), C.c_uint64, C.c_uint64, C.c_int32, P, P]
+        lib.svt_call_consensus_stats_get.argtypes = [P, C.POINTER(SvtCallConsensusStats)]
+        for name in CALLSEQ_SYMBOLS:
+            getattr(lib, name).restype = C.c_int32
     return lib
+
+
+def has_callseq(lib: C.CDLL) -> bool:
+    """Does the library export include/svtrek_callseq.h's entry points?"""
+    return has_call(lib) and all(hasattr(lib, name) for name in CALLSEQ_SYMBOLS)
 
 
 def has_genotype(lib: C.CDLL) -> bool:

@@ -13,7 +13,8 @@
 //   3. parallel per-record extraction in two passes (CIGAR lengths incl. CG tags, then
 //      copies into the final arrays at prefix-summed offsets).
 // A coordinate-sorted BAM (the only kind that has a BAI) needs no reordering; other
-// files are stably sorted by (tid, pos) at the end.  SEQ/QUAL/aux are never copied.
+// files are stably sorted by (tid, pos) at the end.  SEQ/QUAL/aux are never copied -- except, for
+// svth_bam_read_seq, the SEQ bases under every I >= 50 op (the allele-consensus mode's sequences).
 #include <dlfcn.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -515,8 +516,59 @@ struct svth_bam {
     RawVec<uint32_t> cigar;
     RawVec<uint8_t> clip;
     int64_t n_records = 0, n_cg = 0;
+    // svth_bam_read_seq: the inserted bases of the kept reads' I >= 50 ops, in (read, op) order
+    bool has_seq = false;
+    RawVec<uint32_t> ins_cnt, ins_len;   // per read its I >= 50 ops; per op its length
+    RawVec<uint64_t> ins_off;            // [n_ins + 1]
+    RawVec<uint8_t> ins_bases;           // nt4 codes
     double stage_s[6] = {0, 0, 0, 0, 0, 0};   // read, scan, alloc, inflate, wait, total
 };
+
+namespace {
+
+constexpr uint32_t OP_I = 1, INS_MIN = 50;   // the I ops that carry a sequence (include/svtrek_gpu.h: I >= 50)
+
+// A record's I >= 50 ops: their count and the sum of their lengths.
+inline void ins_census(const bamrec::View &v, uint32_t &cnt, uint64_t &bases) {
+    cnt = 0;
+    bases = 0;
+    for (uint32_t j = 0; j < v.n; j++) {
+        const uint32_t w = bamrec::rd32(v.cig + 4ull * j);
+        if ((w & 0xfu) == OP_I && (w >> 4) >= INS_MIN) { cnt++; bases += w >> 4; }
+    }
+}
+
+// The lengths and bases of those ops (r: the record after its block_size word, bs: that word).  The
+// query offset of an op is the summed length of the M, I, S, = and X ops before it in the CIGAR the
+// pileup keeps (the CG-restored one included); bases come from the 4-bit SEQ, high nibble first, codes
+// 1, 2, 4, 8 -> 0 .. 3 and every other code -> 4.  An op that runs past l_seq (l_seq == 0: every op, or
+// a SEQ that runs past the record) keeps its CIGAR length with every base 4.
+inline void ins_extract(const bamrec::View &v, const uint8_t *r, uint32_t bs, uint32_t *len_out, uint8_t *base_out) {
+    static const uint8_t NT4[16] = {4, 0, 1, 4, 2, 4, 4, 4, 3, 4, 4, 4, 4, 4, 4, 4};
+    const uint32_t l_qname = r[8], n_stored = bamrec::rd16(r + 12);
+    int64_t l_seq = (int32_t)bamrec::rd32(r + 16);
+    const uint8_t *seq = r + 32 + l_qname + 4ull * n_stored;
+    if (l_seq < 0 || seq + (size_t)(l_seq + 1) / 2 > r + bs) l_seq = 0;
+    uint64_t q = 0;
+    for (uint32_t j = 0; j < v.n; j++) {
+        const uint32_t w = bamrec::rd32(v.cig + 4ull * j), op = w & 0xfu, len = w >> 4;
+        if (op == OP_I && len >= INS_MIN) {
+            *len_out++ = len;
+            if (q + len <= (uint64_t)l_seq)
+                for (uint64_t t = q; t < q + len; t++) *base_out++ = NT4[(seq[t >> 1] >> ((t & 1) ? 0 : 4)) & 0xf];
+            else {
+                memset(base_out, 4, len);
+                base_out += len;
+            }
+        }
+        if (op == bamrec::OP_M || op == OP_I || op == bamrec::OP_S || op == bamrec::OP_EQ || op == bamrec::OP_X) q += len;
+    }
+}
+
+svth_bam *bam_read_impl(const char *path, int threads, int32_t tid0, int64_t beg0, int32_t tid1, int64_t end1,
+                        const svth_inflater *inf, bool want_seq, char *err, size_t errcap);
+
+}  // namespace
 
 extern "C" {
 
@@ -531,6 +583,28 @@ svth_bam *svth_bam_read_region(const char *path, int threads, int32_t tid0, int6
 
 svth_bam *svth_bam_read_ex(const char *path, int threads, int32_t tid0, int64_t beg0, int32_t tid1, int64_t end1,
                            const svth_inflater *inf, char *err, size_t errcap) {
+    return bam_read_impl(path, threads, tid0, beg0, tid1, end1, inf, false, err, errcap);
+}
+
+svth_bam *svth_bam_read_seq(const char *path, int threads, int32_t tid0, int64_t beg0, int32_t tid1, int64_t end1,
+                            const svth_inflater *inf, char *err, size_t errcap) {
+    return bam_read_impl(path, threads, tid0, beg0, tid1, end1, inf, true, err, errcap);
+}
+
+int svth_bam_insseq(const svth_bam *b, svt_insseq_view *out) {
+    if (!b || !out || !b->has_seq) return 0;
+    out->n_ins = b->ins_off.size() - 1;
+    out->off = b->ins_off.data();
+    out->bases = b->ins_bases.data();
+    return 1;
+}
+
+}  // extern "C"
+
+namespace {
+
+svth_bam *bam_read_impl(const char *path, int threads, int32_t tid0, int64_t beg0, int32_t tid1, int64_t end1,
+                        const svth_inflater *inf, bool want_seq, char *err, size_t errcap) {
     const bool region = tid0 >= 0;
     auto fail = [&](const std::string &m) -> svth_bam * {
         if (err && errcap) snprintf(err, errcap, "%s", m.c_str());
@@ -602,6 +676,9 @@ svth_bam *svth_bam_read_ex(const char *path, int threads, int32_t tid0, int64_t 
     std::vector<size_t> roff;
     std::vector<uint32_t> rlen;
     std::vector<bamrec::View> views;
+    std::vector<uint32_t> insn;          // want_seq: per record its I >= 50 ops ...
+    std::vector<uint64_t> insb;          //           ... and their bases
+    uint64_t n_ins = 0, n_insb = 0;
     while (!done) {
         if (buf.size() - at < 4 && !need(4)) break;   // clean EOF
         // sequential boundary scan over the complete records in the buffer
@@ -625,6 +702,14 @@ svth_bam *svth_bam_read_ex(const char *path, int threads, int32_t tid0, int64_t 
             for (size_t i = i0; i < i1; i++)
                 views[i] = bamrec::view(buf.data() + roff[i], rd32(buf.data() + roff[i] - 4), n_ref);
         });
+        if (want_seq) {
+            insn.assign(nr, 0);
+            insb.assign(nr, 0);
+            parallel_for(rd.threads, nr, [&](size_t i0, size_t i1) {
+                for (size_t i = i0; i < i1; i++)
+                    if (views[i].ok && !views[i].bad) ins_census(views[i], insn[i], insb[i]);
+            });
+        }
         if (region)   // sorted file: the first record past (tid1, end1) ends the read
             for (size_t i = 0; i < nr; i++) {
                 const int32_t t = (int32_t)rd32(buf.data() + roff[i]), ps = (int32_t)rd32(buf.data() + roff[i] + 4);
@@ -653,6 +738,19 @@ svth_bam *svth_bam_read_ex(const char *path, int threads, int32_t tid0, int64_t 
         if (!b->pos.resize(base + kept) || !b->endpos.resize(base + kept) || !b->clip.resize(base + kept) ||
             !tid_of.resize(base + kept) || !b->cig_off.resize(base + kept) || !b->cigar.resize(narena + off[nr]))
             return bail("out of host memory");
+        std::vector<uint64_t> ioff, iboff;   // want_seq: where each record's ops / bases go
+        if (want_seq) {
+            ioff.assign(nr + 1, n_ins);
+            iboff.assign(nr + 1, n_insb);
+            for (size_t i = 0; i < nr; i++) {
+                ioff[i + 1] = ioff[i] + (views[i].ok ? insn[i] : 0);
+                iboff[i + 1] = iboff[i] + (views[i].ok ? insb[i] : 0);
+            }
+            if (!b->ins_cnt.resize(base + kept) || !b->ins_len.resize(ioff[nr]) || !b->ins_bases.resize(iboff[nr]))
+                return bail("out of host memory");
+            n_ins = ioff[nr];
+            n_insb = iboff[nr];
+        }
         parallel_for(rd.threads, nr, [&](size_t i0, size_t i1) {
             for (size_t i = i0; i < i1; i++) {
                 const bamrec::View &v = views[i];
@@ -665,6 +763,12 @@ svth_bam *svth_bam_read_ex(const char *path, int threads, int32_t tid0, int64_t 
                 b->clip[k] = (uint8_t)v.clip;
                 b->cig_off[k] = narena + off[i];
                 tid_of[k] = v.tid;
+                if (want_seq) {
+                    b->ins_cnt[k] = insn[i];
+                    if (insn[i])
+                        ins_extract(v, buf.data() + roff[i], rd32(buf.data() + roff[i] - 4), b->ins_len.data() + ioff[i],
+                                    b->ins_bases.data() + iboff[i]);
+                }
             }
         });
         narena += off[nr];
@@ -684,8 +788,9 @@ svth_bam *svth_bam_read_ex(const char *path, int threads, int32_t tid0, int64_t 
     bool sorted = true;
     for (size_t i = 1; i < n && sorted; i++)
         sorted = tid_of[i] > tid_of[i - 1] || (tid_of[i] == tid_of[i - 1] && b->pos[i] >= b->pos[i - 1]);
+    std::vector<size_t> idx;
     if (!sorted) {
-        std::vector<size_t> idx(n);
+        idx.resize(n);
         std::iota(idx.begin(), idx.end(), 0);
         std::stable_sort(idx.begin(), idx.end(), [&](size_t x, size_t y) {
             return tid_of[x] != tid_of[y] ? tid_of[x] < tid_of[y] : b->pos[x] < b->pos[y];
@@ -712,8 +817,39 @@ svth_bam *svth_bam_read_ex(const char *path, int threads, int32_t tid0, int64_t 
     b->tid_off.assign((size_t)n_ref + 1, 0);
     for (size_t k = 0; k < n; k++) b->tid_off[(size_t)tid_of[k] + 1]++;
     for (int32_t t = 0; t < n_ref; t++) b->tid_off[(size_t)t + 1] += b->tid_off[(size_t)t];
+    if (want_seq) {   // the ops' offsets, in the final (read, op) order
+        if (!b->ins_off.resize((size_t)n_ins + 1)) { delete b; return fail("out of host memory"); }
+        b->ins_off[0] = 0;
+        if (sorted) {
+            for (uint64_t k = 0; k < n_ins; k++) b->ins_off[k + 1] = b->ins_off[k] + b->ins_len[k];
+        } else {
+            // per file-order read its first op and first base, then the reads in sorted order
+            std::vector<uint64_t> first(n + 1, 0), fbase(n + 1, 0);
+            for (size_t i = 0, k = 0; i < n; i++) {
+                first[i + 1] = first[i] + b->ins_cnt[i];
+                fbase[i + 1] = fbase[i];
+                for (; k < first[i + 1]; k++) fbase[i + 1] += b->ins_len[k];
+            }
+            RawVec<uint8_t> bases2;
+            if (!bases2.resize((size_t)n_insb)) { delete b; return fail("out of host memory"); }
+            uint64_t k2 = 0, w = 0;
+            for (size_t r = 0; r < n; r++) {
+                const size_t i = idx[r];
+                for (uint64_t k = first[i]; k < first[i + 1]; k++, k2++) b->ins_off[k2 + 1] = b->ins_off[k2] + b->ins_len[k];
+                const uint64_t m = fbase[i + 1] - fbase[i];
+                if (m) memcpy(bases2.data() + w, b->ins_bases.data() + fbase[i], m);
+                w += m;
+            }
+            b->ins_bases.swap(bases2);
+        }
+        b->has_seq = true;
+    }
     return b;
 }
+
+}  // namespace
+
+extern "C" {
 
 int svth_bam_read_device(const char *path, int threads, const svth_dev_sink *sink, int32_t *n_targets, double *stage4,
                          char *err, size_t errcap) {

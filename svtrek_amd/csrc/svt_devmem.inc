@@ -92,6 +92,16 @@ struct CallScratch {
     svt_call_split_stats split{};
 };
 
+// svt_call_consensus's scratch (svt_callseq.inc, svt_callseq_host.inc): nothing allocated before the
+// first call on a loaded pileup, gone with the pileup.
+struct CallSeqScratch {
+    bool ready = false;            // the item table and the reach are those of the loaded pileup
+    DevBuf<uint2> d_tab;           // [n_ins] {x, len} per sequence index
+    DevBuf<unsigned long long> d_ctr;   // [0] the reach (32 bits), [1..4) the gather's counters
+    uint32_t reach = 0;
+    svt_call_consensus_stats stats{};
+};
+
 // One pool of POA scratch slots (svt_poa.inc, svt_poa_host.inc).
 struct PoaPool {
     DevBuf<uint8_t> d;

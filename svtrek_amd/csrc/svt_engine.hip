@@ -31,9 +31,11 @@
 //   svt_genotype.inc      genotypes of DEL / INS sites (host side: svt_genotype_host.inc)
 //   svt_index.inc, svt_index2.inc, svt_bucket_build.inc   the index builds (span lists, value buckets)
 //   svt_poa.inc, svt_poa_host.inc      allele consensus (POA): kernels, slot pools and poa_run
+//   svt_callseq.inc       consensus sequence of discovered INS calls: item table and support gather
+//                         (host side: svt_callseq_host.inc)
 //   svt_bam.inc, svt_inflate.inc, svt_bam_host.inc   BGZF inflate and BAM decode: kernels, svt_bam_dec_*
 //   svt_devmem.inc        host only: DevBuf / DevEvent, the owners of every device allocation and event
-//                         the host code makes, and the side modes' scratch records (CallScratch, PoaPool)
+//                         the host code makes, and the side modes' scratch records (CallScratch, CallSeqScratch, PoaPool)
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -55,9 +57,10 @@
 #include "../../include/svtrek_evidence.h"
 #include "../../include/svtrek_call.h"
 #include "../../include/svtrek_genotype.h"
+#include "../../include/svtrek_callseq.h"
 #include "svt_bamrec.h"
 
-#define SVT_VERSION "svtrek_amd 0.29.0 (gfx950, value-bucketed event index filed by a lane-per-read walk with a 9-B LDS stage, band + prefix-max facts, packed span walk fed by readlane, lane vote on 64 windows a wave, BGZF inflate + BAM decode, DEL/INS discovery from the value buckets, genotypes from the events' own read extents)"
+#define SVT_VERSION "svtrek_amd 0.30.0 (gfx950, value-bucketed event index filed by a lane-per-read walk with a 9-B LDS stage, band + prefix-max facts, packed span walk fed by readlane, lane vote on 64 windows a wave, BGZF inflate + BAM decode, DEL/INS discovery from the value buckets, genotypes from the events' own read extents, consensus sequence of INS calls)"
 
 namespace {
 
@@ -176,6 +179,7 @@ constexpr int LV_WMAX = 1023;   // band half-width for 16-bit offsets and prefix
 #include "svt_index2.inc"
 #include "svt_bucket_build.inc"
 #include "svt_poa.inc"
+#include "svt_callseq.inc"
 #include "svt_bam.inc"
 #include "svt_inflate.inc"
 
@@ -231,6 +235,7 @@ struct Pileup {
     uint32_t bk_builds = 0;           // filing passes so far (the cursors' epoch)
     uint32_t bk_nev = 0;              // d_bkev's events (every array's)
     CallScratch call;                 // svt_call_scan
+    CallSeqScratch callseq;           // svt_call_consensus
     uint64_t dev_bytes = 0;
     bool loaded = false;
 };
@@ -1323,12 +1328,7 @@ svt_status svt_poa_consensus(svt_ctx *c, const svt_poa_params *p, const svt_locu
     if (n == 0) return SVT_OK;
     if (!loci || !refined || !res || cap < 0 || (cap > 0 && !bases)) return fail(c, SVT_EINVAL, "%s", "null arrays / cap");
     if (n > 0x3fffffffull) return fail(c, SVT_EINVAL, "%s", "batch too large");
-    const int64_t w_max = (int64_t)p->band_b + (int64_t)p->band_f_permille * p->max_len / 1000;
-    if (p->match < 0 || p->mismatch < 0 || p->gap_open < 0 || p->gap_ext < 0 || p->band_b < 1 || p->band_f_permille < 0 ||
-        p->max_seqs < 1 || p->max_seqs > POA_PIN || p->max_len < 1 || p->max_len > POA_SEQ_MAX || w_max > 63 ||
-        p->max_nodes < p->max_len || p->max_nodes > 65000 || p->support_radius < 0 || p->max_support < 1 ||
-        p->match > 1000 || p->mismatch > 1000 || p->gap_open > 1000 || p->gap_ext > 1000)
-        return fail(c, SVT_EINVAL, "%s", "poa params out of range");
+    if (!poa_params_ok(p)) return fail(c, SVT_EINVAL, "%s", "poa params out of range");
     DEV_GUARD(c);
     return poa_run(c, p, loci, refined, n, cap, bases, res);
 }
@@ -1385,6 +1385,9 @@ svt_status svt_evidence_batch(svt_ctx *c, const svt_locus *loci, const svt_resul
 
 // ---- include/svtrek_genotype.h
 #include "svt_genotype_host.inc"
+
+// ---- include/svtrek_callseq.h
+#include "svt_callseq_host.inc"
 
 uint64_t svt_pileup_device_bytes(const svt_ctx *c) { return c ? c->dev_bytes : 0; }
 

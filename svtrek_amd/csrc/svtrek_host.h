@@ -18,6 +18,7 @@
 #include "svtrek_evidence.h"
 #include "svtrek_call.h"
 #include "svtrek_genotype.h"
+#include "svtrek_callseq.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -54,6 +55,18 @@ typedef struct svth_inflater {
  * inf == NULL: host threads inflate. */
 svth_bam *svth_bam_read_ex(const char *path, int threads, int32_t tid0, int64_t beg0, int32_t tid1, int64_t end1,
                            const svth_inflater *inf, char *err, size_t errcap);
+/* svth_bam_read_ex that also keeps the inserted bases of the kept reads' I >= 50 ops -- what
+ * svt_load_insseq takes -- in the final pileup's (read, op) order (after the stable (tid, pos) sort
+ * when the file needed one), so that n_ins == svt_pileup_ins_count() once the pileup is loaded.
+ * The query offset of an op is the summed length of the M, I, S, = and X ops before it (H, P, N and D
+ * consume no SEQ) in the CIGAR the pileup keeps, the one restored from CG:B,I included.  Bases are
+ * unpacked from the 4-bit SEQ, high nibble first: codes 1, 2, 4, 8 become 0, 1, 2, 3, every other code
+ * 4.  With l_seq == 0, or where an op runs past l_seq, the sequence has its CIGAR length and every
+ * base is 4. */
+svth_bam *svth_bam_read_seq(const char *path, int threads, int32_t tid0, int64_t beg0, int32_t tid1, int64_t end1,
+                            const svth_inflater *inf, char *err, size_t errcap);
+/* Those sequences (valid until svth_bam_free): 1, or 0 for a pileup read without them. */
+int svth_bam_insseq(const svth_bam *b, svt_insseq_view *out);
 /* A BAM decoded on the device: the file read in batches of whole BGZF blocks (`threads`
  * parallel preads; buffers from sink->alloc when given, e.g. pinned memory) and handed to
  * sink->feed compressed -- the next batch read by a helper thread meanwhile.  The header is
@@ -127,6 +140,14 @@ char *svth_format_calls(const svt_call *calls, size_t n, const char *const *name
  * takes the sites-only one.  gts == NULL: svth_format_calls, byte for byte. */
 char *svth_format_calls_gt(const svt_call *calls, const svt_gt *gts, size_t n, const char *const *names, size_t n_names,
                            const char *sample, int header, int threads, size_t *len);
+/* The same with the consensus inserted sequences (include/svtrek_callseq.h), cons[k] / bases[k * cap ..] call
+ * k's svt_call_consensus record: the header gains the ##INFO lines of CONSLEN and CONSREADS; an INS call with
+ * 1 <= len <= cap is written as REF N, ALT N followed by the consensus as ACGTN, every other INS call keeps
+ * N <INS>; every INS call's INFO ends in ";CONSLEN=<len, or 0 when there is none>;CONSREADS=<n_used>" (SVTYPE
+ * and END stay first).  DEL records are unchanged.  cons == NULL: svth_format_calls_gt, byte for byte. */
+char *svth_format_calls_seq(const svt_call *calls, const svt_gt *gts, const svt_poa_result *cons, const uint8_t *bases,
+                            int32_t cap, size_t n, const char *const *names, size_t n_names, const char *sample, int header,
+                            int threads, size_t *len);
 void  svth_free(void *p);
 
 /* A11: stdout text for one refined record; returns bytes written (0 = prints nothing:

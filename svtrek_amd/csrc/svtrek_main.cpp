@@ -41,6 +41,9 @@ extern "C" __typeof__(svt_call_split_stats_get) svt_call_split_stats_get __attri
 // include/svtrek_genotype.h likewise (`svtrek call --genotype`)
 extern "C" __typeof__(svt_genotype_default_params) svt_genotype_default_params __attribute__((weak));
 extern "C" __typeof__(svt_genotype_calls) svt_genotype_calls __attribute__((weak));
+// include/svtrek_callseq.h likewise (`svtrek call --ins-seq`)
+extern "C" __typeof__(svt_call_consensus) svt_call_consensus __attribute__((weak));
+extern "C" __typeof__(svt_call_consensus_stats_get) svt_call_consensus_stats_get __attribute__((weak));
 
 namespace {
 
@@ -70,6 +73,10 @@ void call_usage() {
     printf("                                      [Default: a sites-only VCF]\n");
     printf("    --flank <num>                     Bases a read must cover on both sides of a call to count [Default: 50]\n");
     printf("    --sample <name>                   The sample column's name [Default: SAMPLE]\n");
+    printf("    --ins-seq                         Consensus inserted sequence of every INS call from the reads' SEQ: ALT\n");
+    printf("                                      becomes N + the consensus, INFO gains CONSLEN and CONSREADS\n");
+    printf("                                      [Default: N <INS> alone]\n");
+    printf("    --ins-seq-cap <num>               Longest consensus written as ALT; longer ones keep <INS> [Default: 4096]\n");
     printf("    --device <num>                    GPU index [Default: 0]\n");
     printf("    --inflate <auto|gpu|cpu>          BGZF decompression of the BAM: the GPU or -t host threads;\n");
     printf("                                      auto: the GPU from 1 GiB of BAM on [Default: auto]\n");
@@ -568,6 +575,7 @@ int audit(int argc, char **argv) {
 int call_mode(int argc, char **argv) {
     const char *bam_path = nullptr, *out_path = nullptr, *sample = "SAMPLE";
     int threads = THREADS, verbose = 0, device = 0, gpu_inflate = -1, link = -1, min_support = -1, genotype = 0, flank = -1, len_permille = 0;
+    int ins_seq = 0, ins_cap = 4096;
     uint32_t types = (1u << SVT_INS) | (1u << SVT_DEL);
     static const option opts[] = {
         {"bam", required_argument, nullptr, 1}, {"output", required_argument, nullptr, 3},
@@ -576,7 +584,8 @@ int call_mode(int argc, char **argv) {
         {"link", required_argument, nullptr, 30}, {"min-support", required_argument, nullptr, 31},
         {"types", required_argument, nullptr, 32}, {"genotype", no_argument, nullptr, 33},
         {"flank", required_argument, nullptr, 34}, {"sample", required_argument, nullptr, 35},
-        {"len-permille", required_argument, nullptr, 36}, {nullptr, 0, nullptr, 0}};
+        {"len-permille", required_argument, nullptr, 36}, {"ins-seq", no_argument, nullptr, 37},
+        {"ins-seq-cap", required_argument, nullptr, 38}, {nullptr, 0, nullptr, 0}};
     int opt, li;
     while ((opt = getopt_long(argc, argv, "b:o:t:h", opts, &li)) != -1) {
         switch (opt) {
@@ -612,6 +621,8 @@ int call_mode(int argc, char **argv) {
         case 34: flank = atoi(optarg); if (flank < 0 || flank > (1 << 20)) { fprintf(stderr, "[ERROR] --flank must be in [0, 1048576]\n"); exit(EXIT_FAILURE); } break;
         case 35: sample = optarg; break;
         case 36: len_permille = atoi(optarg); if (len_permille < 0 || len_permille > 1000) { fprintf(stderr, "[ERROR] --len-permille must be in [0, 1000]\n"); exit(EXIT_FAILURE); } break;
+        case 37: ins_seq = 1; break;
+        case 38: ins_cap = atoi(optarg); if (ins_cap < 1 || ins_cap > (1 << 20)) { fprintf(stderr, "[ERROR] --ins-seq-cap must be in [1, 1048576]\n"); exit(EXIT_FAILURE); } break;
         default:
             printf("[ERROR] Option %d is invalid.\n", opt);
             call_usage();
@@ -622,6 +633,10 @@ int call_mode(int argc, char **argv) {
     if (threads < 1) { fprintf(stderr, "[ERROR] -t must be >= 1\n"); exit(EXIT_FAILURE); }
     if (genotype && (!svt_genotype_calls || !svt_genotype_default_params)) {
         fprintf(stderr, "[ERROR] genotype: not supported by this backend\n");
+        return 1;
+    }
+    if (ins_seq && (!svt_call_consensus || !svt_call_consensus_stats_get)) {
+        fprintf(stderr, "[ERROR] ins-seq: not supported by this backend\n");
         return 1;
     }
     if (!svt_call_scan || !svt_call_default_params || !svt_call_fetch || !svt_call_stats_get) {
@@ -644,7 +659,8 @@ int call_mode(int argc, char **argv) {
     });
     char err[512];
     const svth_inflater dev_inf{device_inflate, device_host_alloc, device_host_free, &dinf, (size_t)1024 << 20};
-    svth_bam *bam = svth_bam_read_ex(bam_path, threads, -1, 0, -1, 0, gpu_inflate ? &dev_inf : nullptr, err, sizeof err);
+    svth_bam *bam = (ins_seq ? svth_bam_read_seq : svth_bam_read_ex)(bam_path, threads, -1, 0, -1, 0,
+                                                                    gpu_inflate ? &dev_inf : nullptr, err, sizeof err);
     ot.join();
     auto done = [&](int rc) {
         svth_bam_free(bam);
@@ -664,6 +680,11 @@ int call_mode(int argc, char **argv) {
     cp.len_permille = (uint32_t)len_permille;
     uint64_t n = 0;
     svt_status s = svt_load_pileup(ctx, &view);
+    if (!s && ins_seq) {   // the inserted bases the ingest kept
+        svt_insseq_view sv{};
+        if (!svth_bam_insseq(bam, &sv)) { fprintf(stderr, "[ERROR] --ins-seq: the ingest kept no sequences\n"); return done(1); }
+        s = svt_load_insseq(ctx, &sv);
+    }
     const double t_load = now_s();
     if (!s) s = svt_call_scan(ctx, &cp, &n);
     std::vector<svt_call> calls((size_t)n);
@@ -679,14 +700,27 @@ int call_mode(int argc, char **argv) {
         gts.resize((size_t)n);
         s = svt_genotype_calls(ctx, &gp, gts.data(), n);
     }
-    if (s) { fprintf(stderr, "[ERROR] GPU %d: %s (status %d)\n", device, svt_last_error(ctx), (int)s); return done(1); }
     const double t_gt = now_s();
+    std::vector<svt_poa_result> cons;
+    std::vector<uint8_t> cons_bases;
+    svt_call_consensus_stats cs{};
+    if (!s && ins_seq) {
+        svt_poa_params pp;
+        svt_poa_default_params(&pp);
+        cons.resize((size_t)n + 1);   // (no calls: the header still has to name CONSLEN)
+        cons_bases.resize((size_t)n * (size_t)ins_cap + 1);
+        s = svt_call_consensus(ctx, &pp, 0, n, ins_cap, cons_bases.data(), cons.data());
+        if (!s) s = svt_call_consensus_stats_get(ctx, &cs);
+    }
+    if (s) { fprintf(stderr, "[ERROR] GPU %d: %s (status %d)\n", device, svt_last_error(ctx), (int)s); return done(1); }
+    const double t_cons = now_s();
     std::vector<const char *> names((size_t)svth_bam_n_targets(bam));
     for (size_t t = 0; t < names.size(); t++) names[t] = svth_bam_target_name(bam, (int32_t)t);
     size_t olen = 0;
     static const svt_gt no_gt{};   // (no calls: the header still has to say FORMAT)
-    char *text = svth_format_calls_gt(calls.data(), genotype ? (gts.empty() ? &no_gt : gts.data()) : nullptr, calls.size(),
-                                      names.data(), names.size(), sample, 1, threads, &olen);
+    char *text = svth_format_calls_seq(calls.data(), genotype ? (gts.empty() ? &no_gt : gts.data()) : nullptr,
+                                       ins_seq ? cons.data() : nullptr, ins_seq ? cons_bases.data() : nullptr, ins_cap, calls.size(),
+                                       names.data(), names.size(), sample, 1, threads, &olen);
     if (!text) { fprintf(stderr, "[ERROR] out of host memory\n"); return done(1); }
     FILE *of = out_path ? fopen(out_path, "wb") : stdout;
     bool ok = of && fwrite(text, 1, olen, of) == olen;
@@ -695,11 +729,17 @@ int call_mode(int argc, char **argv) {
     svth_free(text);
     if (!ok) { fprintf(stderr, "[ERROR] call: cannot write %s\n", out_path ? out_path : "stdout"); return done(1); }
     if (verbose && genotype) fprintf(stderr, "[svtrek_amd] call: genotype %.3fs\n", t_gt - t_scan);
+    if (verbose && ins_seq)
+        fprintf(stderr, "[svtrek_amd] call: ins-seq %.3fs  items %llu  reach %llu  INS calls %llu  window items %llu (max %llu)  "
+                        "deferred %llu  table %.3f ms  gather %.3f ms  poa %.3f ms\n",
+                t_cons - t_gt, (unsigned long long)cs.items, (unsigned long long)cs.reach, (unsigned long long)cs.ins_calls,
+                (unsigned long long)cs.window_items, (unsigned long long)cs.window_max, (unsigned long long)cs.deferred,
+                cs.table_ms, cs.gather_ms, cs.poa_ms);
     if (verbose)
         fprintf(stderr, "[svtrek_amd] call: ingest %.3fs (%s)  load %.3fs  scan+fetch %.3fs (device scan %.3f ms)  print %.3fs  "
                         "items %llu (skipped %llu)  clusters %llu  calls %llu  big buckets %llu  link %d  min-support %d\n",
                 t_ingest - t0, gpu_inflate ? "gpu inflate, host parse" : "cpu", t_load - t_ingest, t_scan - t_load, st.scan_ms,
-                now_s() - t_gt, (unsigned long long)st.events, (unsigned long long)st.skipped, (unsigned long long)st.clusters,
+                now_s() - t_cons, (unsigned long long)st.events, (unsigned long long)st.skipped, (unsigned long long)st.clusters,
                 (unsigned long long)st.calls, (unsigned long long)st.big_buckets, cp.link, cp.min_support);
     svt_call_split_stats ss{};
     if (verbose && len_permille && svt_call_split_stats_get && !svt_call_split_stats_get(ctx, &ss))

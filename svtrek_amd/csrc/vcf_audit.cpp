@@ -235,6 +235,12 @@ char *svth_format_calls(const svt_call *c, size_t n, const char *const *names, s
 
 char *svth_format_calls_gt(const svt_call *c, const svt_gt *gts, size_t n, const char *const *names, size_t n_names,
                            const char *sample, int header, int threads, size_t *len) {
+    return svth_format_calls_seq(c, gts, nullptr, nullptr, 0, n, names, n_names, sample, header, threads, len);
+}
+
+char *svth_format_calls_seq(const svt_call *c, const svt_gt *gts, const svt_poa_result *cons, const uint8_t *bases, int32_t cap,
+                            size_t n, const char *const *names, size_t n_names, const char *sample, int header, int threads,
+                            size_t *len) {
     const int T = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(threads, 1), n / 16384 + 1));
     // the ID's k: the call's rank among the calls of its type (1-based)
     std::vector<size_t> first_k((size_t)T * 2 + 2, 0);
@@ -259,12 +265,25 @@ char *svth_format_calls_gt(const svt_call *c, const svt_gt *gts, size_t n, const
             if (x.chrom >= 1 && (size_t)x.chrom <= n_names && names && names[x.chrom - 1]) name = names[x.chrom - 1];
             else snprintf(num, sizeof num, "%d", x.chrom);
             o += name;
-            const int m = snprintf(buf, sizeof buf,
-                                   "\t%u\tsvtrek.%s.%zu\tN\t<%s>\t.\tPASS\tSVTYPE=%s;END=%u;SVLEN=%s%u;SUPPORT=%u;DEPTH=%u;"
-                                   "XRANGE=%u,%u;LENRANGE=%u,%u",
-                                   x.pos, ty, ++rank[del ? 0 : 1], ty, ty, x.end, del ? "-" : "", x.len, x.support, x.depth,
-                                   x.x_lo, x.x_hi, x.len_lo, x.len_hi);
+            int m = snprintf(buf, sizeof buf, "\t%u\tsvtrek.%s.%zu\tN\t", x.pos, ty, ++rank[del ? 0 : 1]);
             o.append(buf, (size_t)m);
+            const bool ins_cons = cons && !del;
+            if (ins_cons && cons[k].len >= 1 && cons[k].len <= cap && bases) {   // ALT: the base before + the consensus
+                const uint8_t *q = bases + k * (size_t)cap;
+                o += 'N';
+                for (int32_t i = 0; i < cons[k].len; i++) o += "ACGTN"[q[i] < 4 ? q[i] : 4];
+            } else {
+                o += '<';
+                o += ty;
+                o += '>';
+            }
+            m = snprintf(buf, sizeof buf, "\t.\tPASS\tSVTYPE=%s;END=%u;SVLEN=%s%u;SUPPORT=%u;DEPTH=%u;XRANGE=%u,%u;LENRANGE=%u,%u",
+                         ty, x.end, del ? "-" : "", x.len, x.support, x.depth, x.x_lo, x.x_hi, x.len_lo, x.len_hi);
+            o.append(buf, (size_t)m);
+            if (ins_cons) {
+                m = snprintf(buf, sizeof buf, ";CONSLEN=%d;CONSREADS=%d", cons[k].len > 0 ? cons[k].len : 0, cons[k].n_used);
+                o.append(buf, (size_t)m);
+            }
             if (gts) {
                 const svt_gt &g = gts[k];
                 static const char *const GT[3] = {"0/0", "0/1", "1/1"};
@@ -289,6 +308,9 @@ char *svth_format_calls_gt(const svt_call *c, const svt_gt *gts, size_t n, const
                 "##INFO=<ID=DEPTH,Number=1,Type=Integer,Description=\"Reads covering POS\">\n"
                 "##INFO=<ID=XRANGE,Number=2,Type=Integer,Description=\"Smallest and largest start of the supporting ops\">\n"
                 "##INFO=<ID=LENRANGE,Number=2,Type=Integer,Description=\"Smallest and largest length of the supporting ops\">\n";
+        if (cons)
+            head += "##INFO=<ID=CONSLEN,Number=1,Type=Integer,Description=\"INS: length of the consensus inserted sequence (0: none)\">\n"
+                    "##INFO=<ID=CONSREADS,Number=1,Type=Integer,Description=\"INS: inserted sequences fused into the consensus\">\n";
         if (gts)
             head += "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
                     "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: the smaller PL of the other two genotypes, at most 99\">\n"

@@ -14,9 +14,9 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._lib import (CALL_DTYPE, EVIDENCE_DTYPE, GT_DTYPE, GT_SITE_DTYPE, LOCUS_DTYPE, POA_RESULT_DTYPE, RESULT_DTYPE,
-                   STATUS_NAMES, SVT_DEL, SVT_EINVAL, SVT_INS, SVT_NA, SW_QUERY_DTYPE, SW_WINDOW_DTYPE, SvtCallParams,
-                   SvtCallSplitStats, SvtCallStats, SvtGtParams, SvtInsseqView, SvtLoadStats, SvtParams, SvtPoaParams,
-                   SvtWork, has_call, has_call_split, has_evidence, has_genotype, load_engine, ptr)
+                   STATUS_NAMES, SVT_DEL, SVT_EINVAL, SVT_INS, SVT_NA, SW_QUERY_DTYPE, SW_WINDOW_DTYPE, SvtCallConsensusStats,
+                   SvtCallParams, SvtCallSplitStats, SvtCallStats, SvtGtParams, SvtInsseqView, SvtLoadStats, SvtParams, SvtPoaParams,
+                   SvtWork, has_call, has_call_split, has_callseq, has_evidence, has_genotype, load_engine, ptr)
 from .pileup import Pileup
 
 # params.h:27-32
@@ -194,6 +194,39 @@ class Engine:
         st = SvtCallSplitStats()
         self._check(self.lib.svt_call_split_stats_get(self._h, C.byref(st)))
         return {k: int(getattr(st, k)) for k, _ in SvtCallSplitStats._fields_}
+
+    # ---- consensus inserted sequence of the INS calls (include/svtrek_callseq.h)
+    def _need_callseq(self) -> None:
+        self._need_call()
+        if not has_callseq(self.lib):
+            raise SvtError(SVT_EINVAL, "this backend does not export svt_call_consensus (include/svtrek_callseq.h): "
+                                       "the calls' consensus sequences need the HIP engine 0.30.0 or later")
+
+    def call_consensus(self, first: int = 0, n: int | None = None, cap: int = 4096, **poa_kw):
+        """(POA_RESULT_DTYPE per call, uint8 [n, cap] nt4 consensus bases) of calls [first, first + n) of the
+        last call() -- n None: all from `first` on -- after load_insseq (svt_call_consensus): an INS call's
+        record is {len, n_support, n_used, 0} and bases[j, :min(len, cap)] its consensus, a DEL call's
+        {-1, 0, 0, 0}.  poa_kw: poa_params' fields (max_len, max_support, max_seqs, ...)."""
+        self._need_callseq()
+        first = int(first)
+        if n is None:
+            n = max(self.call_device()[1] - first, 0)
+        n = int(n)
+        res = np.zeros(n, dtype=POA_RESULT_DTYPE)
+        out = np.zeros((n, cap), dtype=np.uint8)
+        p = self.poa_params(**poa_kw)
+        self._check(self.lib.svt_call_consensus(self._h, C.byref(p), first, n, int(cap), ptr(out) if out.size else None,
+                                                ptr(res) if n else None))
+        return res, out
+
+    def call_consensus_stats(self) -> dict:
+        """{items, reach, ins_calls, window_items, window_max, deferred, table_ms, gather_ms, poa_ms} of the
+        last call_consensus()."""
+        self._need_callseq()
+        st = SvtCallConsensusStats()
+        self._check(self.lib.svt_call_consensus_stats_get(self._h, C.byref(st)))
+        return {k: (float(getattr(st, k)) if k.endswith("_ms") else int(getattr(st, k)))
+                for k, _ in SvtCallConsensusStats._fields_}
 
     # ---- genotypes (include/svtrek_genotype.h): alt / ref / spanning reads and GT, GQ, PL per site
     def gt_params(self, flank: int | None = None, costs=None) -> SvtGtParams:

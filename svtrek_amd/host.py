@@ -6,7 +6,7 @@ import os
 
 import numpy as np
 
-from ._lib import LOCUS_DTYPE, PKG, SvtPileupView
+from ._lib import LOCUS_DTYPE, PKG, SvtInsseqView, SvtPileupView
 from .pileup import Pileup
 
 _host = None
@@ -28,6 +28,13 @@ def load_host() -> C.CDLL:
         L.svth_bam_read_ex.argtypes = [C.c_char_p, C.c_int, C.c_int32, C.c_int64, C.c_int32, C.c_int64, P,
                                        C.c_char_p, C.c_size_t]
         L.svth_bam_read_ex.restype = P
+        L.svth_bam_read_seq.argtypes = L.svth_bam_read_ex.argtypes
+        L.svth_bam_read_seq.restype = P
+        L.svth_bam_insseq.argtypes = [P, C.POINTER(SvtInsseqView)]
+        L.svth_bam_insseq.restype = C.c_int
+        L.svth_format_calls_seq.argtypes = [P, P, P, P, C.c_int32, C.c_size_t, P, C.c_size_t, C.c_char_p, C.c_int, C.c_int,
+                                            C.POINTER(C.c_size_t)]
+        L.svth_format_calls_seq.restype = P
         L.svth_bam_read_device.argtypes = [C.c_char_p, C.c_int, P, P, P, C.c_char_p, C.c_size_t]
         L.svth_bam_read_device.restype = C.c_int
         L.svth_vcf_parse.argtypes = [C.c_char_p, C.c_size_t, C.c_int]
@@ -141,17 +148,20 @@ def load_bam_device(engine, path: str, threads: int = 4, batch_bytes: int = 0, p
 
 
 def read_bam(path: str, threads: int = 4, region: tuple[int, int, int, int] | None = None,
-             inflate=None, batch_bytes: int = 0, pinned: bool = True) -> tuple[Pileup, dict]:
+             inflate=None, batch_bytes: int = 0, pinned: bool = True, insseq: bool = False):
     """The BAM as a columnar pileup.  region = (tid0, beg0, tid1, end1): only the records from
     the BAI's linear-index offset of (tid0, beg0) up to the first at or past (tid1, end1)
     (svth_bam_read_region; needs `path`.bai) -- what one shard's queries can yield.
     inflate = an Engine: the BGZF blocks are inflated by its svt_bgzf_inflate (the device, in
-    ~1 GiB batches overlapped with the record parse) instead of host threads."""
+    ~1 GiB batches overlapped with the record parse) instead of host threads.
+    insseq = True (svth_bam_read_seq): the inserted bases of the kept reads' I >= 50 ops too, as
+    Engine.load_insseq takes them -- returns (pileup, info, (off, bases)) instead of (pileup, info)."""
     L = load_host()
     err = C.create_string_buffer(512)
     t0, b0, t1, e1 = (int(x) for x in region) if region is not None else (-1, 0, -1, 0)
+    reader = L.svth_bam_read_seq if insseq else L.svth_bam_read_ex
     if inflate is None:
-        h = L.svth_bam_read_region(path.encode(), threads, t0, b0, t1, e1, err, 512)
+        h = reader(path.encode(), threads, t0, b0, t1, e1, None, err, 512)
     else:
         lib, ctx = inflate.lib, inflate._h
 
@@ -166,7 +176,7 @@ def read_bam(path: str, threads: int = 4, region: tuple[int, int, int, int] | No
         fr = RELEASE_FN(lambda _u, p: lib.svt_host_free(ctx, p))
         inf = SvthInflater(C.cast(fn, C.c_void_p), C.cast(fa, C.c_void_p) if pinned else None,
                            C.cast(fr, C.c_void_p) if pinned else None, None, batch_bytes)
-        h = L.svth_bam_read_ex(path.encode(), threads, t0, b0, t1, e1, C.byref(inf), err, 512)
+        h = reader(path.encode(), threads, t0, b0, t1, e1, C.byref(inf), err, 512)
     if not h:
         raise OSError(err.value.decode())
     try:
@@ -194,7 +204,13 @@ def read_bam(path: str, threads: int = 4, region: tuple[int, int, int, int] | No
         info = {"names": [L.svth_bam_target_name(h, t).decode() for t in range(nt)],
                 "records": int(L.svth_bam_n_records(h)), "cg_restored": int(L.svth_bam_n_cg_restored(h)),
                 "stage_s": dict(zip(("read", "scan", "alloc", "inflate", "wait", "total"), (round(x, 4) for x in st)))}
-        return pl, info
+        if not insseq:
+            return pl, info
+        sv = SvtInsseqView()
+        if not L.svth_bam_insseq(h, C.byref(sv)):
+            raise OSError("svth_bam_insseq: the ingest kept no sequences")
+        off = arr(sv.off, np.uint64, int(sv.n_ins) + 1)
+        return pl, info, (off, arr(sv.bases, np.uint8, int(off[-1])))
     finally:
         L.svth_bam_free(h)
 
@@ -266,11 +282,13 @@ def format_evidence(loci: np.ndarray, res: np.ndarray, ev: np.ndarray, header: b
 
 
 def format_calls(calls: np.ndarray, names, genotypes: np.ndarray | None = None, sample: str = "SAMPLE",
-                 header: bool = True, threads: int = 4) -> str:
+                 header: bool = True, threads: int = 4, consensus=None) -> str:
     """`svtrek call`'s VCF text of CALL_DTYPE records (svth_format_calls_gt); names: the BAM's reference
     names, names[chrom - 1] is a call's CHROM.  genotypes: one GT_DTYPE record per call
-    (`svtrek call --genotype`: FORMAT and a column named `sample`), or None for the sites-only VCF."""
-    from ._lib import CALL_DTYPE, GT_DTYPE
+    (`svtrek call --genotype`: FORMAT and a column named `sample`), or None for the sites-only VCF.
+    consensus: Engine.call_consensus's (res, bases) of all the calls (`svtrek call --ins-seq`,
+    svth_format_calls_seq: sequence ALTs, CONSLEN and CONSREADS), or None."""
+    from ._lib import CALL_DTYPE, GT_DTYPE, POA_RESULT_DTYPE
     L = load_host()
     calls = np.ascontiguousarray(calls, dtype=CALL_DTYPE)
     enc = [str(x).encode() for x in names]
@@ -281,10 +299,23 @@ def format_calls(calls: np.ndarray, names, genotypes: np.ndarray | None = None, 
             raise ValueError(f"format_calls: {len(calls)} calls but {len(genotypes)} genotypes")
         gts = np.ascontiguousarray(genotypes, dtype=GT_DTYPE) if len(calls) else np.zeros(1, dtype=GT_DTYPE)
     n = C.c_size_t(0)
-    p = L.svth_format_calls_gt(calls.ctypes.data if len(calls) else None, None if gts is None else gts.ctypes.data,
-                               len(calls), arr, len(enc), str(sample).encode(), int(header), threads, C.byref(n))
+    if consensus is None:
+        p = L.svth_format_calls_gt(calls.ctypes.data if len(calls) else None, None if gts is None else gts.ctypes.data,
+                                   len(calls), arr, len(enc), str(sample).encode(), int(header), threads, C.byref(n))
+    else:
+        res, bases = consensus
+        if len(res) != len(calls) or len(bases) != len(calls):
+            raise ValueError(f"format_calls: {len(calls)} calls but {len(res)} consensus records")
+        res = np.ascontiguousarray(res, dtype=POA_RESULT_DTYPE) if len(calls) else np.zeros(1, dtype=POA_RESULT_DTYPE)
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        cap = bases.shape[1] if bases.ndim == 2 else 0
+        if bases.size == 0:
+            bases = np.zeros(1, dtype=np.uint8)
+        p = L.svth_format_calls_seq(calls.ctypes.data if len(calls) else None, None if gts is None else gts.ctypes.data,
+                                    res.ctypes.data, bases.ctypes.data, cap, len(calls), arr, len(enc), str(sample).encode(),
+                                    int(header), threads, C.byref(n))
     if not p:
-        raise MemoryError("svth_format_calls_gt failed")
+        raise MemoryError("svth_format_calls failed")
     try:
         return C.string_at(p, n.value).decode("latin-1")
     finally:
