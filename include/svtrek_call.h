@@ -45,9 +45,46 @@
  * part.  After a scan with P = 0 every field is zero, and such a scan launches, allocates and reads
  * back exactly what it did before the split existed, whatever was scanned before it.
  *
+ * JOINING A READ'S FRAGMENTS (svt_call_params.merge_gap = G, merge_min = m).  An aligner often writes
+ * one long deletion of a noisy read as 180D 5M 120D.  With G = 0, the default, the items are exactly
+ * the ones above, merge_min is ignored, and a scan launches, allocates and reads back exactly what it
+ * did before the merge existed, whatever was scanned before it.  With G in 1 .. 2^20 (and m in
+ * 1 .. 50; 20 is the CLI's and Python's default) the items are MERGED ITEMS, defined per read of the
+ * pileup (no flag filter, as everywhere):
+ *   walk position  x is the item definition's -- the position before the op; H, P, N and the codes
+ *                  9-15 advance it, I and S do not -- but kept in 64 bits here, unsaturated.
+ *   FRAGMENT       of type DEL: a D op with len >= m; of type INS: an I op with len >= m.  Its TAIL is
+ *                  x + len for DEL and x for INS.
+ *   JOIN           take the fragments of one read and one type in CIGAR order: fragment j+1 joins
+ *                  fragment j iff x[j+1] - tail[j] <= G.  The two types never interact: a 40I between
+ *                  two D fragments moves nothing (an I does not advance x).  A 19D with m = 20 is no
+ *                  fragment; it only adds 19 to the distance.
+ *   RUN            a maximal chain of joined fragments (single linkage: three fragments each 40 apart
+ *                  at G = 50 are one run).
+ *   MERGED ITEM    a run of total L = sum len is an item iff L > 50 (DEL) / L >= 50 (INS).  The item is
+ *                  (x, len) = (min(x of the first fragment, 2^30), min(L, 2^28 - 1)) and carries its
+ *                  read's pos / endpos.
+ * Because m <= 50, every item of an unmerged scan is a fragment and ends in exactly one run: the merged
+ * items of a pileup in which no two fragments join and no lone fragment is shorter than the thresholds
+ * are the unmerged items.  Everything downstream is unchanged and runs on the merged items: clusters,
+ * min_support, the rounded means, ranges, depth and order; stats.events / skipped (now counts of merged
+ * items); the split by length; svt_genotype_calls, which genotypes against the index the LAST scan
+ * used, so that alt_all == support still holds for every call (svt_genotype_batch / _device keep
+ * using the plain items).  A DEL call's end stays the mean of x + len + 1 with the SUMMED len: the
+ * matched bases between the fragments are not counted, so end lies short of the last fragment's end by
+ * them.  svt_call_merge_stats describes the merge; every field is zero after a scan with G = 0.
+ * The merged items are a function of the pileup and (G, m) alone: they are built by the first scan that
+ * asks for them (stats.scan_ms does not include the build, merge stats' build_ms is its device time),
+ * kept until G or m change or the pileup is replaced or closed, and not touched by svt_reindex.  A
+ * context that never merges allocates nothing for them.
+ * Out of scope: inserted bases of merged calls (svt_call_consensus after a merged scan is
+ * SVT_ESTATE), sites genotyped against the merged items, several devices (the scan acts on the first,
+ * as before), and the CPU backend (no discovery there, as before).
+ *
  * Status codes: svt_call_scan is SVT_ESTATE before svt_load_pileup and when the value buckets are
  * not built (SVTREK_INDEX=lists, or a pileup too large for them); SVT_EINVAL on NULL arguments,
- * link < 0, link > 2^20, min_support < 1, len_permille > 1000, or no known type bit.  svt_call_fetch is SVT_EINVAL for a
+ * link < 0, link > 2^20, min_support < 1, len_permille > 1000, merge_gap > 2^20, merge_gap > 0 with
+ * merge_min outside 1 .. 50, or no known type bit; SVT_ESTATE for more than 2^31 - 1 merged items.  svt_call_fetch is SVT_EINVAL for a
  * range past the scanned count (n == 0 is SVT_OK).  svt_call_scan is ordered after every launch the
  * context has issued (svt_reindex included), selects / restores the device as the other entry
  * points do, acts on the first device of an svt_open_multi context, synchronises, and must not be
@@ -73,6 +110,7 @@ typedef struct svt_call_params {
     int32_t link, min_support;
     uint32_t types;                  /* bit SVT_INS | bit SVT_DEL: (1u << SVT_INS) | (1u << SVT_DEL) */
     uint32_t len_permille;           /* 0: clusters by start alone; 1 .. 1000: split by length (above) */
+    uint32_t merge_gap, merge_min;   /* 0: single ops as items; 1 .. 2^20: join a read's fragments of len >= merge_min (above) */
 } svt_call_params;
 
 typedef struct svt_call_stats {
@@ -90,7 +128,16 @@ typedef struct svt_call_split_stats {   /* all zero after a scan with len_permil
     uint64_t big;                    /* candidates of more items than the tile sort holds (sorted in device memory) */
 } svt_call_split_stats;
 
-/* link 10, min_support = the context's consensus_min_count (at least 1), both types, len_permille 0 */
+typedef struct svt_call_merge_stats {   /* all zero after a scan with merge_gap = 0 */
+    uint64_t fragments;              /* D / I ops of len >= merge_min, of both types whatever the scan's type bits */
+    uint64_t runs;                   /* maximal chains of joined fragments */
+    uint64_t joined_items;           /* merged items of >= 2 fragments */
+    uint64_t items;                  /* merged items (those with x >= 2^30 included) */
+    double build_ms;                 /* HIP-event time of the build of the merged items this scan ran on */
+} svt_call_merge_stats;
+
+/* link 10, min_support = the context's consensus_min_count (at least 1), both types, len_permille 0,
+ * merge_gap 0, merge_min 20 */
 void svt_call_default_params(const svt_ctx *ctx, svt_call_params *out);
 
 /* Synchronous; the calls stay on the device. */
@@ -106,6 +153,9 @@ svt_status svt_call_stats_get(const svt_ctx *ctx, svt_call_stats *out);
 
 /* The last scan's split by length. */
 svt_status svt_call_split_stats_get(const svt_ctx *ctx, svt_call_split_stats *out);
+
+/* The last scan's joining of fragments. */
+svt_status svt_call_merge_stats_get(const svt_ctx *ctx, svt_call_merge_stats *out);
 
 #ifdef __cplusplus
 }

@@ -45,11 +45,16 @@ class SvtGtParams(C.Structure):
 
 
 class SvtCallParams(C.Structure):
-    _fields_ = [("link", C.c_int32), ("min_support", C.c_int32), ("types", C.c_uint32), ("len_permille", C.c_uint32)]
+    _fields_ = [("link", C.c_int32), ("min_support", C.c_int32), ("types", C.c_uint32), ("len_permille", C.c_uint32),
+                ("merge_gap", C.c_uint32), ("merge_min", C.c_uint32)]
 
 
 class SvtCallSplitStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("candidates", "split", "groups", "big")]
+
+
+class SvtCallMergeStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("fragments", "runs", "joined_items", "items")] + [("build_ms", C.c_double)]
 
 
 class SvtCallStats(C.Structure):
@@ -162,6 +167,8 @@ EVIDENCE_SYMBOLS = ("svt_evidence_batch", "svt_evidence_device")
 CALL_SYMBOLS = ("svt_call_default_params", "svt_call_scan", "svt_call_fetch", "svt_call_device", "svt_call_stats_get")
 # its split statistics, added later: an engine without the getter still calls (Engine.call_split_stats raises)
 CALL_SPLIT_SYMBOLS = ("svt_call_split_stats_get",)
+# the joining of a read's fragments (svt_call_params.merge_gap), added later still: Engine.call(merge_gap=...) raises without it
+CALL_MERGE_SYMBOLS = ("svt_call_merge_stats_get",)
 # include/svtrek_genotype.h: likewise (Engine.genotype raises on a backend without it)
 GENOTYPE_SYMBOLS = ("svt_genotype_default_params", "svt_genotype_batch", "svt_genotype_device", "svt_genotype_calls")
 # include/svtrek_callseq.h: likewise (Engine.call_consensus raises on a backend without it)
@@ -268,6 +275,9 @@ def bind_abi(lib: C.CDLL) -> C.CDLL:
     if has_call_split(lib):
         lib.svt_call_split_stats_get.argtypes = [P, C.POINTER(SvtCallSplitStats)]
         lib.svt_call_split_stats_get.restype = C.c_int32
+    if has_call_merge(lib):
+        lib.svt_call_merge_stats_get.argtypes = [P, C.POINTER(SvtCallMergeStats)]
+        lib.svt_call_merge_stats_get.restype = C.c_int32
     if has_genotype(lib):
         lib.svt_genotype_default_params.argtypes = [P, C.POINTER(SvtGtParams)]
         lib.svt_genotype_default_params.restype = None
@@ -292,6 +302,11 @@ def has_callseq(lib: C.CDLL) -> bool:
 def has_genotype(lib: C.CDLL) -> bool:
     """Does the library export include/svtrek_genotype.h's entry points?"""
     return all(hasattr(lib, name) for name in GENOTYPE_SYMBOLS)
+
+
+def has_call_merge(lib: C.CDLL) -> bool:
+    """Does the library export svt_call_merge_stats_get (svt_call_params.merge_gap / merge_min)?"""
+    return has_call(lib) and all(hasattr(lib, name) for name in CALL_MERGE_SYMBOLS)
 
 
 def has_call_split(lib: C.CDLL) -> bool:

@@ -6,44 +6,72 @@ namespace {
 
 constexpr const char *CALL_MEM = "svt_call_scan: device scratch";
 
-// The first scan of a loaded pileup: the segments (the buckets' extents are those of the load for
-// every rebuild) and the scratch that depends on the event counts alone.
-svt_status call_prepare(svt_ctx *c) {
+// The index a scan runs on: the value buckets, or the merged index (merge_gap > 0) in their shape.
+// The segments depend on the extents, so each has its own; the rest of the scratch is shared and
+// only ever grown.
+struct CallView {
+    BkIndex bk;
+    uint64_t n_s, n_i;            // events of arrays S and I
+    bool *ready;
+    uint64_t *n_seg;
+    DevBuf<uint64_t> *d_seg;
+};
+CallView call_view(svt_ctx *c, bool merged) {
     CallScratch &k = c->call;
-    if (k.ready) return SVT_OK;
-    const uint64_t nb2 = 2 * c->bk_n, N = c->bk_events[BA_S] + c->bk_events[BA_I];
+    CallView v{make_args(c, nullptr, nullptr, 0, false).bk, c->bk_events[BA_S], c->bk_events[BA_I], &k.ready, &k.n_seg, &k.d_seg};
+    if (merged) {
+        v.bk.ev = k.mg.d_ev;
+        v.bk.off = k.mg.d_off;
+        v.bk.pm = nullptr;        // (the refine side's: no kernel of the scan or the genotypes reads it)
+        v.n_s = k.mg.events[0];
+        v.n_i = k.mg.events[1];
+        v.ready = &k.mg.ready;
+        v.n_seg = &k.mg.n_seg;
+        v.d_seg = &k.mg.d_seg;
+    }
+    return v;
+}
+
+// The first scan of a loaded pileup (of a merged index): the segments (the buckets' extents are those
+// of the load for every rebuild) and the scratch that depends on the event counts alone.
+svt_status call_prepare(svt_ctx *c, const CallView &v) {
+    CallScratch &k = c->call;
+    if (*v.ready) return SVT_OK;
+    const uint64_t nb2 = 2 * c->bk_n, N = v.n_s + v.n_i;
     svt_status s;
     DevBuf<uint8_t> d_flag;
-    if ((s = nomem(c, d_flag.reserve(nb2), CALL_MEM)) || (s = nomem(c, k.d_seg.reserve(nb2), CALL_MEM)) ||
+    DevBuf<uint64_t> &d_seg = *v.d_seg;
+    uint64_t &n_seg = *v.n_seg;
+    if ((s = nomem(c, d_flag.reserve(nb2), CALL_MEM)) || (s = nomem(c, d_seg.reserve(nb2), CALL_MEM)) ||
         (s = nomem(c, k.d_ctr.reserve(8), CALL_MEM)))
         return s;
-    BkIndex B = make_args(c, nullptr, nullptr, 0, false).bk;
+    const BkIndex &B = v.bk;
     hipLaunchKernelGGL(call_flag_kernel, dim3((unsigned)((nb2 + 255) / 256)), dim3(256), 0, nullptr, B, c->n_targets, d_flag);
     size_t tb = 0;
     hipcub::CountingInputIterator<uint64_t> it(0);
     uint64_t *d_n = reinterpret_cast<uint64_t *>(k.d_ctr.get());
-    HIP_TRY(c, hipcub::DeviceSelect::Flagged(nullptr, tb, it, d_flag.get(), k.d_seg.get(), d_n, (int)nb2, nullptr));
+    HIP_TRY(c, hipcub::DeviceSelect::Flagged(nullptr, tb, it, d_flag.get(), d_seg.get(), d_n, (int)nb2, nullptr));
     if ((s = nomem(c, k.d_tmp.reserve(tb), CALL_MEM))) return s;
-    HIP_TRY(c, hipcub::DeviceSelect::Flagged(k.d_tmp.get(), tb, it, d_flag.get(), k.d_seg.get(), d_n, (int)nb2, nullptr));
-    HIP_TRY(c, hipMemcpy(&k.n_seg, d_n, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipcub::DeviceSelect::Flagged(k.d_tmp.get(), tb, it, d_flag.get(), d_seg.get(), d_n, (int)nb2, nullptr));
+    HIP_TRY(c, hipMemcpy(&n_seg, d_n, 8, hipMemcpyDeviceToHost));
     d_flag.reset();
     if ((s = nomem(c, k.d_keys.reserve(std::max<uint64_t>(N, 1)), CALL_MEM)) ||
         (s = nomem(c, k.d_cid.reserve(std::max<uint64_t>(N, 1)), CALL_MEM)) ||
-        (s = nomem(c, k.d_tmax.reserve(k.n_seg), CALL_MEM)) || (s = nomem(c, k.d_tprev.reserve(k.n_seg), CALL_MEM)))
+        (s = nomem(c, k.d_tmax.reserve(n_seg), CALL_MEM)) || (s = nomem(c, k.d_tprev.reserve(n_seg), CALL_MEM)))
         return s;
     size_t t1 = 0, t2 = 0;
     HIP_TRY(c, hipcub::DeviceScan::ExclusiveScan(nullptr, t1, k.d_tmax.get(), k.d_tprev.get(), hipcub::Max(), 0ull,
-                                                 (int)k.n_seg, nullptr));
+                                                 (int)n_seg, nullptr));
     HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(nullptr, t2, k.d_cid.get(), k.d_cid.get(), (int)std::max<uint64_t>(N, 1), nullptr));
     if ((s = nomem(c, k.d_tmp.reserve(std::max(t1, t2)), CALL_MEM))) return s;
-    k.ready = true;
+    *v.ready = true;
     return SVT_OK;
 }
 
 // The split by length of a scan with len_permille > 0 (svt_call.inc), after call_accum_kernel: the
 // units' records into k.d_uacc in the order the calls take, their number and that of array S's into
 // *nu / *nu_s.  Its scratch is allocated here, by the first such scan, and freed with the pileup.
-svt_status call_split_1(svt_ctx *c, const CallArgs &a, uint32_t ncl, uint32_t ncl_s, uint32_t *nu, uint32_t *nu_s) {
+svt_status call_split_1(svt_ctx *c, const CallArgs &a, uint32_t n_keys, uint32_t ncl, uint32_t ncl_s, uint32_t *nu, uint32_t *nu_s) {
     CallScratch &k = c->call;
     svt_status s;
     if ((s = nomem(c, k.d_cflag.reserve(ncl), CALL_MEM)) || (s = nomem(c, k.d_cand.reserve(ncl), CALL_MEM)) ||
@@ -73,7 +101,7 @@ svt_status call_split_1(svt_ctx *c, const CallArgs &a, uint32_t ncl, uint32_t nc
     sp.kend = k.d_kend;
     sp.unit = k.d_unit;
     sp.stats = k.d_sctr;
-    sp.n_keys = (uint32_t)(c->bk_events[BA_S] + c->bk_events[BA_I]);
+    sp.n_keys = n_keys;
     const dim3 sg(ncand), sb(CALL_T);
     if (ncand) {
         if ((s = nomem(c, k.d_skeys.reserve(nkeys), CALL_MEM))) return s;
@@ -109,26 +137,34 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
     k.scanned = true;
     k.stats = svt_call_stats{};
     k.split = svt_call_split_stats{};
-    const uint64_t N = c->bk_events[BA_S] + c->bk_events[BA_I];
-    if (c->n_reads == 0 || N == 0) {
-        *n_calls = 0;
-        return SVT_OK;
-    }
+    k.merge = svt_call_merge_stats{};
+    const bool merged = p->merge_gap != 0u;
+    k.last_merged = merged;
+    *n_calls = 0;
+    if (c->n_reads == 0) return SVT_OK;
     svt_status s = order_on(c, nullptr);   // after every launch already issued (svt_reindex rebuilds the buckets)
     if (s) return s;
+    if (merged) {   // (before the scan's clock: the build runs once per pileup and (gap, min))
+        if ((s = callmerge_build(c, p->merge_gap, p->merge_min))) return s;
+        k.merge = k.mg.stats;
+    }
+    const CallView v = call_view(c, merged);
+    const uint64_t N = v.n_s + v.n_i;
+    if (N == 0) return SVT_OK;
     DevEvent e0, e1;
     HIP_TRY(c, e0.create());
     HIP_TRY(c, e1.create());
     HIP_TRY(c, hipEventRecord(e0, nullptr));
-    if ((s = call_prepare(c))) return s;
+    if ((s = call_prepare(c, v))) return s;
+    const uint64_t n_seg = *v.n_seg;
     const KArgs ka = make_args(c, nullptr, nullptr, 0, false);
     CallArgs a{};
-    a.bk = ka.bk;
+    a.bk = v.bk;
     a.pile = ka.pile;
     a.nt = c->n_targets;
-    a.n_s = (uint32_t)c->bk_events[BA_S];
-    a.n_seg = k.n_seg;
-    a.seg = k.d_seg;
+    a.n_s = (uint32_t)v.n_s;
+    a.n_seg = n_seg;
+    a.seg = v.d_seg->get();
     a.keys = k.d_keys;
     a.cid = k.d_cid;
     a.tmax = k.d_tmax;
@@ -139,12 +175,12 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
     a.min_support = (uint32_t)p->min_support;
     a.types = p->types;
     a.permille = p->len_permille;
-    const dim3 sg((unsigned)k.n_seg), sb(CALL_T);
+    const dim3 sg((unsigned)n_seg), sb(CALL_T);
     HIP_TRY(c, hipMemsetAsync(k.d_ctr, 0, 8 * sizeof(uint32_t), nullptr));
     hipLaunchKernelGGL(call_sort_kernel, sg, sb, 0, nullptr, a);
     size_t tb = k.d_tmp.cap();
     HIP_TRY(c, hipcub::DeviceScan::ExclusiveScan(k.d_tmp.get(), tb, k.d_tmax.get(), k.d_tprev.get(), hipcub::Max(), 0ull,
-                                                 (int)k.n_seg, nullptr));
+                                                 (int)n_seg, nullptr));
     hipLaunchKernelGGL(call_head_kernel, sg, sb, 0, nullptr, a);
     tb = k.d_tmp.cap();
     HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(k.d_tmp.get(), tb, k.d_cid.get(), k.d_cid.get(), (int)N, nullptr));
@@ -168,7 +204,7 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
         hipLaunchKernelGGL(call_accum_kernel, sg, sb, 0, nullptr, a);
         uint32_t nu = ncl, nu_s = ncl_s;   // what is picked from: the clusters, or the units of a split scan
         if (a.permille) {
-            if ((s = call_split_1(c, a, ncl, ncl_s, &nu, &nu_s))) return s;
+            if ((s = call_split_1(c, a, (uint32_t)N, ncl, ncl_s, &nu, &nu_s))) return s;
             need = 0;
             HIP_TRY(c, hipcub::DeviceSelect::Flagged(nullptr, need, it, k.d_flag.get(), k.d_pick.get(), k.d_ctr.get(), (int)nu, nullptr));
             if ((s = nomem(c, k.d_pick.reserve(nu), CALL_MEM)) || (s = nomem(c, k.d_flag.reserve(nu), CALL_MEM)) ||
@@ -225,6 +261,8 @@ void svt_call_default_params(const svt_ctx *c, svt_call_params *out) {
     out->min_support = c ? std::max(c->prm.consensus_min_count, 1) : 3;
     out->types = (1u << SVT_INS) | (1u << SVT_DEL);
     out->len_permille = 0;
+    out->merge_gap = 0;
+    out->merge_min = 20;
 }
 
 svt_status svt_call_scan(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) {
@@ -233,6 +271,8 @@ svt_status svt_call_scan(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls
     if (p->link < 0 || p->link > (1 << 20) || p->min_support < 1 || !(p->types & ((1u << SVT_INS) | (1u << SVT_DEL))))
         return fail(c, SVT_EINVAL, "%s", "svt_call_scan: link in [0, 2^20], min_support >= 1 and a type bit of DEL / INS");
     if (p->len_permille > 1000u) return fail(c, SVT_EINVAL, "%s", "svt_call_scan: len_permille in [0, 1000]");
+    if (p->merge_gap > (1u << 20) || (p->merge_gap != 0u && (p->merge_min < 1u || p->merge_min > (uint32_t)SV_MIN_LENGTH)))
+        return fail(c, SVT_EINVAL, "%s", "svt_call_scan: merge_gap in [0, 2^20] and, with it, merge_min in [1, 50]");
     if (!c->loaded) return fail(c, SVT_ESTATE, "%s", "svt_load_pileup not called");
     if (c->n_reads != 0 && !c->bk_ready)
         return fail(c, SVT_ESTATE, "%s",
@@ -270,5 +310,11 @@ svt_status svt_call_stats_get(const svt_ctx *c, svt_call_stats *out) {
 svt_status svt_call_split_stats_get(const svt_ctx *c, svt_call_split_stats *out) {
     if (!c || !out) return SVT_EINVAL;
     *out = c->call.split;
+    return SVT_OK;
+}
+
+svt_status svt_call_merge_stats_get(const svt_ctx *c, svt_call_merge_stats *out) {
+    if (!c || !out) return SVT_EINVAL;
+    *out = c->call.merge;
     return SVT_OK;
 }

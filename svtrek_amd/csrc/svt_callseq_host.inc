@@ -122,6 +122,8 @@ svt_status svt_call_consensus(svt_ctx *c, const svt_poa_params *p, uint64_t firs
     if (!c || !p) return SVT_EINVAL;
     if (!c->loaded) return fail(c, SVT_ESTATE, "%s", "svt_load_pileup not called");
     if (!c->call.scanned) return fail(c, SVT_ESTATE, "%s", "svt_call_consensus: no svt_call_scan of the loaded pileup");
+    if (c->call.last_merged)
+        return fail(c, SVT_ESTATE, "%s", "svt_call_consensus: the last scan merged fragments (merge_gap > 0): no inserted bases for merged calls");
     if (!c->insseq_loaded) return fail(c, SVT_ESTATE, "%s", "svt_load_insseq not called");
     if (first > c->call.n_calls || n > c->call.n_calls - first)
         return fail(c, SVT_EINVAL, "%s", "svt_call_consensus: range past the scanned calls");

@@ -90,6 +90,21 @@ struct CallScratch {
     DevBuf<unsigned long long> d_sctr;    // [0..3) split / groups / big, [3] the candidates (32 bits)
     DevBuf<CallAcc> d_gacc, d_uacc;       // per unit: the groups as accumulated / every unit in order
     svt_call_split_stats split{};
+    // the merged index (merge_gap > 0; svt_callmerge.inc, svt_callmerge_host.inc): nothing allocated
+    // before the first such scan, rebuilt when (gap, min) change, untouched by svt_reindex
+    struct Merged {
+        bool built = false;
+        uint32_t gap = 0, min_len = 0;    // what it was built for
+        DevBuf<uint4> d_ev;               // the merged items, array S's then array I's
+        DevBuf<uint32_t> d_off;           // [BA_N][bk_n + 1], rows S and I filled
+        uint64_t events[2] = {};          // DEL / INS items
+        bool ready = false;               // its own segments (they depend on the extents)
+        uint64_t n_seg = 0;
+        DevBuf<uint64_t> d_seg;
+        svt_call_merge_stats stats{};     // of the build
+    } mg;
+    bool last_merged = false;             // the last scan ran on the merged index (svt_genotype_calls, svt_call_consensus)
+    svt_call_merge_stats merge{};         // the last scan's (all zero after merge_gap = 0)
 };
 
 // svt_call_consensus's scratch (svt_callseq.inc, svt_callseq_host.inc): nothing allocated before the

@@ -18,12 +18,13 @@ svt_status gt_check(svt_ctx *c, const svt_gt_params *p, size_t n) {
 
 // One launch over n > 0 records of either kind, ordered after the context's earlier launches.
 template <typename Site>
-svt_status gt_launch(svt_ctx *c, const svt_gt_params *p, const Site *d_sites, size_t n, svt_gt *d_out, hipStream_t st) {
+svt_status gt_launch(svt_ctx *c, const svt_gt_params *p, const Site *d_sites, size_t n, svt_gt *d_out, hipStream_t st,
+                     bool merged = false) {
     const svt_status s = order_on(c, st);   // (svt_reindex rebuilds the buckets)
     if (s) return s;
     const KArgs ka = make_args(c, nullptr, nullptr, 0, false);
     GtArgs g{};
-    g.bk = ka.bk;
+    g.bk = merged ? call_view(c, true).bk : ka.bk;   // (svt_genotype_calls after a merged scan: the items it clustered)
     g.pile = ka.pile;
     g.prm = *p;
     g.nt = c->n_reads ? c->n_targets : 0;
@@ -78,7 +79,7 @@ svt_status svt_genotype_calls(svt_ctx *c, const svt_gt_params *p, svt_gt *out, u
     DEV_GUARD(c);
     svt_status s;
     if ((s = nomem(c, c->d_gt.reserve(n_out), "svt_genotype_calls: device buffer"))) return s;
-    if ((s = gt_launch(c, p, c->call.d_calls.get(), (size_t)n_out, c->d_gt.get(), nullptr))) return s;
+    if ((s = gt_launch(c, p, c->call.d_calls.get(), (size_t)n_out, c->d_gt.get(), nullptr, c->call.last_merged))) return s;
     HIP_TRY(c, hipStreamSynchronize(nullptr));
     HIP_TRY(c, hipMemcpy(out, c->d_gt, n_out * sizeof(svt_gt), hipMemcpyDeviceToHost));
     return SVT_OK;

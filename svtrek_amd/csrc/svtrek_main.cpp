@@ -38,6 +38,7 @@ extern "C" __typeof__(svt_call_scan) svt_call_scan __attribute__((weak));
 extern "C" __typeof__(svt_call_fetch) svt_call_fetch __attribute__((weak));
 extern "C" __typeof__(svt_call_stats_get) svt_call_stats_get __attribute__((weak));
 extern "C" __typeof__(svt_call_split_stats_get) svt_call_split_stats_get __attribute__((weak));
+extern "C" __typeof__(svt_call_merge_stats_get) svt_call_merge_stats_get __attribute__((weak));
 // include/svtrek_genotype.h likewise (`svtrek call --genotype`)
 extern "C" __typeof__(svt_genotype_default_params) svt_genotype_default_params __attribute__((weak));
 extern "C" __typeof__(svt_genotype_calls) svt_genotype_calls __attribute__((weak));
@@ -69,6 +70,11 @@ void call_usage() {
     printf("    --len-permille <num>              Split the calls of one start by length: a new allele where the sorted\n");
     printf("                                      lengths step by more than max(link, num/1000 of the shorter); 0: no split\n");
     printf("                                      [Default: 0]\n");
+    printf("    --merge-gap <num>                 Join a read's D (I) ops of at least --merge-min bases that lie within num\n");
+    printf("                                      bases of each other into one item of their summed length before calling\n");
+    printf("                                      (180D 5M 120D counts as one 300 bp deletion); 0: single ops only; not with\n");
+    printf("                                      --ins-seq [Default: 0]\n");
+    printf("    --merge-min <num>                 Shortest op joined by --merge-gap, in [1, 50] [Default: 20]\n");
     printf("    --genotype                        Genotype every call: a FORMAT and a sample column with GT:GQ:DR:DV:PL\n");
     printf("                                      [Default: a sites-only VCF]\n");
     printf("    --flank <num>                     Bases a read must cover on both sides of a call to count [Default: 50]\n");
@@ -575,7 +581,7 @@ int audit(int argc, char **argv) {
 int call_mode(int argc, char **argv) {
     const char *bam_path = nullptr, *out_path = nullptr, *sample = "SAMPLE";
     int threads = THREADS, verbose = 0, device = 0, gpu_inflate = -1, link = -1, min_support = -1, genotype = 0, flank = -1, len_permille = 0;
-    int ins_seq = 0, ins_cap = 4096;
+    int ins_seq = 0, ins_cap = 4096, merge_gap = 0, merge_min = -1;
     uint32_t types = (1u << SVT_INS) | (1u << SVT_DEL);
     static const option opts[] = {
         {"bam", required_argument, nullptr, 1}, {"output", required_argument, nullptr, 3},
@@ -585,7 +591,8 @@ int call_mode(int argc, char **argv) {
         {"types", required_argument, nullptr, 32}, {"genotype", no_argument, nullptr, 33},
         {"flank", required_argument, nullptr, 34}, {"sample", required_argument, nullptr, 35},
         {"len-permille", required_argument, nullptr, 36}, {"ins-seq", no_argument, nullptr, 37},
-        {"ins-seq-cap", required_argument, nullptr, 38}, {nullptr, 0, nullptr, 0}};
+        {"ins-seq-cap", required_argument, nullptr, 38}, {"merge-gap", required_argument, nullptr, 39},
+        {"merge-min", required_argument, nullptr, 40}, {nullptr, 0, nullptr, 0}};
     int opt, li;
     while ((opt = getopt_long(argc, argv, "b:o:t:h", opts, &li)) != -1) {
         switch (opt) {
@@ -623,6 +630,8 @@ int call_mode(int argc, char **argv) {
         case 36: len_permille = atoi(optarg); if (len_permille < 0 || len_permille > 1000) { fprintf(stderr, "[ERROR] --len-permille must be in [0, 1000]\n"); exit(EXIT_FAILURE); } break;
         case 37: ins_seq = 1; break;
         case 38: ins_cap = atoi(optarg); if (ins_cap < 1 || ins_cap > (1 << 20)) { fprintf(stderr, "[ERROR] --ins-seq-cap must be in [1, 1048576]\n"); exit(EXIT_FAILURE); } break;
+        case 39: merge_gap = atoi(optarg); if (merge_gap < 0 || merge_gap > (1 << 20)) { fprintf(stderr, "[ERROR] --merge-gap must be in [0, 1048576]\n"); exit(EXIT_FAILURE); } break;
+        case 40: merge_min = atoi(optarg); if (merge_min < 1 || merge_min > 50) { fprintf(stderr, "[ERROR] --merge-min must be in [1, 50]\n"); exit(EXIT_FAILURE); } break;
         default:
             printf("[ERROR] Option %d is invalid.\n", opt);
             call_usage();
@@ -631,6 +640,14 @@ int call_mode(int argc, char **argv) {
     }
     validate_file(bam_path, "[ERROR] BAM file is not provided.");
     if (threads < 1) { fprintf(stderr, "[ERROR] -t must be >= 1\n"); exit(EXIT_FAILURE); }
+    if (merge_gap && ins_seq) {   // (before any ingest: no inserted bases for merged calls)
+        fprintf(stderr, "[ERROR] --merge-gap cannot be combined with --ins-seq: merged calls have no consensus sequence\n");
+        return 1;
+    }
+    if (merge_gap && !svt_call_merge_stats_get) {
+        fprintf(stderr, "[ERROR] merge-gap: not supported by this backend\n");
+        return 1;
+    }
     if (genotype && (!svt_genotype_calls || !svt_genotype_default_params)) {
         fprintf(stderr, "[ERROR] genotype: not supported by this backend\n");
         return 1;
@@ -672,12 +689,16 @@ int call_mode(int argc, char **argv) {
     const double t_ingest = now_s();
     svt_pileup_view view{};
     svth_bam_view(bam, &view);
-    svt_call_params cp;
+    svt_call_params cp{};
     svt_call_default_params(ctx, &cp);
     if (link >= 0) cp.link = link;
     if (min_support >= 1) cp.min_support = min_support;
     cp.types = types;
     cp.len_permille = (uint32_t)len_permille;
+    if (merge_gap) {   // (a backend without the merge is refused above and never sees the two fields)
+        cp.merge_gap = (uint32_t)merge_gap;
+        cp.merge_min = (uint32_t)(merge_min >= 1 ? merge_min : 20);
+    }
     uint64_t n = 0;
     svt_status s = svt_load_pileup(ctx, &view);
     if (!s && ins_seq) {   // the inserted bases the ingest kept
@@ -746,6 +767,11 @@ int call_mode(int argc, char **argv) {
         fprintf(stderr, "[svtrek_amd] call: len-permille %d  candidates %llu  split %llu  groups %llu  big %llu\n", len_permille,
                 (unsigned long long)ss.candidates, (unsigned long long)ss.split, (unsigned long long)ss.groups,
                 (unsigned long long)ss.big);
+    svt_call_merge_stats ms{};
+    if (verbose && merge_gap && !svt_call_merge_stats_get(ctx, &ms))
+        fprintf(stderr, "[svtrek_amd] call: merge-gap %d  merge-min %u  fragments %llu  runs %llu  joined items %llu  items %llu  "
+                        "build %.3f ms\n", merge_gap, cp.merge_min, (unsigned long long)ms.fragments, (unsigned long long)ms.runs,
+                (unsigned long long)ms.joined_items, (unsigned long long)ms.items, ms.build_ms);
     return done(0);
 }
 

@@ -15,8 +15,8 @@ import numpy as np
 
 from ._lib import (CALL_DTYPE, EVIDENCE_DTYPE, GT_DTYPE, GT_SITE_DTYPE, LOCUS_DTYPE, POA_RESULT_DTYPE, RESULT_DTYPE,
                    STATUS_NAMES, SVT_DEL, SVT_EINVAL, SVT_INS, SVT_NA, SW_QUERY_DTYPE, SW_WINDOW_DTYPE, SvtCallConsensusStats,
-                   SvtCallParams, SvtCallSplitStats, SvtCallStats, SvtGtParams, SvtInsseqView, SvtLoadStats, SvtParams, SvtPoaParams,
-                   SvtWork, has_call, has_call_split, has_callseq, has_evidence, has_genotype, load_engine, ptr)
+                   SvtCallMergeStats, SvtCallParams, SvtCallSplitStats, SvtCallStats, SvtGtParams, SvtInsseqView, SvtLoadStats, SvtParams, SvtPoaParams,
+                   SvtWork, has_call, has_call_merge, has_call_split, has_callseq, has_evidence, has_genotype, load_engine, ptr)
 from .pileup import Pileup
 
 # params.h:27-32
@@ -142,16 +142,27 @@ class Engine:
             raise SvtError(SVT_EINVAL, "this backend does not export svt_call_split_stats_get: splitting calls by "
                                        "length (len_permille) needs engine 0.29.0 or later")
 
+    def _need_call_merge(self) -> None:
+        self._need_call()
+        if not has_call_merge(self.lib):
+            raise SvtError(SVT_EINVAL, "this backend does not export svt_call_merge_stats_get: joining a read's "
+                                       "fragments (merge_gap) needs engine 0.31.0 or later")
+
     def call(self, link: int | None = None, min_support: int | None = None, types=("DEL", "INS"),
-             len_permille: int | None = None) -> np.ndarray:
+             len_permille: int | None = None, merge_gap: int | None = None, merge_min: int | None = None) -> np.ndarray:
         """Cluster the pileup's D > 50 / I >= 50 ops by start (svt_call_scan): CALL_DTYPE records in
         (chrom, pos, type, len) order.  link: the largest gap between neighbouring starts of one
         cluster (default 10); min_support: the fewest ops of a call (default consensus_min_count);
         len_permille: 1 .. 1000 cuts every start cluster where its sorted lengths step by more than
-        max(link, len * len_permille / 1000), one call per allele (default 0: no split)."""
+        max(link, len * len_permille / 1000), one call per allele (default 0: no split);
+        merge_gap: 1 .. 2^20 joins a read's D (I) ops of at least merge_min bases (1 .. 50, default 20)
+        that lie within merge_gap bases of each other into one item of their summed length before
+        clustering -- 180D 5M 120D counts as one 300 bp deletion (default 0: single ops only)."""
         self._need_call()
         if len_permille:
             self._need_call_split()
+        if merge_gap:
+            self._need_call_merge()
         p = SvtCallParams()
         self.lib.svt_call_default_params(self._h, C.byref(p))
         if link is not None:
@@ -163,6 +174,13 @@ class Engine:
             if not 0 <= int(len_permille) <= 0xffffffff:
                 raise SvtError(SVT_EINVAL, "call: len_permille in [0, 1000]")
             p.len_permille = int(len_permille)
+        if merge_gap is not None or merge_min is not None:
+            self._need_call_merge()   # (an older engine never sees the two fields)
+            for name, v in (("merge_gap", merge_gap), ("merge_min", merge_min)):
+                if v is not None:
+                    if not 0 <= int(v) <= 0xffffffff:
+                        raise SvtError(SVT_EINVAL, "call: merge_gap in [0, 2^20], merge_min in [1, 50]")
+                    setattr(p, name, int(v))
         n = C.c_uint64(0)
         self._check(self.lib.svt_call_scan(self._h, C.byref(p), C.byref(n)))
         return self.call_fetch(0, n.value)
@@ -194,6 +212,13 @@ class Engine:
         st = SvtCallSplitStats()
         self._check(self.lib.svt_call_split_stats_get(self._h, C.byref(st)))
         return {k: int(getattr(st, k)) for k, _ in SvtCallSplitStats._fields_}
+
+    def call_merge_stats(self) -> dict:
+        """{fragments, runs, joined_items, items, build_ms} of the last call(): all zero without merge_gap."""
+        self._need_call_merge()
+        st = SvtCallMergeStats()
+        self._check(self.lib.svt_call_merge_stats_get(self._h, C.byref(st)))
+        return {k: (float(getattr(st, k)) if k == "build_ms" else int(getattr(st, k))) for k, _ in SvtCallMergeStats._fields_}
 
     # ---- consensus inserted sequence of the INS calls (include/svtrek_callseq.h)
     def _need_callseq(self) -> None:

@@ -18,6 +18,11 @@ with --hotspot-last, spread over 650 kb of the contig's last bucket (the in-memo
 adds the split statistics; the hot spot then gives every start two alternating lengths (D 60 + k % 50
 and ten times that): the regular bucket's 700 neighbouring starts are one candidate holding every
 item, the last bucket's starts, 13 apart, are one with --link 13 and 50 000 candidates without.
+
+--merge-gap N [--merge-min M] scans with svt_call_params.merge_gap = N (a read's fragmented D / I ops
+joined into merged items first) and adds the merge statistics, the build of the merged index
+(build_ms: --merge-builds builds, each forced by a scan at N + 1 in between) and the same process's
+plain scan (plain_scan_ms) next to the merged one.
 """
 from __future__ import annotations
 
@@ -93,8 +98,34 @@ def hotspot(a) -> None:
 
 
 def split_kw(a) -> dict:
-    """Engine.call's extra argument: none without --len-permille (an engine from before the split runs too)."""
-    return {"len_permille": a.len_permille} if a.len_permille else {}
+    """Engine.call's extra arguments: none without --len-permille / --merge-gap (an engine from before them runs too)."""
+    kw = {"len_permille": a.len_permille} if a.len_permille else {}
+    if a.merge_gap:
+        kw.update(merge_gap=a.merge_gap, merge_min=a.merge_min)
+    return kw
+
+
+def merge_out(a, eng, r=None) -> dict:
+    """The merge statistics, the build's time over --merge-builds builds and the plain scan beside it."""
+    if not a.merge_gap:
+        return {}
+    out = {"merge_gap": a.merge_gap, "merge_min": a.merge_min, "merge_stats": eng.call_merge_stats()}
+    kw = {k: v for k, v in split_kw(a).items() if k != "merge_gap"}
+    build = []
+    for _ in range(a.merge_builds):
+        eng.call(link=a.link, min_support=a.min_support, merge_gap=a.merge_gap + 1, **kw)   # another gap: the index is dropped
+        eng.call(link=a.link, min_support=a.min_support, merge_gap=a.merge_gap, **kw)
+        build.append(eng.call_merge_stats()["build_ms"])
+    plain = []
+    kw.pop("merge_min")
+    for k in range(a.warmup + a.repeat):
+        eng.call(link=a.link, min_support=a.min_support, **kw)
+        if k >= a.warmup:
+            plain.append(eng.call_stats()["scan_ms"])
+    out.update(build_ms=round(float(np.median(build)), 4), build_ms_all=[round(x, 4) for x in build],
+               plain_scan_ms=round(float(np.median(plain)), 4), plain_events=eng.call_stats()["events"],
+               plain_calls=eng.call_stats()["calls"])
+    return out
 
 
 def split_out(a, eng) -> dict:
@@ -110,6 +141,9 @@ def main() -> None:
     ap.add_argument("--min-support", type=int, default=None)
     ap.add_argument("--tol", type=int, default=10)
     ap.add_argument("--len-permille", type=int, default=0)
+    ap.add_argument("--merge-gap", type=int, default=0)
+    ap.add_argument("--merge-min", type=int, default=20)
+    ap.add_argument("--merge-builds", type=int, default=5)
     ap.add_argument("--hotspot", type=int, default=0)
     ap.add_argument("--hotspot-last", action="store_true")
     a = ap.parse_args()
@@ -154,7 +188,7 @@ def main() -> None:
         nops = np.diff(pl.cig_off.astype(np.int64))
         last = pl.cig_off[1:].astype(np.int64)[nops > 0] - 1
         markers = int(((pl.cigar[last] & 15) == 4).sum())
-    keys = st["events"] + markers
+    keys = st["events"] + (0 if a.merge_gap else markers)   # (the merged index holds items alone)
     alg = 16 * keys + 8 * keys + 2 * 8 * keys + 48 * st["calls"]
     print(json.dumps({
         "metric": "svt_call_scan ms (1 GPU)", "value": round(med, 4), "unit": "ms",
@@ -166,7 +200,7 @@ def main() -> None:
                   f"{a.repeat} after {a.warmup} warm-up scans; call_wall: Engine.call with the fetch; reindex: HIP events "
                   "around svt_reindex on one stream",
         "events": st["events"], "skipped": st["skipped"], "clusters": st["clusters"], "calls": st["calls"],
-        "big_buckets": st["big_buckets"], **split_out(a, eng), "events_read": keys,
+        "big_buckets": st["big_buckets"], **split_out(a, eng), **merge_out(a, eng), "events_read": keys,
         "alg_bytes_per_scan": alg, "alg_gbs": round(alg / (med * 1e-3) / 1e9, 2),
         "alg": "per event of arrays S and I (items + trailing-S markers): 16 B read + 8 B key written + 2 x 8 B key read; "
                "48 B per call",
