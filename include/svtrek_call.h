@@ -111,6 +111,7 @@ typedef struct svt_call_params {
     uint32_t types;                  /* bit SVT_INS | bit SVT_DEL: (1u << SVT_INS) | (1u << SVT_DEL) */
     uint32_t len_permille;           /* 0: clusters by start alone; 1 .. 1000: split by length (above) */
     uint32_t merge_gap, merge_min;   /* 0: single ops as items; 1 .. 2^20: join a read's fragments of len >= merge_min (above) */
+    uint32_t junctions;              /* 0: CIGAR items alone; 1: plus the items of split alignments (svtrek_junction.h) */
 } svt_call_params;
 
 typedef struct svt_call_stats {
@@ -137,7 +138,7 @@ typedef struct svt_call_merge_stats {   /* all zero after a scan with merge_gap 
 } svt_call_merge_stats;
 
 /* link 10, min_support = the context's consensus_min_count (at least 1), both types, len_permille 0,
- * merge_gap 0, merge_min 20 */
+ * merge_gap 0, merge_min 20, junctions 0 */
 void svt_call_default_params(const svt_ctx *ctx, svt_call_params *out);
 
 /* Synchronous; the calls stay on the device. */

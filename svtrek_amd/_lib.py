@@ -46,7 +46,7 @@ class SvtGtParams(C.Structure):
 
 class SvtCallParams(C.Structure):
     _fields_ = [("link", C.c_int32), ("min_support", C.c_int32), ("types", C.c_uint32), ("len_permille", C.c_uint32),
-                ("merge_gap", C.c_uint32), ("merge_min", C.c_uint32)]
+                ("merge_gap", C.c_uint32), ("merge_min", C.c_uint32), ("junctions", C.c_uint32)]
 
 
 class SvtCallSplitStats(C.Structure):
@@ -55,6 +55,19 @@ class SvtCallSplitStats(C.Structure):
 
 class SvtCallMergeStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("fragments", "runs", "joined_items", "items")] + [("build_ms", C.c_double)]
+
+
+class SvtCallJunctionStats(C.Structure):   # svt_call_junction_stats
+    _fields_ = [(n, C.c_uint64) for n in ("records", "segments", "junctions", "del_items", "ins_items", "other", "skipped")] + \
+        [("build_ms", C.c_double)]
+
+
+class SvtJunctionView(C.Structure):   # svt_junction_view
+    _fields_ = [("n", C.c_uint64), ("read", C.c_void_p), ("off", C.c_void_p), ("seg", C.c_void_p)]
+
+
+JUNCTION_SEG_DTYPE = np.dtype([("tid", "<i4"), ("strand", "<u4"), ("r_beg", "<u4"), ("r_end", "<u4"), ("q_beg", "<u4"),
+                               ("q_end", "<u4")])   # svt_junction_seg (24 B)
 
 
 class SvtCallStats(C.Structure):
@@ -169,6 +182,8 @@ CALL_SYMBOLS = ("svt_call_default_params", "svt_call_scan", "svt_call_fetch", "s
 CALL_SPLIT_SYMBOLS = ("svt_call_split_stats_get",)
 # the joining of a read's fragments (svt_call_params.merge_gap), added later still: Engine.call(merge_gap=...) raises without it
 CALL_MERGE_SYMBOLS = ("svt_call_merge_stats_get",)
+# include/svtrek_junction.h (svt_call_params.junctions), added with engine 0.32.0: Engine.call(junctions=True) raises without it
+JUNCTION_SYMBOLS = ("svt_load_junctions", "svt_call_junction_stats_get")
 # include/svtrek_genotype.h: likewise (Engine.genotype raises on a backend without it)
 GENOTYPE_SYMBOLS = ("svt_genotype_default_params", "svt_genotype_batch", "svt_genotype_device", "svt_genotype_calls")
 # include/svtrek_callseq.h: likewise (Engine.call_consensus raises on a backend without it)
@@ -278,6 +293,11 @@ def bind_abi(lib: C.CDLL) -> C.CDLL:
     if has_call_merge(lib):
         lib.svt_call_merge_stats_get.argtypes = [P, C.POINTER(SvtCallMergeStats)]
         lib.svt_call_merge_stats_get.restype = C.c_int32
+    if has_junctions(lib):
+        lib.svt_load_junctions.argtypes = [P, C.POINTER(SvtJunctionView)]
+        lib.svt_call_junction_stats_get.argtypes = [P, C.POINTER(SvtCallJunctionStats)]
+        for name in JUNCTION_SYMBOLS:
+            getattr(lib, name).restype = C.c_int32
     if has_genotype(lib):
         lib.svt_genotype_default_params.argtypes = [P, C.POINTER(SvtGtParams)]
         lib.svt_genotype_default_params.restype = None
@@ -302,6 +322,11 @@ def has_callseq(lib: C.CDLL) -> bool:
 def has_genotype(lib: C.CDLL) -> bool:
     """Does the library export include/svtrek_genotype.h's entry points?"""
     return all(hasattr(lib, name) for name in GENOTYPE_SYMBOLS)
+
+
+def has_junctions(lib: C.CDLL) -> bool:
+    """Does the library export include/svtrek_junction.h's entry points (svt_call_params.junctions)?"""
+    return has_call(lib) and all(hasattr(lib, name) for name in JUNCTION_SYMBOLS)
 
 
 def has_call_merge(lib: C.CDLL) -> bool:

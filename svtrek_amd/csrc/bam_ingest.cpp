@@ -30,6 +30,7 @@
 #include <numeric>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "svtrek_host.h"
@@ -521,6 +522,11 @@ struct svth_bam {
     RawVec<uint32_t> ins_cnt, ins_len;   // per read its I >= 50 ops; per op its length
     RawVec<uint64_t> ins_off;            // [n_ins + 1]
     RawVec<uint8_t> ins_bases;           // nt4 codes
+    // svth_bam_read_sa: the segment table of the kept reads that carry an SA:Z tag (include/svtrek_junction.h)
+    bool has_sa = false;
+    std::vector<uint64_t> sa_read, sa_off;   // sorted pileup read indices; [n + 1] rows
+    std::vector<svt_junction_seg> sa_seg;
+    int64_t n_sa_malformed = 0;          // records whose SA value did not parse (their row is dropped)
     double stage_s[6] = {0, 0, 0, 0, 0, 0};   // read, scan, alloc, inflate, wait, total
 };
 
@@ -565,8 +571,129 @@ inline void ins_extract(const bamrec::View &v, const uint8_t *r, uint32_t bs, ui
     }
 }
 
+// The value of the record's SA:Z tag (r: the record after its block_size word, bs: that word), found by
+// walking the aux fields as the CG restoration does: [*beg, *end) without the NUL.  False: no such tag
+// (or aux fields that cannot be walked).
+inline bool find_sa(const uint8_t *r, uint32_t bs, const uint8_t **beg, const uint8_t **vend) {
+    const uint8_t *end = r + bs;
+    const uint32_t l_qname = r[8], n_stored = bamrec::rd16(r + 12);
+    const int64_t l_seq = (int32_t)bamrec::rd32(r + 16);
+    if (l_seq < 0) return false;
+    const uint8_t *p = r + 32 + l_qname + 4ull * n_stored + (size_t)(l_seq + 1) / 2 + (size_t)l_seq;
+    while (p < end && end - p >= 3) {
+        const char t0 = (char)p[0], t1 = (char)p[1], ty = (char)p[2];
+        p += 3;
+        size_t sz = 0;
+        switch (ty) {
+        case 'A': case 'c': case 'C': sz = 1; break;
+        case 's': case 'S': sz = 2; break;
+        case 'i': case 'I': case 'f': sz = 4; break;
+        case 'Z': case 'H': {
+            const uint8_t *q = p;
+            while (q < end && *q) q++;
+            if (q >= end) return false;
+            if (ty == 'Z' && t0 == 'S' && t1 == 'A') { *beg = p; *vend = q; return true; }
+            p = q + 1;
+            continue;
+        }
+        case 'B': {
+            if (end - p < 5) return false;
+            const char sub = (char)p[0];
+            const uint64_t n = bamrec::rd32(p + 1);
+            const size_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2
+                              : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
+            if (!es || (uint64_t)(end - p - 5) < n * es) return false;
+            p += 5 + n * es;
+            continue;
+        }
+        default:
+            return false;
+        }
+        if ((size_t)(end - p) < sz) return false;
+        p += sz;
+    }
+    return false;
+}
+
+// One CIGAR as a segment's numbers: cl / ct the leading / trailing run of S and H, qlen the M I = X, rlen
+// the M D N = X (include/svtrek_junction.h).  False when a sum passes 32 bits.
+struct SegLen { uint64_t cl = 0, ct = 0, qlen = 0, rlen = 0; bool lead = true; };
+inline void seg_op(SegLen &g, uint32_t op, uint64_t len) {
+    const bool clip = op == bamrec::OP_S || op == 5u;
+    if (clip) { if (g.lead) g.cl += len; g.ct += len; }
+    else { g.lead = false; g.ct = 0; }
+    if (op == bamrec::OP_M || op == OP_I || op == bamrec::OP_EQ || op == bamrec::OP_X) g.qlen += len;
+    if (op == bamrec::OP_M || op == bamrec::OP_D || op == bamrec::OP_N || op == bamrec::OP_EQ || op == bamrec::OP_X) g.rlen += len;
+}
+inline bool seg_make(const SegLen &g, int32_t tid, uint32_t strand, uint64_t r_beg, svt_junction_seg *out) {
+    const uint64_t qb = strand ? g.ct : g.cl;
+    if (r_beg + g.rlen > 0xffffffffull || qb + g.qlen > 0xffffffffull) return false;
+    *out = svt_junction_seg{tid, strand, (uint32_t)r_beg, (uint32_t)(r_beg + g.rlen), (uint32_t)qb, (uint32_t)(qb + g.qlen)};
+    return true;
+}
+
+// The entries rname,pos,strand,CIGAR,mapQ,NM; of an SA value appended to `out`.  False -- a malformed
+// value -- for a missing or empty field, an unknown rname, an empty or invalid CIGAR, pos < 1 (or past
+// 2^31 - 1), a strand other than + / -, or an entry without its terminator.
+bool parse_sa(const uint8_t *p, const uint8_t *end, const std::unordered_map<std::string, int32_t> &tids,
+              std::vector<svt_junction_seg> &out) {
+    while (p < end) {
+        const uint8_t *semi = (const uint8_t *)memchr(p, ';', (size_t)(end - p));
+        if (!semi) return false;
+        const uint8_t *f[7];
+        int nf = 0;
+        f[nf++] = p;
+        for (const uint8_t *q = p; q < semi; q++)
+            if (*q == ',') {
+                if (nf == 6) return false;
+                f[nf++] = q + 1;
+            }
+        if (nf != 6) return false;
+        f[6] = semi + 1;
+        for (int k = 0; k < 6; k++)
+            if (f[k + 1] - f[k] < 2) return false;   // (an empty field: only its separator)
+        const auto it = tids.find(std::string((const char *)f[0], (size_t)(f[1] - f[0] - 1)));
+        if (it == tids.end()) return false;
+        uint64_t pos = 0;
+        for (const uint8_t *q = f[1]; q < f[2] - 1; q++) {
+            if (*q < '0' || *q > '9' || pos > 0x7fffffffull) return false;
+            pos = pos * 10 + (uint64_t)(*q - '0');
+        }
+        if (pos < 1 || pos > 0x7fffffffull) return false;
+        if (f[3] - f[2] != 2 || (*f[2] != '+' && *f[2] != '-')) return false;
+        SegLen g;
+        uint64_t len = 0;
+        bool digits = false;
+        for (const uint8_t *q = f[3]; q < f[4] - 1; q++) {
+            if (*q >= '0' && *q <= '9') {
+                len = len * 10 + (uint64_t)(*q - '0');
+                digits = true;
+                if (len > 0xfffffffull) return false;
+            } else {
+                static const char OPS[] = "MIDNSHP=X";
+                const char *o = (const char *)memchr(OPS, *q, 9);
+                if (!o || !digits) return false;
+                seg_op(g, (uint32_t)(o - OPS), len);
+                len = 0;
+                digits = false;
+            }
+        }
+        if (digits) return false;                     // (a length without its op)
+        for (int k = 4; k < 6; k++)                   // mapQ and NM: numbers, not otherwise read
+            for (const uint8_t *q = f[k]; q < f[k + 1] - 1; q++)
+                if (*q < '0' || *q > '9') return false;
+        svt_junction_seg sg;
+        if (!seg_make(g, it->second, *f[2] == '-' ? 1u : 0u, pos - 1, &sg)) return false;
+        out.push_back(sg);
+        p = semi + 1;
+    }
+    return true;
+}
+
+constexpr int WANT_SEQ = 1, WANT_SA = 2;
+
 svth_bam *bam_read_impl(const char *path, int threads, int32_t tid0, int64_t beg0, int32_t tid1, int64_t end1,
-                        const svth_inflater *inf, bool want_seq, char *err, size_t errcap);
+                        const svth_inflater *inf, int want, char *err, size_t errcap);
 
 }  // namespace
 
@@ -583,13 +710,29 @@ svth_bam *svth_bam_read_region(const char *path, int threads, int32_t tid0, int6
 
 svth_bam *svth_bam_read_ex(const char *path, int threads, int32_t tid0, int64_t beg0, int32_t tid1, int64_t end1,
                            const svth_inflater *inf, char *err, size_t errcap) {
-    return bam_read_impl(path, threads, tid0, beg0, tid1, end1, inf, false, err, errcap);
+    return bam_read_impl(path, threads, tid0, beg0, tid1, end1, inf, 0, err, errcap);
 }
 
 svth_bam *svth_bam_read_seq(const char *path, int threads, int32_t tid0, int64_t beg0, int32_t tid1, int64_t end1,
                             const svth_inflater *inf, char *err, size_t errcap) {
-    return bam_read_impl(path, threads, tid0, beg0, tid1, end1, inf, true, err, errcap);
+    return bam_read_impl(path, threads, tid0, beg0, tid1, end1, inf, WANT_SEQ, err, errcap);
 }
+
+svth_bam *svth_bam_read_sa(const char *path, int threads, int32_t tid0, int64_t beg0, int32_t tid1, int64_t end1,
+                           const svth_inflater *inf, char *err, size_t errcap) {
+    return bam_read_impl(path, threads, tid0, beg0, tid1, end1, inf, WANT_SA, err, errcap);
+}
+
+int svth_bam_junctions(const svth_bam *b, svt_junction_view *out) {
+    if (!b || !out || !b->has_sa) return 0;
+    out->n = b->sa_read.size();
+    out->read = b->sa_read.data();
+    out->off = b->sa_off.data();
+    out->seg = b->sa_seg.data();
+    return 1;
+}
+
+int64_t svth_bam_n_sa_malformed(const svth_bam *b) { return b ? b->n_sa_malformed : 0; }
 
 int svth_bam_insseq(const svth_bam *b, svt_insseq_view *out) {
     if (!b || !out || !b->has_seq) return 0;
@@ -604,8 +747,8 @@ int svth_bam_insseq(const svth_bam *b, svt_insseq_view *out) {
 namespace {
 
 svth_bam *bam_read_impl(const char *path, int threads, int32_t tid0, int64_t beg0, int32_t tid1, int64_t end1,
-                        const svth_inflater *inf, bool want_seq, char *err, size_t errcap) {
-    const bool region = tid0 >= 0;
+                        const svth_inflater *inf, int want, char *err, size_t errcap) {
+    const bool region = tid0 >= 0, want_seq = (want & WANT_SEQ) != 0, want_sa = (want & WANT_SA) != 0;
     auto fail = [&](const std::string &m) -> svth_bam * {
         if (err && errcap) snprintf(err, errcap, "%s", m.c_str());
         return nullptr;
@@ -679,6 +822,15 @@ svth_bam *bam_read_impl(const char *path, int threads, int32_t tid0, int64_t beg
     std::vector<uint32_t> insn;          // want_seq: per record its I >= 50 ops ...
     std::vector<uint64_t> insb;          //           ... and their bases
     uint64_t n_ins = 0, n_insb = 0;
+    // want_sa: per record of a chunk its rows (the own segment first; empty: no SA tag, or a malformed one),
+    // then per table record in file order its kept-read index and rows
+    std::unordered_map<std::string, int32_t> tids;
+    std::vector<std::vector<svt_junction_seg>> sa_rows;
+    std::vector<uint8_t> sa_bad;
+    std::vector<uint64_t> sa_read, sa_off(1, 0);
+    std::vector<svt_junction_seg> sa_seg;
+    if (want_sa)
+        for (int32_t t = 0; t < n_ref; t++) tids.emplace(b->names[(size_t)t], t);   // (the first of equal names)
     while (!done) {
         if (buf.size() - at < 4 && !need(4)) break;   // clean EOF
         // sequential boundary scan over the complete records in the buffer
@@ -751,11 +903,30 @@ svth_bam *bam_read_impl(const char *path, int threads, int32_t tid0, int64_t beg
             n_ins = ioff[nr];
             n_insb = iboff[nr];
         }
+        if (want_sa) {
+            sa_rows.assign(nr, {});
+            sa_bad.assign(nr, 0);
+        }
         parallel_for(rd.threads, nr, [&](size_t i0, size_t i1) {
             for (size_t i = i0; i < i1; i++) {
                 const bamrec::View &v = views[i];
                 if (!v.ok) continue;
                 const size_t k = slot[i];
+                const uint8_t *sa0, *sa1;
+                if (want_sa && find_sa(buf.data() + roff[i], rd32(buf.data() + roff[i] - 4), &sa0, &sa1)) {
+                    SegLen g;
+                    for (uint32_t j = 0; j < v.n; j++) {
+                        const uint32_t w = bamrec::rd32(v.cig + 4ull * j);
+                        seg_op(g, w & 0xfu, w >> 4);
+                    }
+                    if (v.flag & 4u) g.rlen = 0;   // (bam_endpos: an unmapped record covers no reference base)
+                    std::vector<svt_junction_seg> &rows = sa_rows[i];
+                    rows.resize(1);
+                    if (!seg_make(g, v.tid, (v.flag >> 4) & 1u, (uint64_t)v.pos, &rows[0]) || !parse_sa(sa0, sa1, tids, rows)) {
+                        rows.clear();
+                        sa_bad[i] = 1;
+                    }
+                }
                 uint32_t *dst = b->cigar.data() + narena + off[i];
                 if (v.n) memcpy(dst, v.cig, 4ull * v.n);
                 b->pos[k] = v.pos;
@@ -771,6 +942,14 @@ svth_bam *bam_read_impl(const char *path, int threads, int32_t tid0, int64_t beg
                 }
             }
         });
+        if (want_sa)
+            for (size_t i = 0; i < nr; i++) {
+                b->n_sa_malformed += sa_bad[i];
+                if (sa_rows[i].empty()) continue;
+                sa_read.push_back(slot[i]);
+                sa_seg.insert(sa_seg.end(), sa_rows[i].begin(), sa_rows[i].end());
+                sa_off.push_back(sa_seg.size());
+            }
         narena += off[nr];
         at = p;
     }
@@ -843,6 +1022,26 @@ svth_bam *bam_read_impl(const char *path, int threads, int32_t tid0, int64_t beg
             b->ins_bases.swap(bases2);
         }
         b->has_seq = true;
+    }
+    if (want_sa) {   // the table in the final read order: `read` holds sorted indices
+        const size_t m = sa_read.size();
+        std::vector<size_t> ord(m);
+        std::iota(ord.begin(), ord.end(), 0);
+        if (!sorted) {
+            std::vector<uint64_t> inv(n);
+            for (size_t k = 0; k < n; k++) inv[idx[k]] = k;
+            for (size_t j = 0; j < m; j++) sa_read[j] = inv[(size_t)sa_read[j]];
+            std::sort(ord.begin(), ord.end(), [&](size_t x, size_t y) { return sa_read[x] < sa_read[y]; });
+        }
+        b->sa_read.reserve(m);
+        b->sa_off.assign(1, 0);
+        b->sa_seg.reserve(sa_seg.size());
+        for (size_t j : ord) {
+            b->sa_read.push_back(sa_read[j]);
+            b->sa_seg.insert(b->sa_seg.end(), sa_seg.begin() + (ptrdiff_t)sa_off[j], sa_seg.begin() + (ptrdiff_t)sa_off[j + 1]);
+            b->sa_off.push_back(b->sa_seg.size());
+        }
+        b->has_sa = true;
     }
     return b;
 }

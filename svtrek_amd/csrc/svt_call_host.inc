@@ -6,9 +6,9 @@ namespace {
 
 constexpr const char *CALL_MEM = "svt_call_scan: device scratch";
 
-// The index a scan runs on: the value buckets, or the merged index (merge_gap > 0) in their shape.
-// The segments depend on the extents, so each has its own; the rest of the scratch is shared and
-// only ever grown.
+// The index a scan runs on: the value buckets, the merged index (merge_gap > 0) in their shape, or the
+// union of either with the junction events (junctions = 1).  The segments depend on the extents, so
+// each has its own; the rest of the scratch is shared and only ever grown.
 struct CallView {
     BkIndex bk;
     uint64_t n_s, n_i;            // events of arrays S and I
@@ -16,7 +16,7 @@ struct CallView {
     uint64_t *n_seg;
     DevBuf<uint64_t> *d_seg;
 };
-CallView call_view(svt_ctx *c, bool merged) {
+CallView call_view(svt_ctx *c, bool merged, bool junction = false) {
     CallScratch &k = c->call;
     CallView v{make_args(c, nullptr, nullptr, 0, false).bk, c->bk_events[BA_S], c->bk_events[BA_I], &k.ready, &k.n_seg, &k.d_seg};
     if (merged) {
@@ -29,8 +29,20 @@ CallView call_view(svt_ctx *c, bool merged) {
         v.n_seg = &k.mg.n_seg;
         v.d_seg = &k.mg.d_seg;
     }
+    if (junction) {               // (built on the view above: svt_junction_host.inc)
+        v.bk.ev = k.jn.d_ev;
+        v.bk.off = k.jn.d_off;
+        v.bk.pm = nullptr;
+        v.n_s = k.jn.events[0];
+        v.n_i = k.jn.events[1];
+        v.ready = &k.jn.ready;
+        v.n_seg = &k.jn.n_seg;
+        v.d_seg = &k.jn.d_seg;
+    }
     return v;
 }
+
+svt_status junction_build(svt_ctx *c, uint32_t gap, uint32_t min_len);   // svt_junction_host.inc
 
 // The first scan of a loaded pileup (of a merged index): the segments (the buckets' extents are those
 // of the load for every rebuild) and the scratch that depends on the event counts alone.
@@ -138,17 +150,28 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
     k.stats = svt_call_stats{};
     k.split = svt_call_split_stats{};
     k.merge = svt_call_merge_stats{};
-    const bool merged = p->merge_gap != 0u;
-    k.last_merged = merged;
+    k.junction = svt_call_junction_stats{};
+    const bool merged = p->merge_gap != 0u, junction = p->junctions != 0u;
+    k.last_merged = k.last_junction = false;   // (set once the index the scan runs on is built)
     *n_calls = 0;
-    if (c->n_reads == 0) return SVT_OK;
+    if (c->n_reads == 0) {   // (no index to build: every site of such a pileup is invalid)
+        k.last_merged = merged;
+        k.last_junction = junction;
+        return SVT_OK;
+    }
     svt_status s = order_on(c, nullptr);   // after every launch already issued (svt_reindex rebuilds the buckets)
     if (s) return s;
     if (merged) {   // (before the scan's clock: the build runs once per pileup and (gap, min))
         if ((s = callmerge_build(c, p->merge_gap, p->merge_min))) return s;
         k.merge = k.mg.stats;
     }
-    const CallView v = call_view(c, merged);
+    if (junction) {   // (likewise: once per pileup, table and base view)
+        if ((s = junction_build(c, p->merge_gap, p->merge_min))) return s;
+        k.junction = k.jn.stats;
+    }
+    k.last_merged = merged;
+    k.last_junction = junction;
+    const CallView v = call_view(c, merged, junction);
     const uint64_t N = v.n_s + v.n_i;
     if (N == 0) return SVT_OK;
     DevEvent e0, e1;
@@ -263,6 +286,7 @@ void svt_call_default_params(const svt_ctx *c, svt_call_params *out) {
     out->len_permille = 0;
     out->merge_gap = 0;
     out->merge_min = 20;
+    out->junctions = 0;
 }
 
 svt_status svt_call_scan(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) {
@@ -273,7 +297,10 @@ svt_status svt_call_scan(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls
     if (p->len_permille > 1000u) return fail(c, SVT_EINVAL, "%s", "svt_call_scan: len_permille in [0, 1000]");
     if (p->merge_gap > (1u << 20) || (p->merge_gap != 0u && (p->merge_min < 1u || p->merge_min > (uint32_t)SV_MIN_LENGTH)))
         return fail(c, SVT_EINVAL, "%s", "svt_call_scan: merge_gap in [0, 2^20] and, with it, merge_min in [1, 50]");
+    if (p->junctions > 1u) return fail(c, SVT_EINVAL, "%s", "svt_call_scan: junctions is 0 or 1");
     if (!c->loaded) return fail(c, SVT_ESTATE, "%s", "svt_load_pileup not called");
+    if (p->junctions && !c->call.jn.loaded)
+        return fail(c, SVT_ESTATE, "%s", "svt_call_scan: junctions = 1 without svt_load_junctions for the loaded pileup");
     if (c->n_reads != 0 && !c->bk_ready)
         return fail(c, SVT_ESTATE, "%s",
                     "svt_call_scan needs the value buckets (not built: SVTREK_INDEX=lists, or a pileup past 2^32 events)");

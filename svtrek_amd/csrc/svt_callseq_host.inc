@@ -124,6 +124,8 @@ svt_status svt_call_consensus(svt_ctx *c, const svt_poa_params *p, uint64_t firs
     if (!c->call.scanned) return fail(c, SVT_ESTATE, "%s", "svt_call_consensus: no svt_call_scan of the loaded pileup");
     if (c->call.last_merged)
         return fail(c, SVT_ESTATE, "%s", "svt_call_consensus: the last scan merged fragments (merge_gap > 0): no inserted bases for merged calls");
+    if (c->call.last_junction)
+        return fail(c, SVT_ESTATE, "%s", "svt_call_consensus: the last scan read split alignments (junctions = 1): no inserted bases for junction calls");
     if (!c->insseq_loaded) return fail(c, SVT_ESTATE, "%s", "svt_load_insseq not called");
     if (first > c->call.n_calls || n > c->call.n_calls - first)
         return fail(c, SVT_EINVAL, "%s", "svt_call_consensus: range past the scanned calls");

@@ -105,6 +105,26 @@ struct CallScratch {
     } mg;
     bool last_merged = false;             // the last scan ran on the merged index (svt_genotype_calls, svt_call_consensus)
     svt_call_merge_stats merge{};         // the last scan's (all zero after merge_gap = 0)
+    // the segment table and the union index (junctions = 1; svt_junction.inc, svt_junction_host.inc):
+    // nothing allocated before svt_load_junctions / the first such scan; the index is rebuilt when the
+    // table or the base view's (merge_gap, merge_min) change, untouched by svt_reindex
+    struct Junction {
+        bool loaded = false;              // a table for the loaded pileup (n == 0 included)
+        uint64_t n = 0, rows = 0;         // its records and segment rows
+        DevBuf<uint64_t> d_toff;          // [n + 1]
+        DevBuf<svt_junction_seg> d_tseg;  // [rows]
+        bool built = false;
+        uint32_t gap = 0, min_len = 0;    // the base view it was built on (gap 0: the plain buckets)
+        DevBuf<uint4> d_ev;               // the union's events, array S's then array I's
+        DevBuf<uint32_t> d_off;           // [BA_N][bk_n + 1], rows S and I filled
+        uint64_t events[2] = {};          // S / I events (the base view's non-items included)
+        bool ready = false;               // its own segments (they depend on the extents)
+        uint64_t n_seg = 0;
+        DevBuf<uint64_t> d_seg;
+        svt_call_junction_stats stats{};  // of the build
+    } jn;
+    bool last_junction = false;           // the last scan ran on the union index (svt_genotype_calls, svt_call_consensus)
+    svt_call_junction_stats junction{};   // the last scan's (all zero after junctions = 0)
 };
 
 // svt_call_consensus's scratch (svt_callseq.inc, svt_callseq_host.inc): nothing allocated before the

@@ -31,6 +31,8 @@
 //   svt_genotype.inc      genotypes of DEL / INS sites (host side: svt_genotype_host.inc)
 //   svt_callmerge.inc     a read's fragmented D / I ops joined into the merged index of svt_call_scan's
 //                         merge_gap (host side: svt_callmerge_host.inc)
+//   svt_junction.inc      DEL / INS items from split alignments filed beside the base view's events into the
+//                         union index of svt_call_scan's junctions (host side: svt_junction_host.inc)
 //   svt_index.inc, svt_index2.inc, svt_bucket_build.inc   the index builds (span lists, value buckets)
 //   svt_poa.inc, svt_poa_host.inc      allele consensus (POA): kernels, slot pools and poa_run
 //   svt_callseq.inc       consensus sequence of discovered INS calls: item table and support gather
@@ -60,9 +62,10 @@
 #include "../../include/svtrek_call.h"
 #include "../../include/svtrek_genotype.h"
 #include "../../include/svtrek_callseq.h"
+#include "../../include/svtrek_junction.h"
 #include "svt_bamrec.h"
 
-#define SVT_VERSION "svtrek_amd 0.31.0 (gfx950, value-bucketed event index filed by a lane-per-read walk with a 9-B LDS stage, band + prefix-max facts, packed span walk fed by readlane, lane vote on 64 windows a wave, BGZF inflate + BAM decode, DEL/INS discovery from the value buckets, genotypes from the events' own read extents, consensus sequence of INS calls, a read's fragmented D / I ops joined before calling)"
+#define SVT_VERSION "svtrek_amd 0.32.0 (gfx950, value-bucketed event index filed by a lane-per-read walk with a 9-B LDS stage, band + prefix-max facts, packed span walk fed by readlane, lane vote on 64 windows a wave, BGZF inflate + BAM decode, DEL/INS discovery from the value buckets, genotypes from the events' own read extents, consensus sequence of INS calls, a read's fragmented D / I ops joined before calling, DEL/INS items from split alignments)"
 
 namespace {
 
@@ -181,6 +184,7 @@ constexpr int LV_WMAX = 1023;   // band half-width for 16-bit offsets and prefix
 #include "svt_index2.inc"
 #include "svt_bucket_build.inc"
 #include "svt_callmerge.inc"
+#include "svt_junction.inc"
 #include "svt_poa.inc"
 #include "svt_callseq.inc"
 #include "svt_bam.inc"
@@ -1386,6 +1390,7 @@ svt_status svt_evidence_batch(svt_ctx *c, const svt_locus *loci, const svt_resul
 // ---- include/svtrek_call.h
 #include "svt_callmerge_host.inc"
 #include "svt_call_host.inc"
+#include "svt_junction_host.inc"
 
 // ---- include/svtrek_genotype.h
 #include "svt_genotype_host.inc"

@@ -13,7 +13,10 @@
 //   genotype       three 64-bit dot products and the PL arithmetic of the header, by every lane alike.
 // The 32-B record is stored by lanes 0-7, one word each.  The kernel is a template on the record it
 // reads: an svt_call is a site through its fields of the same names, so svt_genotype_calls runs on
-// the last scan's calls where they lie.
+// the last scan's calls where they lie.  JUNC (svt_genotype_calls after a scan with junctions = 1,
+// include/svtrek_junction.h) is the instantiation for the union index: an event whose word w has
+// JN_MARK set is a junction item, its extent the other 31 bits and word z; the junction items among
+// alt are counted apart and do not reduce ref (the halves of a split read do not span).
 static_assert(sizeof(svt_gt_site) == 32 && sizeof(svt_gt) == 32 && sizeof(svt_gt_params) == 32, "include/svtrek_genotype.h");
 
 struct GtArgs {
@@ -25,9 +28,10 @@ struct GtArgs {
 };
 
 // alt_all and alt of the items of array A (op `want`) in [x_lo, x_hi] x [len_lo, len_hi]; x_hi < 2^30.
+template <bool JUNC>
 __device__ __forceinline__ void gt_items(const BkIndex &B, int A, uint32_t want, int tid, uint32_t x_lo, uint32_t x_hi,
                                          uint32_t len_lo, uint32_t len_hi, int64_t a, int64_t b, uint32_t &alt_all,
-                                         uint32_t &alt) {
+                                         uint32_t &alt, uint32_t &alt_j) {
     const int ln = lane_id();
     uint32_t E0, E1;
     bk_range(B, A, tid, x_lo, x_hi, E0, E1);
@@ -36,13 +40,15 @@ __device__ __forceinline__ void gt_items(const BkIndex &B, int A, uint32_t want,
         const uint4 v = i < E1 ? B.ev[i] : make_uint4(0, 0, 0, 0);
         const uint32_t len = v.y >> 4;
         const bool item = i < E1 && (v.y & 0xfu) == want && v.x >= x_lo && v.x <= x_hi && len >= len_lo && len <= len_hi;
-        const bool spans = (int64_t)(int32_t)v.w <= a && (int64_t)(int32_t)v.z > b;   // v.w: the read's pos, v.z: its endpos
+        const uint32_t beg = JUNC ? v.w & 0x7fffffffu : v.w;
+        const bool spans = (int64_t)(int32_t)beg <= a && (int64_t)(int32_t)v.z > b;   // v.w: the read's pos, v.z: its endpos
         alt_all += (uint32_t)__popcll(ballot(item));
         alt += (uint32_t)__popcll(ballot(item && spans));
+        if (JUNC) alt_j += (uint32_t)__popcll(ballot(item && spans && (v.w >> 31) != 0u));
     }
 }
 
-template <typename Site>
+template <typename Site, bool JUNC = false>
 __global__ __launch_bounds__(64 * WPB) void genotype_kernel(GtArgs g, const Site *sites, svt_gt *out) {
     const uint32_t k = blockIdx.x * WPB + (threadIdx.x >> 6);
     if (k >= g.n) return;
@@ -59,12 +65,13 @@ __global__ __launch_bounds__(64 * WPB) void genotype_kernel(GtArgs g, const Site
         const int64_t a = max((int64_t)pos - (int64_t)g.prm.flank, (int64_t)0), b = (int64_t)end + (int64_t)g.prm.flank;
         const uint32_t span = span_reads(g.pile, tid, a, b);
         const uint32_t xh = min(x_hi, IX_SAT - 1u);
-        uint32_t alt_all = 0, alt = 0;
+        uint32_t alt_all = 0, alt = 0, alt_j = 0;
         if (x_lo <= xh) {
-            if (type == SVT_INS) gt_items(g.bk, BA_I, OP_INS, tid, x_lo, xh, len_lo, len_hi, a, b, alt_all, alt);
-            else gt_items(g.bk, BA_S, OP_DEL, tid, x_lo, xh, len_lo, len_hi, a, b, alt_all, alt);
+            if (type == SVT_INS) gt_items<JUNC>(g.bk, BA_I, OP_INS, tid, x_lo, xh, len_lo, len_hi, a, b, alt_all, alt, alt_j);
+            else gt_items<JUNC>(g.bk, BA_S, OP_DEL, tid, x_lo, xh, len_lo, len_hi, a, b, alt_all, alt, alt_j);
         }
-        const uint32_t ref = span > alt ? span - alt : 0u;
+        const uint32_t alt_r = alt - alt_j;   // the ALT items of spanning pileup records
+        const uint32_t ref = span > alt_r ? span - alt_r : 0u;
         w[0] = alt;
         w[1] = ref;
         w[2] = span;

@@ -19,17 +19,19 @@ svt_status gt_check(svt_ctx *c, const svt_gt_params *p, size_t n) {
 // One launch over n > 0 records of either kind, ordered after the context's earlier launches.
 template <typename Site>
 svt_status gt_launch(svt_ctx *c, const svt_gt_params *p, const Site *d_sites, size_t n, svt_gt *d_out, hipStream_t st,
-                     bool merged = false) {
+                     bool merged = false, bool junction = false) {
     const svt_status s = order_on(c, st);   // (svt_reindex rebuilds the buckets)
     if (s) return s;
     const KArgs ka = make_args(c, nullptr, nullptr, 0, false);
     GtArgs g{};
-    g.bk = merged ? call_view(c, true).bk : ka.bk;   // (svt_genotype_calls after a merged scan: the items it clustered)
+    g.bk = merged || junction ? call_view(c, merged, junction).bk : ka.bk;   // (svt_genotype_calls after a merged / junction scan: the items it clustered)
     g.pile = ka.pile;
     g.prm = *p;
     g.nt = c->n_reads ? c->n_targets : 0;
     g.n = (uint32_t)n;
-    hipLaunchKernelGGL(genotype_kernel<Site>, dim3((unsigned)((n + WPB - 1) / WPB)), dim3(64 * WPB), 0, st, g, d_sites, d_out);
+    const dim3 grid((unsigned)((n + WPB - 1) / WPB)), block(64 * WPB);
+    if (junction) hipLaunchKernelGGL((genotype_kernel<Site, true>), grid, block, 0, st, g, d_sites, d_out);
+    else hipLaunchKernelGGL(genotype_kernel<Site>, grid, block, 0, st, g, d_sites, d_out);
     HIP_TRY(c, hipGetLastError());
     return SVT_OK;
 }
@@ -79,7 +81,8 @@ svt_status svt_genotype_calls(svt_ctx *c, const svt_gt_params *p, svt_gt *out, u
     DEV_GUARD(c);
     svt_status s;
     if ((s = nomem(c, c->d_gt.reserve(n_out), "svt_genotype_calls: device buffer"))) return s;
-    if ((s = gt_launch(c, p, c->call.d_calls.get(), (size_t)n_out, c->d_gt.get(), nullptr, c->call.last_merged))) return s;
+    if ((s = gt_launch(c, p, c->call.d_calls.get(), (size_t)n_out, c->d_gt.get(), nullptr, c->call.last_merged, c->call.last_junction)))
+        return s;
     HIP_TRY(c, hipStreamSynchronize(nullptr));
     HIP_TRY(c, hipMemcpy(out, c->d_gt, n_out * sizeof(svt_gt), hipMemcpyDeviceToHost));
     return SVT_OK;

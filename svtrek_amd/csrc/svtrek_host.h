@@ -19,6 +19,7 @@
 #include "svtrek_call.h"
 #include "svtrek_genotype.h"
 #include "svtrek_callseq.h"
+#include "svtrek_junction.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -67,6 +68,19 @@ svth_bam *svth_bam_read_seq(const char *path, int threads, int32_t tid0, int64_t
                             const svth_inflater *inf, char *err, size_t errcap);
 /* Those sequences (valid until svth_bam_free): 1, or 0 for a pileup read without them. */
 int svth_bam_insseq(const svth_bam *b, svt_insseq_view *out);
+/* svth_bam_read_ex that also keeps the segment table of include/svtrek_junction.h -- what svt_load_junctions
+ * takes: one record for every kept read that carries an SA:Z tag (found by walking the aux fields, as the CG
+ * restoration does), its own segment from the CIGAR the pileup keeps (the CG-restored one included) and flag
+ * 0x10 (rlen 0 for an unmapped record, flag 4, as bam_endpos has it), then one row per entry rname,pos,strand,CIGAR,mapQ,NM; of the value in tag order (pos 1-based in the
+ * tag, 0-based in the row).  `read` holds indices of the final pileup, after the stable (tid, pos) sort when
+ * the file needed one.  A malformed value -- a missing or empty field, an unknown rname, an empty or invalid
+ * CIGAR, pos < 1, a strand other than + / -, an entry without its `;`, a number past 32 bits -- drops that
+ * record's row and is counted (svth_bam_n_sa_malformed); it is never an error for the file. */
+svth_bam *svth_bam_read_sa(const char *path, int threads, int32_t tid0, int64_t beg0, int32_t tid1, int64_t end1,
+                           const svth_inflater *inf, char *err, size_t errcap);
+/* That table (valid until svth_bam_free): 1, or 0 for a pileup read without it. */
+int svth_bam_junctions(const svth_bam *b, svt_junction_view *out);
+int64_t svth_bam_n_sa_malformed(const svth_bam *b);
 /* A BAM decoded on the device: the file read in batches of whole BGZF blocks (`threads`
  * parallel preads; buffers from sink->alloc when given, e.g. pinned memory) and handed to
  * sink->feed compressed -- the next batch read by a helper thread meanwhile.  The header is

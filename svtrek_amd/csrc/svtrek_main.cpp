@@ -39,6 +39,9 @@ extern "C" __typeof__(svt_call_fetch) svt_call_fetch __attribute__((weak));
 extern "C" __typeof__(svt_call_stats_get) svt_call_stats_get __attribute__((weak));
 extern "C" __typeof__(svt_call_split_stats_get) svt_call_split_stats_get __attribute__((weak));
 extern "C" __typeof__(svt_call_merge_stats_get) svt_call_merge_stats_get __attribute__((weak));
+// include/svtrek_junction.h likewise (`svtrek call --split-reads`)
+extern "C" __typeof__(svt_load_junctions) svt_load_junctions __attribute__((weak));
+extern "C" __typeof__(svt_call_junction_stats_get) svt_call_junction_stats_get __attribute__((weak));
 // include/svtrek_genotype.h likewise (`svtrek call --genotype`)
 extern "C" __typeof__(svt_genotype_default_params) svt_genotype_default_params __attribute__((weak));
 extern "C" __typeof__(svt_genotype_calls) svt_genotype_calls __attribute__((weak));
@@ -75,6 +78,9 @@ void call_usage() {
     printf("                                      (180D 5M 120D counts as one 300 bp deletion); 0: single ops only; not with\n");
     printf("                                      --ins-seq [Default: 0]\n");
     printf("    --merge-min <num>                 Shortest op joined by --merge-gap, in [1, 50] [Default: 20]\n");
+    printf("    --split-reads                     Also call from split alignments: a read written as two alignments linked\n");
+    printf("                                      by SA tags gives the deletion / insertion between them as one more item;\n");
+    printf("                                      not with --ins-seq [Default: CIGAR ops alone]\n");
     printf("    --genotype                        Genotype every call: a FORMAT and a sample column with GT:GQ:DR:DV:PL\n");
     printf("                                      [Default: a sites-only VCF]\n");
     printf("    --flank <num>                     Bases a read must cover on both sides of a call to count [Default: 50]\n");
@@ -581,7 +587,7 @@ int audit(int argc, char **argv) {
 int call_mode(int argc, char **argv) {
     const char *bam_path = nullptr, *out_path = nullptr, *sample = "SAMPLE";
     int threads = THREADS, verbose = 0, device = 0, gpu_inflate = -1, link = -1, min_support = -1, genotype = 0, flank = -1, len_permille = 0;
-    int ins_seq = 0, ins_cap = 4096, merge_gap = 0, merge_min = -1;
+    int ins_seq = 0, ins_cap = 4096, merge_gap = 0, merge_min = -1, split_reads = 0;
     uint32_t types = (1u << SVT_INS) | (1u << SVT_DEL);
     static const option opts[] = {
         {"bam", required_argument, nullptr, 1}, {"output", required_argument, nullptr, 3},
@@ -592,7 +598,7 @@ int call_mode(int argc, char **argv) {
         {"flank", required_argument, nullptr, 34}, {"sample", required_argument, nullptr, 35},
         {"len-permille", required_argument, nullptr, 36}, {"ins-seq", no_argument, nullptr, 37},
         {"ins-seq-cap", required_argument, nullptr, 38}, {"merge-gap", required_argument, nullptr, 39},
-        {"merge-min", required_argument, nullptr, 40}, {nullptr, 0, nullptr, 0}};
+        {"merge-min", required_argument, nullptr, 40}, {"split-reads", no_argument, nullptr, 41}, {nullptr, 0, nullptr, 0}};
     int opt, li;
     while ((opt = getopt_long(argc, argv, "b:o:t:h", opts, &li)) != -1) {
         switch (opt) {
@@ -632,6 +638,7 @@ int call_mode(int argc, char **argv) {
         case 38: ins_cap = atoi(optarg); if (ins_cap < 1 || ins_cap > (1 << 20)) { fprintf(stderr, "[ERROR] --ins-seq-cap must be in [1, 1048576]\n"); exit(EXIT_FAILURE); } break;
         case 39: merge_gap = atoi(optarg); if (merge_gap < 0 || merge_gap > (1 << 20)) { fprintf(stderr, "[ERROR] --merge-gap must be in [0, 1048576]\n"); exit(EXIT_FAILURE); } break;
         case 40: merge_min = atoi(optarg); if (merge_min < 1 || merge_min > 50) { fprintf(stderr, "[ERROR] --merge-min must be in [1, 50]\n"); exit(EXIT_FAILURE); } break;
+        case 41: split_reads = 1; break;
         default:
             printf("[ERROR] Option %d is invalid.\n", opt);
             call_usage();
@@ -642,6 +649,14 @@ int call_mode(int argc, char **argv) {
     if (threads < 1) { fprintf(stderr, "[ERROR] -t must be >= 1\n"); exit(EXIT_FAILURE); }
     if (merge_gap && ins_seq) {   // (before any ingest: no inserted bases for merged calls)
         fprintf(stderr, "[ERROR] --merge-gap cannot be combined with --ins-seq: merged calls have no consensus sequence\n");
+        return 1;
+    }
+    if (split_reads && ins_seq) {   // (before any ingest: no inserted bases for junction calls)
+        fprintf(stderr, "[ERROR] --split-reads cannot be combined with --ins-seq: calls from split alignments have no consensus sequence\n");
+        return 1;
+    }
+    if (split_reads && (!svt_load_junctions || !svt_call_junction_stats_get)) {
+        fprintf(stderr, "[ERROR] split-reads: not supported by this backend\n");
         return 1;
     }
     if (merge_gap && !svt_call_merge_stats_get) {
@@ -676,7 +691,7 @@ int call_mode(int argc, char **argv) {
     });
     char err[512];
     const svth_inflater dev_inf{device_inflate, device_host_alloc, device_host_free, &dinf, (size_t)1024 << 20};
-    svth_bam *bam = (ins_seq ? svth_bam_read_seq : svth_bam_read_ex)(bam_path, threads, -1, 0, -1, 0,
+    svth_bam *bam = (ins_seq ? svth_bam_read_seq : split_reads ? svth_bam_read_sa : svth_bam_read_ex)(bam_path, threads, -1, 0, -1, 0,
                                                                     gpu_inflate ? &dev_inf : nullptr, err, sizeof err);
     ot.join();
     auto done = [&](int rc) {
@@ -705,6 +720,12 @@ int call_mode(int argc, char **argv) {
         svt_insseq_view sv{};
         if (!svth_bam_insseq(bam, &sv)) { fprintf(stderr, "[ERROR] --ins-seq: the ingest kept no sequences\n"); return done(1); }
         s = svt_load_insseq(ctx, &sv);
+    }
+    if (!s && split_reads) {   // the segment table the ingest kept (a backend without it is refused above)
+        svt_junction_view jv{};
+        if (!svth_bam_junctions(bam, &jv)) { fprintf(stderr, "[ERROR] --split-reads: the ingest kept no segment table\n"); return done(1); }
+        s = svt_load_junctions(ctx, &jv);
+        cp.junctions = 1;
     }
     const double t_load = now_s();
     if (!s) s = svt_call_scan(ctx, &cp, &n);
@@ -772,6 +793,13 @@ int call_mode(int argc, char **argv) {
         fprintf(stderr, "[svtrek_amd] call: merge-gap %d  merge-min %u  fragments %llu  runs %llu  joined items %llu  items %llu  "
                         "build %.3f ms\n", merge_gap, cp.merge_min, (unsigned long long)ms.fragments, (unsigned long long)ms.runs,
                 (unsigned long long)ms.joined_items, (unsigned long long)ms.items, ms.build_ms);
+    svt_call_junction_stats js{};
+    if (verbose && split_reads && !svt_call_junction_stats_get(ctx, &js))
+        fprintf(stderr, "[svtrek_amd] call: split-reads  records %llu  segments %llu  junctions %llu  DEL items %llu  INS items %llu  "
+                        "other %llu  skipped %llu  malformed SA %lld  build %.3f ms\n", (unsigned long long)js.records,
+                (unsigned long long)js.segments, (unsigned long long)js.junctions, (unsigned long long)js.del_items,
+                (unsigned long long)js.ins_items, (unsigned long long)js.other, (unsigned long long)js.skipped,
+                (long long)svth_bam_n_sa_malformed(bam), js.build_ms);
     return done(0);
 }
 

@@ -13,10 +13,10 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import (CALL_DTYPE, EVIDENCE_DTYPE, GT_DTYPE, GT_SITE_DTYPE, LOCUS_DTYPE, POA_RESULT_DTYPE, RESULT_DTYPE,
+from ._lib import (CALL_DTYPE, EVIDENCE_DTYPE, GT_DTYPE, GT_SITE_DTYPE, JUNCTION_SEG_DTYPE, LOCUS_DTYPE, POA_RESULT_DTYPE, RESULT_DTYPE,
                    STATUS_NAMES, SVT_DEL, SVT_EINVAL, SVT_INS, SVT_NA, SW_QUERY_DTYPE, SW_WINDOW_DTYPE, SvtCallConsensusStats,
-                   SvtCallMergeStats, SvtCallParams, SvtCallSplitStats, SvtCallStats, SvtGtParams, SvtInsseqView, SvtLoadStats, SvtParams, SvtPoaParams,
-                   SvtWork, has_call, has_call_merge, has_call_split, has_callseq, has_evidence, has_genotype, load_engine, ptr)
+                   SvtCallJunctionStats, SvtCallMergeStats, SvtCallParams, SvtCallSplitStats, SvtCallStats, SvtGtParams, SvtInsseqView, SvtJunctionView, SvtLoadStats, SvtParams, SvtPoaParams,
+                   SvtWork, has_call, has_call_merge, has_call_split, has_callseq, has_evidence, has_genotype, has_junctions, load_engine, ptr)
 from .pileup import Pileup
 
 # params.h:27-32
@@ -148,8 +148,31 @@ class Engine:
             raise SvtError(SVT_EINVAL, "this backend does not export svt_call_merge_stats_get: joining a read's "
                                        "fragments (merge_gap) needs engine 0.31.0 or later")
 
+    def _need_junctions(self) -> None:
+        self._need_call()
+        if not has_junctions(self.lib):
+            raise SvtError(SVT_EINVAL, "this backend does not export svt_load_junctions (include/svtrek_junction.h): "
+                                       "calls from split alignments need the HIP engine 0.32.0 or later")
+
+    def load_junctions(self, read, off, seg) -> None:
+        """The segment table of the loaded pileup's records that carry an SA tag (svt_load_junctions,
+        include/svtrek_junction.h): read uint64 [n] ascending pileup read indices, off uint64 [n + 1], seg
+        JUNCTION_SEG_DTYPE rows, a record's own segment first.  host.read_bam(path, junctions=True) gives all three."""
+        self._need_junctions()
+        read = np.ascontiguousarray(read, dtype=np.uint64)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        seg = np.ascontiguousarray(seg, dtype=JUNCTION_SEG_DTYPE)
+        if len(off) != len(read) + 1 and not (len(read) == 0 and len(off) == 0):
+            raise SvtError(SVT_EINVAL, "load_junctions: off has one entry more than read")
+        if len(read) and int(off[-1]) != len(seg):
+            raise SvtError(SVT_EINVAL, "load_junctions: off[-1] is not the number of segment rows")
+        v = SvtJunctionView(len(read), ptr(read) if len(read) else None, ptr(off) if len(read) else None,
+                            ptr(seg) if len(seg) else None)
+        self._check(self.lib.svt_load_junctions(self._h, C.byref(v)))
+
     def call(self, link: int | None = None, min_support: int | None = None, types=("DEL", "INS"),
-             len_permille: int | None = None, merge_gap: int | None = None, merge_min: int | None = None) -> np.ndarray:
+             len_permille: int | None = None, merge_gap: int | None = None, merge_min: int | None = None,
+             junctions: bool = False) -> np.ndarray:
         """Cluster the pileup's D > 50 / I >= 50 ops by start (svt_call_scan): CALL_DTYPE records in
         (chrom, pos, type, len) order.  link: the largest gap between neighbouring starts of one
         cluster (default 10); min_support: the fewest ops of a call (default consensus_min_count);
@@ -157,8 +180,11 @@ class Engine:
         max(link, len * len_permille / 1000), one call per allele (default 0: no split);
         merge_gap: 1 .. 2^20 joins a read's D (I) ops of at least merge_min bases (1 .. 50, default 20)
         that lie within merge_gap bases of each other into one item of their summed length before
-        clustering -- 180D 5M 120D counts as one 300 bp deletion (default 0: single ops only)."""
+        clustering -- 180D 5M 120D counts as one 300 bp deletion (default 0: single ops only);
+        junctions: the DEL / INS items of split alignments (load_junctions) join the CIGAR items."""
         self._need_call()
+        if junctions:
+            self._need_junctions()
         if len_permille:
             self._need_call_split()
         if merge_gap:
@@ -181,6 +207,8 @@ class Engine:
                     if not 0 <= int(v) <= 0xffffffff:
                         raise SvtError(SVT_EINVAL, "call: merge_gap in [0, 2^20], merge_min in [1, 50]")
                     setattr(p, name, int(v))
+        if junctions:
+            p.junctions = 1
         n = C.c_uint64(0)
         self._check(self.lib.svt_call_scan(self._h, C.byref(p), C.byref(n)))
         return self.call_fetch(0, n.value)
@@ -219,6 +247,14 @@ class Engine:
         st = SvtCallMergeStats()
         self._check(self.lib.svt_call_merge_stats_get(self._h, C.byref(st)))
         return {k: (float(getattr(st, k)) if k == "build_ms" else int(getattr(st, k))) for k, _ in SvtCallMergeStats._fields_}
+
+    def call_junction_stats(self) -> dict:
+        """{records, segments, junctions, del_items, ins_items, other, skipped, build_ms} of the last call():
+        all zero without junctions."""
+        self._need_junctions()
+        st = SvtCallJunctionStats()
+        self._check(self.lib.svt_call_junction_stats_get(self._h, C.byref(st)))
+        return {k: (float(getattr(st, k)) if k == "build_ms" else int(getattr(st, k))) for k, _ in SvtCallJunctionStats._fields_}
 
     # ---- consensus inserted sequence of the INS calls (include/svtrek_callseq.h)
     def _need_callseq(self) -> None:

@@ -6,7 +6,7 @@ import os
 
 import numpy as np
 
-from ._lib import LOCUS_DTYPE, PKG, SvtInsseqView, SvtPileupView
+from ._lib import JUNCTION_SEG_DTYPE, LOCUS_DTYPE, PKG, SvtInsseqView, SvtJunctionView, SvtPileupView
 from .pileup import Pileup
 
 _host = None
@@ -32,6 +32,12 @@ def load_host() -> C.CDLL:
         L.svth_bam_read_seq.restype = P
         L.svth_bam_insseq.argtypes = [P, C.POINTER(SvtInsseqView)]
         L.svth_bam_insseq.restype = C.c_int
+        L.svth_bam_read_sa.argtypes = L.svth_bam_read_ex.argtypes
+        L.svth_bam_read_sa.restype = P
+        L.svth_bam_junctions.argtypes = [P, C.POINTER(SvtJunctionView)]
+        L.svth_bam_junctions.restype = C.c_int
+        L.svth_bam_n_sa_malformed.argtypes = [P]
+        L.svth_bam_n_sa_malformed.restype = C.c_int64
         L.svth_format_calls_seq.argtypes = [P, P, P, P, C.c_int32, C.c_size_t, P, C.c_size_t, C.c_char_p, C.c_int, C.c_int,
                                             C.POINTER(C.c_size_t)]
         L.svth_format_calls_seq.restype = P
@@ -148,18 +154,23 @@ def load_bam_device(engine, path: str, threads: int = 4, batch_bytes: int = 0, p
 
 
 def read_bam(path: str, threads: int = 4, region: tuple[int, int, int, int] | None = None,
-             inflate=None, batch_bytes: int = 0, pinned: bool = True, insseq: bool = False):
+             inflate=None, batch_bytes: int = 0, pinned: bool = True, insseq: bool = False, junctions: bool = False):
     """The BAM as a columnar pileup.  region = (tid0, beg0, tid1, end1): only the records from
     the BAI's linear-index offset of (tid0, beg0) up to the first at or past (tid1, end1)
     (svth_bam_read_region; needs `path`.bai) -- what one shard's queries can yield.
     inflate = an Engine: the BGZF blocks are inflated by its svt_bgzf_inflate (the device, in
     ~1 GiB batches overlapped with the record parse) instead of host threads.
     insseq = True (svth_bam_read_seq): the inserted bases of the kept reads' I >= 50 ops too, as
-    Engine.load_insseq takes them -- returns (pileup, info, (off, bases)) instead of (pileup, info)."""
+    Engine.load_insseq takes them -- returns (pileup, info, (off, bases)) instead of (pileup, info).
+    junctions = True (svth_bam_read_sa): the segment table of the kept reads' SA:Z tags too, as
+    Engine.load_junctions takes it -- returns (pileup, info, (read, off, seg)); info["sa_malformed"] counts the
+    records whose SA value did not parse (their rows are dropped)."""
+    if insseq and junctions:
+        raise ValueError("read_bam: insseq and junctions are separate reads")
     L = load_host()
     err = C.create_string_buffer(512)
     t0, b0, t1, e1 = (int(x) for x in region) if region is not None else (-1, 0, -1, 0)
-    reader = L.svth_bam_read_seq if insseq else L.svth_bam_read_ex
+    reader = L.svth_bam_read_seq if insseq else L.svth_bam_read_sa if junctions else L.svth_bam_read_ex
     if inflate is None:
         h = reader(path.encode(), threads, t0, b0, t1, e1, None, err, 512)
     else:
@@ -204,6 +215,15 @@ def read_bam(path: str, threads: int = 4, region: tuple[int, int, int, int] | No
         info = {"names": [L.svth_bam_target_name(h, t).decode() for t in range(nt)],
                 "records": int(L.svth_bam_n_records(h)), "cg_restored": int(L.svth_bam_n_cg_restored(h)),
                 "stage_s": dict(zip(("read", "scan", "alloc", "inflate", "wait", "total"), (round(x, 4) for x in st)))}
+        if junctions:
+            jv = SvtJunctionView()
+            if not L.svth_bam_junctions(h, C.byref(jv)):
+                raise OSError("svth_bam_junctions: the ingest kept no segment table")
+            info["sa_malformed"] = int(L.svth_bam_n_sa_malformed(h))
+            off = arr(jv.off, np.uint64, int(jv.n) + 1)
+            if len(off) == 0:
+                off = np.zeros(1, dtype=np.uint64)
+            return pl, info, (arr(jv.read, np.uint64, int(jv.n)), off, arr(jv.seg, JUNCTION_SEG_DTYPE, int(off[-1])))
         if not insseq:
             return pl, info
         sv = SvtInsseqView()

@@ -23,6 +23,13 @@ item, the last bucket's starts, 13 apart, are one with --link 13 and 50 000 cand
 joined into merged items first) and adds the merge statistics, the build of the merged index
 (build_ms: --merge-builds builds, each forced by a scan at N + 1 in between) and the same process's
 plain scan (plain_scan_ms) next to the merged one.
+
+--junctions SHARE cuts that share of the workload's D > 50 / I >= 50 ops into two records plus segment-table
+rows with the model's cut helper (tests/junction_ref.py; the simulator writes no SA), scans with
+svt_call_params.junctions = 1 and adds the junction statistics, the build of the union index (--merge-builds
+builds, each forced by reloading the table) with its algorithmic bytes -- the base events copied once (16 B read
++ 16 B written), 24 B per segment row, 16 B per junction event -- the same process's plain scan and, for scale, the merged index's build at gap 50 on the side.  The cut is
+pure Python, one read at a time: --loci N shrinks the workload to N loci for it.
 """
 from __future__ import annotations
 
@@ -128,6 +135,51 @@ def merge_out(a, eng, r=None) -> dict:
     return out
 
 
+def junction_cut(a, pl):
+    """(pileup, table) with --junctions' share of the D > 50 / I >= 50 ops cut (at most one a read)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import junction_ref as J
+    rng = np.random.default_rng(1)
+    which = []
+    for r in range(pl.n_reads):
+        ops = J.parse_cigar(pl.read_cigar(r))
+        cand = [j for j, (op, ln) in enumerate(ops) if ((op == 2 and ln > 50) or (op == 1 and ln >= 50)) and J.cuttable(ops, j)]
+        if cand and rng.random() < a.junctions:
+            which.append((r, cand[int(rng.integers(len(cand)))]))
+    out, table, _ = J.cut(pl, which)
+    out.clip = None
+    return out, table
+
+
+def junction_out(a, eng, table) -> dict:
+    """The junction statistics, the union build's time over --merge-builds builds, its bytes, the plain scan beside it."""
+    if not a.junctions:
+        return {}
+    js = eng.call_junction_stats()
+    kw = split_kw(a)
+    build = []
+    for _ in range(a.merge_builds):
+        eng.load_junctions(*table)   # the same table again: the index is dropped
+        eng.call(link=a.link, min_support=a.min_support, junctions=True, **kw)
+        build.append(eng.call_junction_stats()["build_ms"])
+    plain = []
+    for k in range(a.warmup + a.repeat):
+        eng.call(link=a.link, min_support=a.min_support, **kw)
+        if k >= a.warmup:
+            plain.append(eng.call_stats()["scan_ms"])
+    side = {}
+    if not a.merge_gap:   # for scale: the merged index's build on the side (the union stays on the plain view)
+        mb = []
+        for _ in range(a.merge_builds):
+            eng.call(link=a.link, min_support=a.min_support, merge_gap=51, merge_min=a.merge_min, **kw)   # another gap: the index is dropped
+            eng.call(link=a.link, min_support=a.min_support, merge_gap=50, merge_min=a.merge_min, **kw)
+            mb.append(eng.call_merge_stats()["build_ms"])
+        side = {"merged_build_ms": round(float(np.median(mb)), 4), "merged_build_ms_all": [round(x, 4) for x in mb]}
+    return {**side, "junctions": a.junctions, "junction_stats": js, "junction_build_ms": round(float(np.median(build)), 4),
+            "junction_build_ms_all": [round(x, 4) for x in build], "plain_scan_ms": round(float(np.median(plain)), 4),
+            "plain_events": eng.call_stats()["events"], "plain_calls": eng.call_stats()["calls"]}
+
+
 def split_out(a, eng) -> dict:
     return {"len_permille": a.len_permille, "split_stats": eng.call_split_stats()} if a.len_permille else {}
 
@@ -144,6 +196,8 @@ def main() -> None:
     ap.add_argument("--merge-gap", type=int, default=0)
     ap.add_argument("--merge-min", type=int, default=20)
     ap.add_argument("--merge-builds", type=int, default=5)
+    ap.add_argument("--junctions", type=float, default=0.0)
+    ap.add_argument("--loci", type=int, default=0)
     ap.add_argument("--hotspot", type=int, default=0)
     ap.add_argument("--hotspot-last", action="store_true")
     a = ap.parse_args()
@@ -152,10 +206,19 @@ def main() -> None:
         return
 
     t0 = time.perf_counter()
-    r = sim.generate(sim.WORKLOADS[a.workload])
+    cfg = sim.WORKLOADS[a.workload]
+    if a.loci:
+        from dataclasses import replace
+        cfg = replace(cfg, n_loci=a.loci)
+    r = sim.generate(cfg)
+    table = None
+    if a.junctions:
+        r.pileup, table = junction_cut(a, r.pileup)
     t_gen = time.perf_counter() - t0
     eng = Engine(Params(), device=0)
     eng.load_pileup(r.pileup)
+    if table is not None:
+        eng.load_junctions(*table)
     import torch
     s = torch.cuda.Stream()
 
@@ -172,7 +235,7 @@ def main() -> None:
     calls = None
     for k in range(a.warmup + a.repeat):
         t0 = time.perf_counter()
-        calls = eng.call(link=a.link, min_support=a.min_support, **split_kw(a))
+        calls = eng.call(link=a.link, min_support=a.min_support, **split_kw(a), **({"junctions": True} if a.junctions else {}))
         t1 = time.perf_counter()
         if k >= a.warmup:
             scan_ms.append(eng.call_stats()["scan_ms"])
@@ -189,6 +252,11 @@ def main() -> None:
         last = pl.cig_off[1:].astype(np.int64)[nops > 0] - 1
         markers = int(((pl.cigar[last] & 15) == 4).sum())
     keys = st["events"] + (0 if a.merge_gap else markers)   # (the merged index holds items alone)
+    jout = junction_out(a, eng, table)
+    if jout:   # the union's build: the base events copied once, the table's rows read, the junction events written
+        js = jout["junction_stats"]
+        base = keys - js["del_items"] - js["ins_items"]
+        jout["junction_build_alg_bytes"] = 32 * base + 24 * js["segments"] + 16 * (js["del_items"] + js["ins_items"])
     alg = 16 * keys + 8 * keys + 2 * 8 * keys + 48 * st["calls"]
     print(json.dumps({
         "metric": "svt_call_scan ms (1 GPU)", "value": round(med, 4), "unit": "ms",
@@ -200,7 +268,7 @@ def main() -> None:
                   f"{a.repeat} after {a.warmup} warm-up scans; call_wall: Engine.call with the fetch; reindex: HIP events "
                   "around svt_reindex on one stream",
         "events": st["events"], "skipped": st["skipped"], "clusters": st["clusters"], "calls": st["calls"],
-        "big_buckets": st["big_buckets"], **split_out(a, eng), **merge_out(a, eng), "events_read": keys,
+        "big_buckets": st["big_buckets"], **split_out(a, eng), **merge_out(a, eng), **jout, "events_read": keys,
         "alg_bytes_per_scan": alg, "alg_gbs": round(alg / (med * 1e-3) / 1e9, 2),
         "alg": "per event of arrays S and I (items + trailing-S markers): 16 B read + 8 B key written + 2 x 8 B key read; "
                "48 B per call",
