@@ -73,7 +73,8 @@
  * junctions > 1; SVT_ESTATE for junctions = 1 without a table for the loaded pileup (a new
  * svt_load_pileup drops it) and for more than 2^31 - 1 union items.  svt_call_consensus after a scan
  * with junctions = 1 is SVT_ESTATE.
- * Out of scope: inversions, duplications, translocations and BND records (counted in other), MAPQ or
+ * Out of scope: inversions and duplications (counted in other here; include/svtrek_rearr.h calls them
+ * from the same table), translocations and BND records (counted in other), MAPQ or
  * flag filters, a per-call count of junction support, inserted bases of junction calls, SA in the device
  * BAM decoder, several devices and the CPU backend.
  */

@@ -46,7 +46,8 @@ class SvtGtParams(C.Structure):
 
 class SvtCallParams(C.Structure):
     _fields_ = [("link", C.c_int32), ("min_support", C.c_int32), ("types", C.c_uint32), ("len_permille", C.c_uint32),
-                ("merge_gap", C.c_uint32), ("merge_min", C.c_uint32), ("junctions", C.c_uint32)]
+                ("merge_gap", C.c_uint32), ("merge_min", C.c_uint32), ("junctions", C.c_uint32),
+                ("rearr", C.c_uint32)]   # (rearr: engine 0.33.0; an older engine neither sets nor reads it)
 
 
 class SvtCallSplitStats(C.Structure):
@@ -60,6 +61,10 @@ class SvtCallMergeStats(C.Structure):
 class SvtCallJunctionStats(C.Structure):   # svt_call_junction_stats
     _fields_ = [(n, C.c_uint64) for n in ("records", "segments", "junctions", "del_items", "ins_items", "other", "skipped")] + \
         [("build_ms", C.c_double)]
+
+
+class SvtCallRearrStats(C.Structure):   # svt_call_rearr_stats
+    _fields_ = [(n, C.c_uint64) for n in ("dup_items", "inv_items", "skipped", "clusters", "calls")] + [("build_ms", C.c_double)]
 
 
 class SvtJunctionView(C.Structure):   # svt_junction_view
@@ -184,6 +189,8 @@ CALL_SPLIT_SYMBOLS = ("svt_call_split_stats_get",)
 CALL_MERGE_SYMBOLS = ("svt_call_merge_stats_get",)
 # include/svtrek_junction.h (svt_call_params.junctions), added with engine 0.32.0: Engine.call(junctions=True) raises without it
 JUNCTION_SYMBOLS = ("svt_load_junctions", "svt_call_junction_stats_get")
+# include/svtrek_rearr.h (svt_call_params.rearr), added with engine 0.33.0: Engine.call(rearrangements=...) raises without it
+REARR_SYMBOLS = ("svt_call_rearr_stats_get",)
 # include/svtrek_genotype.h: likewise (Engine.genotype raises on a backend without it)
 GENOTYPE_SYMBOLS = ("svt_genotype_default_params", "svt_genotype_batch", "svt_genotype_device", "svt_genotype_calls")
 # include/svtrek_callseq.h: likewise (Engine.call_consensus raises on a backend without it)
@@ -298,6 +305,9 @@ def bind_abi(lib: C.CDLL) -> C.CDLL:
         lib.svt_call_junction_stats_get.argtypes = [P, C.POINTER(SvtCallJunctionStats)]
         for name in JUNCTION_SYMBOLS:
             getattr(lib, name).restype = C.c_int32
+    if has_rearr(lib):
+        lib.svt_call_rearr_stats_get.argtypes = [P, C.POINTER(SvtCallRearrStats)]
+        lib.svt_call_rearr_stats_get.restype = C.c_int32
     if has_genotype(lib):
         lib.svt_genotype_default_params.argtypes = [P, C.POINTER(SvtGtParams)]
         lib.svt_genotype_default_params.restype = None
@@ -327,6 +337,11 @@ def has_genotype(lib: C.CDLL) -> bool:
 def has_junctions(lib: C.CDLL) -> bool:
     """Does the library export include/svtrek_junction.h's entry points (svt_call_params.junctions)?"""
     return has_call(lib) and all(hasattr(lib, name) for name in JUNCTION_SYMBOLS)
+
+
+def has_rearr(lib: C.CDLL) -> bool:
+    """Does the library export include/svtrek_rearr.h's entry point (svt_call_params.rearr)?"""
+    return has_junctions(lib) and all(hasattr(lib, name) for name in REARR_SYMBOLS)
 
 
 def has_call_merge(lib: C.CDLL) -> bool:

@@ -44,7 +44,7 @@ def _engine_deps() -> list[str]:
     return [os.path.join(CSRC, "svt_engine.hip")] + incs + \
         [os.path.join(CSRC, "svt_bamrec.h"), os.path.join(INC, "svtrek_gpu.h"), os.path.join(INC, "svtrek_evidence.h"),
             os.path.join(INC, "svtrek_call.h"), os.path.join(INC, "svtrek_genotype.h"), os.path.join(INC, "svtrek_callseq.h"),
-            os.path.join(INC, "svtrek_junction.h")]
+            os.path.join(INC, "svtrek_junction.h"), os.path.join(INC, "svtrek_rearr.h")]
 
 
 def build_engine(force: bool = False) -> str:
@@ -73,7 +73,7 @@ def build_host(force: bool = False) -> str:
     srcs = [os.path.join(CSRC, f) for f in ("bam_ingest.cpp", "vcf_audit.cpp")]
     hdrs = [os.path.join(CSRC, "svtrek_host.h"), os.path.join(INC, "svtrek_gpu.h"), os.path.join(INC, "svtrek_evidence.h"),
             os.path.join(INC, "svtrek_call.h"), os.path.join(INC, "svtrek_genotype.h"), os.path.join(INC, "svtrek_callseq.h"),
-            os.path.join(INC, "svtrek_junction.h"), os.path.join(CSRC, "svt_bamrec.h")]
+            os.path.join(INC, "svtrek_junction.h"), os.path.join(INC, "svtrek_rearr.h"), os.path.join(CSRC, "svt_bamrec.h")]
     if all(os.path.exists(s) for s in srcs) and (force or _stale(out, srcs + hdrs)):
         _run(["g++", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-pthread",
               "-I", INC, "-o", out] + srcs + ["-lz", "-ldl"])
@@ -86,7 +86,7 @@ def build_cli(force: bool = False) -> str:
     srcs = [main] + [os.path.join(CSRC, f) for f in ("bam_ingest.cpp", "vcf_audit.cpp")]
     hdrs = [os.path.join(CSRC, "svtrek_host.h"), os.path.join(INC, "svtrek_gpu.h"), os.path.join(INC, "svtrek_evidence.h"),
             os.path.join(INC, "svtrek_call.h"), os.path.join(INC, "svtrek_genotype.h"), os.path.join(INC, "svtrek_callseq.h"),
-            os.path.join(INC, "svtrek_junction.h"), os.path.join(CSRC, "svt_bamrec.h")]
+            os.path.join(INC, "svtrek_junction.h"), os.path.join(INC, "svtrek_rearr.h"), os.path.join(CSRC, "svt_bamrec.h")]
     eng = os.path.join(PKG, "libsvtrek_hip.so")
     if all(os.path.exists(s) for s in srcs) and (force or _stale(out, srcs + hdrs + [eng])):
         _run(["g++", "-O3", "-std=c++17", "-Wall", "-Wextra", "-pthread", "-I", INC, "-o", out] + srcs +

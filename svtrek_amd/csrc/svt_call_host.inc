@@ -43,6 +43,22 @@ CallView call_view(svt_ctx *c, bool merged, bool junction = false) {
 }
 
 svt_status junction_build(svt_ctx *c, uint32_t gap, uint32_t min_len);   // svt_junction_host.inc
+svt_status rearr_build(svt_ctx *c);                                      // svt_rearr_host.inc
+
+// The rearrangement index (rearr != 0; svt_rearr_host.inc builds it): rows S and I hold the DUP and the INV events.
+CallView rearr_view(svt_ctx *c) {
+    CallScratch &k = c->call;
+    CallView v = call_view(c, false);
+    v.bk.ev = k.rr.d_ev;
+    v.bk.off = k.rr.d_off;
+    v.bk.pm = nullptr;
+    v.n_s = k.rr.events[0];
+    v.n_i = k.rr.events[1];
+    v.ready = &k.rr.ready;
+    v.n_seg = &k.rr.n_seg;
+    v.d_seg = &k.rr.d_seg;
+    return v;
+}
 
 // The first scan of a loaded pileup (of a merged index): the segments (the buckets' extents are those
 // of the load for every rebuild) and the scratch that depends on the event counts alone.
@@ -139,45 +155,23 @@ svt_status call_split_1(svt_ctx *c, const CallArgs &a, uint32_t n_keys, uint32_t
     hipLaunchKernelGGL(call_unit_kernel, cg, cb, 0, nullptr, a, sp, ncl);
     if (ncand) hipLaunchKernelGGL(call_order_kernel, sg, sb, 0, nullptr, a, sp);
     HIP_TRY(c, hipGetLastError());
-    k.split.candidates = ncand;
+    k.split.candidates += ncand;   // (zeroed when the scan began; a scan with rearr != 0 has two passes)
     return SVT_OK;
 }
 
-svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) {
+// One pass of the scan over view v: the sort, the link, the accumulation, the split by length and the pick,
+// then the records -- call_emit_kernel's, or rearr_emit_kernel's for the rearrangement index (svt_rearr.inc) --
+// and the merge of the pass's two lists into dst.  The pass's counters stay in k.d_ctr / k.d_sctr for
+// call_pass_stats.
+struct CallPass {
+    uint32_t ncl = 0, npick = 0;
+    bool split = false;           // the split ran: its counters are in k.d_sctr
+};
+svt_status call_pass(svt_ctx *c, const svt_call_params *p, const CallView &v, uint32_t types, bool rearr, DevBuf<svt_call> &dst,
+                     CallPass *out) {
     CallScratch &k = c->call;
-    k.n_calls = 0;
-    k.scanned = true;
-    k.stats = svt_call_stats{};
-    k.split = svt_call_split_stats{};
-    k.merge = svt_call_merge_stats{};
-    k.junction = svt_call_junction_stats{};
-    const bool merged = p->merge_gap != 0u, junction = p->junctions != 0u;
-    k.last_merged = k.last_junction = false;   // (set once the index the scan runs on is built)
-    *n_calls = 0;
-    if (c->n_reads == 0) {   // (no index to build: every site of such a pileup is invalid)
-        k.last_merged = merged;
-        k.last_junction = junction;
-        return SVT_OK;
-    }
-    svt_status s = order_on(c, nullptr);   // after every launch already issued (svt_reindex rebuilds the buckets)
-    if (s) return s;
-    if (merged) {   // (before the scan's clock: the build runs once per pileup and (gap, min))
-        if ((s = callmerge_build(c, p->merge_gap, p->merge_min))) return s;
-        k.merge = k.mg.stats;
-    }
-    if (junction) {   // (likewise: once per pileup, table and base view)
-        if ((s = junction_build(c, p->merge_gap, p->merge_min))) return s;
-        k.junction = k.jn.stats;
-    }
-    k.last_merged = merged;
-    k.last_junction = junction;
-    const CallView v = call_view(c, merged, junction);
     const uint64_t N = v.n_s + v.n_i;
-    if (N == 0) return SVT_OK;
-    DevEvent e0, e1;
-    HIP_TRY(c, e0.create());
-    HIP_TRY(c, e1.create());
-    HIP_TRY(c, hipEventRecord(e0, nullptr));
+    svt_status s;
     if ((s = call_prepare(c, v))) return s;
     const uint64_t n_seg = *v.n_seg;
     const KArgs ka = make_args(c, nullptr, nullptr, 0, false);
@@ -196,7 +190,7 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
     a.stats = reinterpret_cast<unsigned long long *>(k.d_ctr + 2);
     a.link = (uint32_t)p->link;
     a.min_support = (uint32_t)p->min_support;
-    a.types = p->types;
+    a.types = types;
     a.permille = p->len_permille;
     const dim3 sg((unsigned)n_seg), sb(CALL_T);
     HIP_TRY(c, hipMemsetAsync(k.d_ctr, 0, 8 * sizeof(uint32_t), nullptr));
@@ -245,33 +239,122 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
     }
     const uint32_t npick = picked[0], ndel = std::min(picked[1], picked[0]);
     if (npick) {
-        if ((s = nomem(c, k.d_calls.reserve(npick), CALL_MEM)) || (s = nomem(c, k.d_raw.reserve(npick), CALL_MEM))) return s;
-        hipLaunchKernelGGL(call_emit_kernel, dim3((npick + WPB - 1) / WPB), dim3(64 * WPB), 0, nullptr, a, npick, k.d_raw);
+        if ((s = nomem(c, dst.reserve(npick), CALL_MEM)) || (s = nomem(c, k.d_raw.reserve(npick), CALL_MEM))) return s;
+        const dim3 eg((npick + WPB - 1) / WPB), eb(64 * WPB);
+        if (rearr) hipLaunchKernelGGL(rearr_emit_kernel, eg, eb, 0, nullptr, a, npick, k.d_raw);
+        else hipLaunchKernelGGL(call_emit_kernel, eg, eb, 0, nullptr, a, npick, k.d_raw);
         hipLaunchKernelGGL(call_merge_kernel, dim3((npick + 255u) / 256u), dim3(256), 0, nullptr, k.d_raw, npick, ndel,
-                           k.d_calls);
+                           dst.get());
         HIP_TRY(c, hipGetLastError());
     }
-    HIP_TRY(c, hipEventRecord(e1, nullptr));
-    HIP_TRY(c, hipEventSynchronize(e1));
+    out->ncl = ncl;
+    out->npick = npick;
+    out->split = a.permille && ncl;
+    return SVT_OK;
+}
+
+// The counters of the pass that ran last, added to the scan's stats (zeroed when the scan began).
+svt_status call_pass_stats(svt_ctx *c, const CallPass &ps, unsigned long long *skipped = nullptr) {
+    CallScratch &k = c->call;
     unsigned long long st[3] = {};
     HIP_TRY(c, hipMemcpy(st, k.d_ctr + 2, sizeof st, hipMemcpyDeviceToHost));
-    if (a.permille && ncl) {
+    if (ps.split) {
         unsigned long long ss[3] = {};
         HIP_TRY(c, hipMemcpy(ss, k.d_sctr, sizeof ss, hipMemcpyDeviceToHost));
-        k.split.split = ss[0];
-        k.split.groups = ss[1];
-        k.split.big = ss[2];
+        k.split.split += ss[0];
+        k.split.groups += ss[1];
+        k.split.big += ss[2];
+    }
+    k.stats.events += st[0];
+    k.stats.skipped += st[1];
+    k.stats.big_buckets += st[2];
+    k.stats.clusters += ps.ncl;
+    k.stats.calls += ps.npick;
+    if (skipped) *skipped = st[1];
+    return SVT_OK;
+}
+
+svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) {
+    CallScratch &k = c->call;
+    k.n_calls = 0;
+    k.scanned = true;
+    k.stats = svt_call_stats{};
+    k.split = svt_call_split_stats{};
+    k.merge = svt_call_merge_stats{};
+    k.junction = svt_call_junction_stats{};
+    k.rearr = svt_call_rearr_stats{};
+    const bool merged = p->merge_gap != 0u, junction = p->junctions != 0u;
+    const uint32_t rearr = p->rearr, base_types = p->types & ((1u << SVT_INS) | (1u << SVT_DEL));
+    k.last_merged = k.last_junction = false;   // (set once the index the scan runs on is built)
+    k.last_rearr = 0;
+    *n_calls = 0;
+    if (c->n_reads == 0) {   // (no index to build: every site of such a pileup is invalid)
+        k.last_merged = merged;
+        k.last_junction = junction;
+        k.last_rearr = rearr;
+        return SVT_OK;
+    }
+    svt_status s = order_on(c, nullptr);   // after every launch already issued (svt_reindex rebuilds the buckets)
+    if (s) return s;
+    if (merged) {   // (before the scan's clock: the build runs once per pileup and (gap, min))
+        if ((s = callmerge_build(c, p->merge_gap, p->merge_min))) return s;
+        k.merge = k.mg.stats;
+    }
+    if (junction) {   // (likewise: once per pileup, table and base view)
+        if ((s = junction_build(c, p->merge_gap, p->merge_min))) return s;
+        k.junction = k.jn.stats;
+    }
+    if (rearr) {   // (likewise: once per pileup and table)
+        if ((s = rearr_build(c))) return s;
+        k.rearr = k.rr.stats;
+    }
+    k.last_merged = merged;
+    k.last_junction = junction;
+    k.last_rearr = rearr;
+    const CallView v = call_view(c, merged, junction);
+    const uint64_t N = base_types ? v.n_s + v.n_i : 0;   // (no DEL / INS bit: a rearrangement-only scan)
+    if (N == 0 && !rearr) return SVT_OK;
+    DevEvent e0, e1;
+    HIP_TRY(c, e0.create());
+    HIP_TRY(c, e1.create());
+    HIP_TRY(c, hipEventRecord(e0, nullptr));
+    CallPass ps{};
+    if (N && (s = call_pass(c, p, v, p->types, false, rearr ? k.rr.d_a : k.d_calls, &ps))) return s;
+    uint64_t total = ps.npick;
+    if (rearr) {   // the second pass, over the rearrangement index, and the merge of the two lists (svt_rearr.inc)
+        if (N && (s = call_pass_stats(c, ps))) return s;
+        const CallView rv = rearr_view(c);
+        CallPass pr{};
+        const uint32_t rtypes = ((rearr >> SVT_DUP) & 1u) << SVT_DEL | ((rearr >> SVT_INV) & 1u) << SVT_INS;
+        const bool second = rv.n_s + rv.n_i != 0;
+        if (second && (s = call_pass(c, p, rv, rtypes, true, k.rr.d_b, &pr))) return s;
+        total += pr.npick;
+        if (total > 0x7fffffffull) return fail(c, SVT_ESTATE, "%s", "svt_call_scan: more than 2^31 - 1 calls are not supported");
+        if (total) {
+            if ((s = nomem(c, k.d_calls.reserve(total), CALL_MEM))) return s;
+            hipLaunchKernelGGL(rearr_merge_kernel, dim3((unsigned)((total + 255u) / 256u)), dim3(256), 0, nullptr, k.rr.d_a.get(),
+                               ps.npick, k.rr.d_b.get(), pr.npick, k.d_calls.get());
+            HIP_TRY(c, hipGetLastError());
+        }
+        HIP_TRY(c, hipEventRecord(e1, nullptr));
+        HIP_TRY(c, hipEventSynchronize(e1));
+        if (second) {   // (no counters of a pass that did not run)
+            unsigned long long skipped = 0;
+            if ((s = call_pass_stats(c, pr, &skipped))) return s;
+            k.rearr.skipped = skipped;
+            k.rearr.clusters = pr.ncl;
+            k.rearr.calls = pr.npick;
+        }
+    } else {
+        HIP_TRY(c, hipEventRecord(e1, nullptr));
+        HIP_TRY(c, hipEventSynchronize(e1));
+        if ((s = call_pass_stats(c, ps))) return s;
     }
     float ms = 0.f;
     HIP_TRY(c, hipEventElapsedTime(&ms, e0, e1));
-    k.stats.events = st[0];
-    k.stats.skipped = st[1];
-    k.stats.big_buckets = st[2];
-    k.stats.clusters = ncl;
-    k.stats.calls = npick;
     k.stats.scan_ms = ms;
-    k.n_calls = npick;
-    *n_calls = npick;
+    k.n_calls = total;
+    *n_calls = total;
     return SVT_OK;
 }
 
@@ -287,12 +370,14 @@ void svt_call_default_params(const svt_ctx *c, svt_call_params *out) {
     out->merge_gap = 0;
     out->merge_min = 20;
     out->junctions = 0;
+    out->rearr = 0;
 }
 
 svt_status svt_call_scan(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) {
     if (!c) return SVT_EINVAL;
     if (!p || !n_calls) return fail(c, SVT_EINVAL, "%s", "null params/n_calls");
-    if (p->link < 0 || p->link > (1 << 20) || p->min_support < 1 || !(p->types & ((1u << SVT_INS) | (1u << SVT_DEL))))
+    if (p->rearr & ~((1u << SVT_DUP) | (1u << SVT_INV))) return fail(c, SVT_EINVAL, "%s", "svt_call_scan: rearr is a mask of the DUP and INV bits");
+    if (p->link < 0 || p->link > (1 << 20) || p->min_support < 1 || (!(p->types & ((1u << SVT_INS) | (1u << SVT_DEL))) && !p->rearr))
         return fail(c, SVT_EINVAL, "%s", "svt_call_scan: link in [0, 2^20], min_support >= 1 and a type bit of DEL / INS");
     if (p->len_permille > 1000u) return fail(c, SVT_EINVAL, "%s", "svt_call_scan: len_permille in [0, 1000]");
     if (p->merge_gap > (1u << 20) || (p->merge_gap != 0u && (p->merge_min < 1u || p->merge_min > (uint32_t)SV_MIN_LENGTH)))
@@ -301,6 +386,8 @@ svt_status svt_call_scan(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls
     if (!c->loaded) return fail(c, SVT_ESTATE, "%s", "svt_load_pileup not called");
     if (p->junctions && !c->call.jn.loaded)
         return fail(c, SVT_ESTATE, "%s", "svt_call_scan: junctions = 1 without svt_load_junctions for the loaded pileup");
+    if (p->rearr && !c->call.jn.loaded)
+        return fail(c, SVT_ESTATE, "%s", "svt_call_scan: rearr != 0 without svt_load_junctions for the loaded pileup");
     if (c->n_reads != 0 && !c->bk_ready)
         return fail(c, SVT_ESTATE, "%s",
                     "svt_call_scan needs the value buckets (not built: SVTREK_INDEX=lists, or a pileup past 2^32 events)");

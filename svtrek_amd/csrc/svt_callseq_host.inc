@@ -127,6 +127,8 @@ svt_status svt_call_consensus(svt_ctx *c, const svt_poa_params *p, uint64_t firs
     if (c->call.last_junction)
         return fail(c, SVT_ESTATE, "%s", "svt_call_consensus: the last scan read split alignments (junctions = 1): no inserted bases for junction calls");
     if (!c->insseq_loaded) return fail(c, SVT_ESTATE, "%s", "svt_load_insseq not called");
+    if (c->call.last_rearr)
+        return fail(c, SVT_ESTATE, "%s", "svt_call_consensus: the last scan called rearrangements (rearr != 0): scan without them for inserted bases");
     if (first > c->call.n_calls || n > c->call.n_calls - first)
         return fail(c, SVT_EINVAL, "%s", "svt_call_consensus: range past the scanned calls");
     if (n == 0) return SVT_OK;

@@ -125,6 +125,21 @@ struct CallScratch {
     } jn;
     bool last_junction = false;           // the last scan ran on the union index (svt_genotype_calls, svt_call_consensus)
     svt_call_junction_stats junction{};   // the last scan's (all zero after junctions = 0)
+    // the rearrangement index (rearr != 0; svt_rearr.inc, svt_rearr_host.inc): nothing allocated before the
+    // first such scan; rebuilt when the table changes, untouched by svt_reindex
+    struct Rearr {
+        bool built = false;
+        DevBuf<uint4> d_ev;               // the DUP events (row S), then the INV events (row I)
+        DevBuf<uint32_t> d_off;           // [BA_N][bk_n + 1], rows S and I filled
+        uint64_t events[2] = {};          // DUP / INV items
+        bool ready = false;               // its own segments (they depend on the extents)
+        uint64_t n_seg = 0;
+        DevBuf<uint64_t> d_seg;
+        DevBuf<svt_call> d_a, d_b;        // the scan's two sorted lists before their merge: DEL / INS, INV / DUP
+        svt_call_rearr_stats stats{};     // of the build
+    } rr;
+    uint32_t last_rearr = 0;              // the last scan's rearr mask (svt_call_consensus)
+    svt_call_rearr_stats rearr{};         // the last scan's (all zero after rearr = 0)
 };
 
 // svt_call_consensus's scratch (svt_callseq.inc, svt_callseq_host.inc): nothing allocated before the

@@ -33,6 +33,8 @@
 //                         merge_gap (host side: svt_callmerge_host.inc)
 //   svt_junction.inc      DEL / INS items from split alignments filed beside the base view's events into the
 //                         union index of svt_call_scan's junctions (host side: svt_junction_host.inc)
+//   svt_rearr.inc         DUP / INV items from the same table in an index of their own, the scan's second
+//                         pass over it and the merge of the two call lists (host side: svt_rearr_host.inc)
 //   svt_index.inc, svt_index2.inc, svt_bucket_build.inc   the index builds (span lists, value buckets)
 //   svt_poa.inc, svt_poa_host.inc      allele consensus (POA): kernels, slot pools and poa_run
 //   svt_callseq.inc       consensus sequence of discovered INS calls: item table and support gather
@@ -63,9 +65,10 @@
 #include "../../include/svtrek_genotype.h"
 #include "../../include/svtrek_callseq.h"
 #include "../../include/svtrek_junction.h"
+#include "../../include/svtrek_rearr.h"
 #include "svt_bamrec.h"
 
-#define SVT_VERSION "svtrek_amd 0.32.0 (gfx950, value-bucketed event index filed by a lane-per-read walk with a 9-B LDS stage, band + prefix-max facts, packed span walk fed by readlane, lane vote on 64 windows a wave, BGZF inflate + BAM decode, DEL/INS discovery from the value buckets, genotypes from the events' own read extents, consensus sequence of INS calls, a read's fragmented D / I ops joined before calling, DEL/INS items from split alignments)"
+#define SVT_VERSION "svtrek_amd 0.33.0 (gfx950, value-bucketed event index filed by a lane-per-read walk with a 9-B LDS stage, band + prefix-max facts, packed span walk fed by readlane, lane vote on 64 windows a wave, BGZF inflate + BAM decode, DEL/INS discovery from the value buckets, genotypes from the events' own read extents, consensus sequence of INS calls, a read's fragmented D / I ops joined before calling, DEL/INS items and DUP/INV calls from split alignments)"
 
 namespace {
 
@@ -185,6 +188,7 @@ constexpr int LV_WMAX = 1023;   // band half-width for 16-bit offsets and prefix
 #include "svt_bucket_build.inc"
 #include "svt_callmerge.inc"
 #include "svt_junction.inc"
+#include "svt_rearr.inc"
 #include "svt_poa.inc"
 #include "svt_callseq.inc"
 #include "svt_bam.inc"
@@ -1391,6 +1395,7 @@ svt_status svt_evidence_batch(svt_ctx *c, const svt_locus *loci, const svt_resul
 #include "svt_callmerge_host.inc"
 #include "svt_call_host.inc"
 #include "svt_junction_host.inc"
+#include "svt_rearr_host.inc"
 
 // ---- include/svtrek_genotype.h
 #include "svt_genotype_host.inc"

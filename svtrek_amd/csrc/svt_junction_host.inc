@@ -151,6 +151,14 @@ svt_status junction_load_1(svt_ctx *c, const svt_junction_view *v) {
         j.d_seg.reset();
     }
     j.built = j.ready = false;
+    CallScratch::Rearr &rr = c->call.rr;   // the rearrangement index of the table before (svt_rearr_host.inc): likewise
+    if (rr.built || rr.ready) {
+        HIP_TRY(c, hipDeviceSynchronize());
+        rr.d_ev.reset();
+        rr.d_off.reset();
+        rr.d_seg.reset();
+    }
+    rr.built = rr.ready = false;
     j.d_toff = std::move(d_toff);
     j.d_tseg = std::move(d_tseg);
     j.n = n;

@@ -20,6 +20,7 @@
 #include "svtrek_genotype.h"
 #include "svtrek_callseq.h"
 #include "svtrek_junction.h"
+#include "svtrek_rearr.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -162,6 +163,16 @@ char *svth_format_calls_gt(const svt_call *calls, const svt_gt *gts, size_t n, c
 char *svth_format_calls_seq(const svt_call *calls, const svt_gt *gts, const svt_poa_result *cons, const uint8_t *bases,
                             int32_t cap, size_t n, const char *const *names, size_t n_names, const char *sample, int header,
                             int threads, size_t *len);
+/* The same for a scan that asked for rearrangements (include/svtrek_rearr.h), rearr = the scan's svt_call_params.rearr:
+ * a call of type SVT_DUP / SVT_INV is written as
+ *   name  pos  svtrek.DUP.<k>|svtrek.INV.<k>  N  <DUP>|<INV>  .  PASS  SVTYPE=DUP|INV;END=e;SVLEN=len;...
+ * with k its rank among the calls of its own type, SVLEN positive, the INFO keys those of a DEL record and the
+ * genotype column, if any, its svt_gt record (the invalid one prints ./.); the header gains
+ * ##ALT=<ID=DUP,...> / ##ALT=<ID=INV,...> behind the INS line for the bits set in rearr.  rearr == 0:
+ * svth_format_calls_seq, byte for byte (every type but DEL is written as INS there, as before). */
+char *svth_format_calls_rearr(const svt_call *calls, const svt_gt *gts, const svt_poa_result *cons, const uint8_t *bases,
+                              int32_t cap, size_t n, const char *const *names, size_t n_names, const char *sample, int header,
+                              int threads, uint32_t rearr, size_t *len);
 void  svth_free(void *p);
 
 /* A11: stdout text for one refined record; returns bytes written (0 = prints nothing:

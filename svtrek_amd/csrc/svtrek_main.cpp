@@ -42,6 +42,8 @@ extern "C" __typeof__(svt_call_merge_stats_get) svt_call_merge_stats_get __attri
 // include/svtrek_junction.h likewise (`svtrek call --split-reads`)
 extern "C" __typeof__(svt_load_junctions) svt_load_junctions __attribute__((weak));
 extern "C" __typeof__(svt_call_junction_stats_get) svt_call_junction_stats_get __attribute__((weak));
+// include/svtrek_rearr.h likewise (`svtrek call --rearrangements`)
+extern "C" __typeof__(svt_call_rearr_stats_get) svt_call_rearr_stats_get __attribute__((weak));
 // include/svtrek_genotype.h likewise (`svtrek call --genotype`)
 extern "C" __typeof__(svt_genotype_default_params) svt_genotype_default_params __attribute__((weak));
 extern "C" __typeof__(svt_genotype_calls) svt_genotype_calls __attribute__((weak));
@@ -81,6 +83,10 @@ void call_usage() {
     printf("    --split-reads                     Also call from split alignments: a read written as two alignments linked\n");
     printf("                                      by SA tags gives the deletion / insertion between them as one more item;\n");
     printf("                                      not with --ins-seq [Default: CIGAR ops alone]\n");
+    printf("    --rearrangements <DUP,INV>        Also call tandem duplications and / or inversions from split alignments:\n");
+    printf("                                      a second alignment upstream of the first (DUP) or on the other strand (INV);\n");
+    printf("                                      <DUP> / <INV> records in the same VCF, never genotyped (./.); with or without\n");
+    printf("                                      --split-reads; not with --ins-seq [Default: none]\n");
     printf("    --genotype                        Genotype every call: a FORMAT and a sample column with GT:GQ:DR:DV:PL\n");
     printf("                                      [Default: a sites-only VCF]\n");
     printf("    --flank <num>                     Bases a read must cover on both sides of a call to count [Default: 50]\n");
@@ -588,7 +594,7 @@ int call_mode(int argc, char **argv) {
     const char *bam_path = nullptr, *out_path = nullptr, *sample = "SAMPLE";
     int threads = THREADS, verbose = 0, device = 0, gpu_inflate = -1, link = -1, min_support = -1, genotype = 0, flank = -1, len_permille = 0;
     int ins_seq = 0, ins_cap = 4096, merge_gap = 0, merge_min = -1, split_reads = 0;
-    uint32_t types = (1u << SVT_INS) | (1u << SVT_DEL);
+    uint32_t types = (1u << SVT_INS) | (1u << SVT_DEL), rearr = 0;
     static const option opts[] = {
         {"bam", required_argument, nullptr, 1}, {"output", required_argument, nullptr, 3},
         {"verbose", no_argument, nullptr, 4}, {"help", no_argument, nullptr, 11},
@@ -598,7 +604,8 @@ int call_mode(int argc, char **argv) {
         {"flank", required_argument, nullptr, 34}, {"sample", required_argument, nullptr, 35},
         {"len-permille", required_argument, nullptr, 36}, {"ins-seq", no_argument, nullptr, 37},
         {"ins-seq-cap", required_argument, nullptr, 38}, {"merge-gap", required_argument, nullptr, 39},
-        {"merge-min", required_argument, nullptr, 40}, {"split-reads", no_argument, nullptr, 41}, {nullptr, 0, nullptr, 0}};
+        {"merge-min", required_argument, nullptr, 40}, {"split-reads", no_argument, nullptr, 41},
+        {"rearrangements", required_argument, nullptr, 42}, {nullptr, 0, nullptr, 0}};
     int opt, li;
     while ((opt = getopt_long(argc, argv, "b:o:t:h", opts, &li)) != -1) {
         switch (opt) {
@@ -639,6 +646,19 @@ int call_mode(int argc, char **argv) {
         case 39: merge_gap = atoi(optarg); if (merge_gap < 0 || merge_gap > (1 << 20)) { fprintf(stderr, "[ERROR] --merge-gap must be in [0, 1048576]\n"); exit(EXIT_FAILURE); } break;
         case 40: merge_min = atoi(optarg); if (merge_min < 1 || merge_min > 50) { fprintf(stderr, "[ERROR] --merge-min must be in [1, 50]\n"); exit(EXIT_FAILURE); } break;
         case 41: split_reads = 1; break;
+        case 42: {
+            rearr = 0;
+            std::string t(optarg);
+            for (size_t i = 0; i <= t.size();) {
+                const size_t e = std::min(t.find(',', i), t.size());
+                const std::string w = t.substr(i, e - i);
+                if (w == "DUP") rearr |= 1u << SVT_DUP;
+                else if (w == "INV") rearr |= 1u << SVT_INV;
+                else { fprintf(stderr, "[ERROR] --rearrangements expects DUP, INV or DUP,INV\n"); exit(EXIT_FAILURE); }
+                i = e + 1;
+            }
+            break;
+        }
         default:
             printf("[ERROR] Option %d is invalid.\n", opt);
             call_usage();
@@ -653,6 +673,14 @@ int call_mode(int argc, char **argv) {
     }
     if (split_reads && ins_seq) {   // (before any ingest: no inserted bases for junction calls)
         fprintf(stderr, "[ERROR] --split-reads cannot be combined with --ins-seq: calls from split alignments have no consensus sequence\n");
+        return 1;
+    }
+    if (rearr && ins_seq) {   // (before any ingest: svt_call_consensus refuses the calls of such a scan)
+        fprintf(stderr, "[ERROR] --rearrangements cannot be combined with --ins-seq: scan without them for the consensus sequences\n");
+        return 1;
+    }
+    if (rearr && (!svt_load_junctions || !svt_call_rearr_stats_get)) {
+        fprintf(stderr, "[ERROR] rearrangements: not supported by this backend\n");
         return 1;
     }
     if (split_reads && (!svt_load_junctions || !svt_call_junction_stats_get)) {
@@ -691,7 +719,7 @@ int call_mode(int argc, char **argv) {
     });
     char err[512];
     const svth_inflater dev_inf{device_inflate, device_host_alloc, device_host_free, &dinf, (size_t)1024 << 20};
-    svth_bam *bam = (ins_seq ? svth_bam_read_seq : split_reads ? svth_bam_read_sa : svth_bam_read_ex)(bam_path, threads, -1, 0, -1, 0,
+    svth_bam *bam = (ins_seq ? svth_bam_read_seq : split_reads || rearr ? svth_bam_read_sa : svth_bam_read_ex)(bam_path, threads, -1, 0, -1, 0,
                                                                     gpu_inflate ? &dev_inf : nullptr, err, sizeof err);
     ot.join();
     auto done = [&](int rc) {
@@ -721,11 +749,15 @@ int call_mode(int argc, char **argv) {
         if (!svth_bam_insseq(bam, &sv)) { fprintf(stderr, "[ERROR] --ins-seq: the ingest kept no sequences\n"); return done(1); }
         s = svt_load_insseq(ctx, &sv);
     }
-    if (!s && split_reads) {   // the segment table the ingest kept (a backend without it is refused above)
+    if (!s && (split_reads || rearr)) {   // the segment table the ingest kept (a backend without it is refused above)
         svt_junction_view jv{};
-        if (!svth_bam_junctions(bam, &jv)) { fprintf(stderr, "[ERROR] --split-reads: the ingest kept no segment table\n"); return done(1); }
+        if (!svth_bam_junctions(bam, &jv)) {
+            fprintf(stderr, "[ERROR] %s: the ingest kept no segment table\n", split_reads ? "--split-reads" : "--rearrangements");
+            return done(1);
+        }
         s = svt_load_junctions(ctx, &jv);
-        cp.junctions = 1;
+        if (split_reads) cp.junctions = 1;
+        if (rearr) cp.rearr = rearr;   // (a backend without them is refused above and never sees the field)
     }
     const double t_load = now_s();
     if (!s) s = svt_call_scan(ctx, &cp, &n);
@@ -760,9 +792,9 @@ int call_mode(int argc, char **argv) {
     for (size_t t = 0; t < names.size(); t++) names[t] = svth_bam_target_name(bam, (int32_t)t);
     size_t olen = 0;
     static const svt_gt no_gt{};   // (no calls: the header still has to say FORMAT)
-    char *text = svth_format_calls_seq(calls.data(), genotype ? (gts.empty() ? &no_gt : gts.data()) : nullptr,
-                                       ins_seq ? cons.data() : nullptr, ins_seq ? cons_bases.data() : nullptr, ins_cap, calls.size(),
-                                       names.data(), names.size(), sample, 1, threads, &olen);
+    char *text = svth_format_calls_rearr(calls.data(), genotype ? (gts.empty() ? &no_gt : gts.data()) : nullptr,
+                                         ins_seq ? cons.data() : nullptr, ins_seq ? cons_bases.data() : nullptr, ins_cap, calls.size(),
+                                         names.data(), names.size(), sample, 1, threads, rearr, &olen);
     if (!text) { fprintf(stderr, "[ERROR] out of host memory\n"); return done(1); }
     FILE *of = out_path ? fopen(out_path, "wb") : stdout;
     bool ok = of && fwrite(text, 1, olen, of) == olen;
@@ -800,6 +832,12 @@ int call_mode(int argc, char **argv) {
                 (unsigned long long)js.segments, (unsigned long long)js.junctions, (unsigned long long)js.del_items,
                 (unsigned long long)js.ins_items, (unsigned long long)js.other, (unsigned long long)js.skipped,
                 (long long)svth_bam_n_sa_malformed(bam), js.build_ms);
+    svt_call_rearr_stats rs{};
+    if (verbose && rearr && !svt_call_rearr_stats_get(ctx, &rs))
+        fprintf(stderr, "[svtrek_amd] call: rearrangements %s%s%s  DUP items %llu  INV items %llu  skipped %llu  clusters %llu  calls %llu  "
+                        "build %.3f ms\n", rearr & (1u << SVT_DUP) ? "DUP" : "", rearr == ((1u << SVT_DUP) | (1u << SVT_INV)) ? "," : "",
+                rearr & (1u << SVT_INV) ? "INV" : "", (unsigned long long)rs.dup_items, (unsigned long long)rs.inv_items,
+                (unsigned long long)rs.skipped, (unsigned long long)rs.clusters, (unsigned long long)rs.calls, rs.build_ms);
     return done(0);
 }
 

@@ -241,33 +241,48 @@ char *svth_format_calls_gt(const svt_call *c, const svt_gt *gts, size_t n, const
 char *svth_format_calls_seq(const svt_call *c, const svt_gt *gts, const svt_poa_result *cons, const uint8_t *bases, int32_t cap,
                             size_t n, const char *const *names, size_t n_names, const char *sample, int header, int threads,
                             size_t *len) {
+    return svth_format_calls_rearr(c, gts, cons, bases, cap, n, names, n_names, sample, header, threads, 0u, len);
+}
+
+char *svth_format_calls_rearr(const svt_call *c, const svt_gt *gts, const svt_poa_result *cons, const uint8_t *bases, int32_t cap,
+                              size_t n, const char *const *names, size_t n_names, const char *sample, int header, int threads,
+                              uint32_t rearr, size_t *len) {
     const int T = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(threads, 1), n / 16384 + 1));
+    // a call's class: 0 DEL, 1 INS (and, with rearr == 0, every other type, as ever), 2 DUP, 3 INV
+    auto cls = [rearr](const svt_call &x) {
+        if (x.type == SVT_DEL) return 0;
+        if (rearr && x.type == SVT_DUP) return 2;
+        if (rearr && x.type == SVT_INV) return 3;
+        return 1;
+    };
+    static const char *const TY[4] = {"DEL", "INS", "DUP", "INV"};
     // the ID's k: the call's rank among the calls of its type (1-based)
-    std::vector<size_t> first_k((size_t)T * 2 + 2, 0);
+    std::vector<size_t> first_k((size_t)T * 4 + 4, 0);
     for (int t = 0; t < T; t++) {
-        size_t d = 0, i = 0;
-        for (size_t k = n * (size_t)t / (size_t)T, e = n * (size_t)(t + 1) / (size_t)T; k < e; k++) (c[k].type == SVT_DEL ? d : i)++;
-        first_k[2 * (size_t)t + 2] = first_k[2 * (size_t)t] + d;
-        first_k[2 * (size_t)t + 3] = first_k[2 * (size_t)t + 1] + i;
+        size_t cnt[4] = {0, 0, 0, 0};
+        for (size_t k = n * (size_t)t / (size_t)T, e = n * (size_t)(t + 1) / (size_t)T; k < e; k++) cnt[cls(c[k])]++;
+        for (int q = 0; q < 4; q++) first_k[4 * (size_t)t + 4 + (size_t)q] = first_k[4 * (size_t)t + (size_t)q] + cnt[q];
     }
     std::vector<std::string> part((size_t)T);
     run_parts(T, [&](int t) {
         std::string &o = part[(size_t)t];
         const size_t b = n * (size_t)t / (size_t)T, e = n * (size_t)(t + 1) / (size_t)T;
         o.reserve((e - b) * 160);
-        size_t rank[2] = {first_k[2 * (size_t)t], first_k[2 * (size_t)t + 1]};
+        size_t rank[4];
+        for (int q = 0; q < 4; q++) rank[q] = first_k[4 * (size_t)t + (size_t)q];
         char buf[320], num[16];
         for (size_t k = b; k < e; k++) {
             const svt_call &x = c[k];
-            const bool del = x.type == SVT_DEL;
-            const char *ty = del ? "DEL" : "INS";
+            const int cl = cls(x);
+            const bool del = cl == 0;
+            const char *ty = TY[cl];
             const char *name = num;
             if (x.chrom >= 1 && (size_t)x.chrom <= n_names && names && names[x.chrom - 1]) name = names[x.chrom - 1];
             else snprintf(num, sizeof num, "%d", x.chrom);
             o += name;
-            int m = snprintf(buf, sizeof buf, "\t%u\tsvtrek.%s.%zu\tN\t", x.pos, ty, ++rank[del ? 0 : 1]);
+            int m = snprintf(buf, sizeof buf, "\t%u\tsvtrek.%s.%zu\tN\t", x.pos, ty, ++rank[cl]);
             o.append(buf, (size_t)m);
-            const bool ins_cons = cons && !del;
+            const bool ins_cons = cons && cl == 1;
             if (ins_cons && cons[k].len >= 1 && cons[k].len <= cap && bases) {   // ALT: the base before + the consensus
                 const uint8_t *q = bases + k * (size_t)cap;
                 o += 'N';
@@ -300,8 +315,10 @@ char *svth_format_calls_seq(const svt_call *c, const svt_gt *gts, const svt_poa_
     if (header) {
         head = "##fileformat=VCFv4.2\n##source=svtrek_amd call\n";
         for (size_t t = 0; t < n_names; t++) head += std::string("##contig=<ID=") + (names && names[t] ? names[t] : "") + ">\n";
-        head += "##ALT=<ID=DEL,Description=\"Deletion\">\n##ALT=<ID=INS,Description=\"Insertion\">\n"
-                "##INFO=<ID=SVTYPE,Number=1,Type=String,Description=\"Type of structural variant\">\n"
+        head += "##ALT=<ID=DEL,Description=\"Deletion\">\n##ALT=<ID=INS,Description=\"Insertion\">\n";
+        if (rearr & (1u << SVT_DUP)) head += "##ALT=<ID=DUP,Description=\"Tandem duplication\">\n";
+        if (rearr & (1u << SVT_INV)) head += "##ALT=<ID=INV,Description=\"Inversion\">\n";
+        head += "##INFO=<ID=SVTYPE,Number=1,Type=String,Description=\"Type of structural variant\">\n"
                 "##INFO=<ID=END,Number=1,Type=Integer,Description=\"DEL: rounded mean of the ops' walk end + 1; INS: POS + 1\">\n"
                 "##INFO=<ID=SVLEN,Number=1,Type=Integer,Description=\"Rounded mean length of the supporting ops (negative: DEL)\">\n"
                 "##INFO=<ID=SUPPORT,Number=1,Type=Integer,Description=\"CIGAR ops in the cluster\">\n"

@@ -14,9 +14,9 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._lib import (CALL_DTYPE, EVIDENCE_DTYPE, GT_DTYPE, GT_SITE_DTYPE, JUNCTION_SEG_DTYPE, LOCUS_DTYPE, POA_RESULT_DTYPE, RESULT_DTYPE,
-                   STATUS_NAMES, SVT_DEL, SVT_EINVAL, SVT_INS, SVT_NA, SW_QUERY_DTYPE, SW_WINDOW_DTYPE, SvtCallConsensusStats,
+                   STATUS_NAMES, SVT_DEL, SVT_DUP, SVT_EINVAL, SVT_INS, SVT_INV, SVT_NA, SW_QUERY_DTYPE, SW_WINDOW_DTYPE, SvtCallConsensusStats, SvtCallRearrStats,
                    SvtCallJunctionStats, SvtCallMergeStats, SvtCallParams, SvtCallSplitStats, SvtCallStats, SvtGtParams, SvtInsseqView, SvtJunctionView, SvtLoadStats, SvtParams, SvtPoaParams,
-                   SvtWork, has_call, has_call_merge, has_call_split, has_callseq, has_evidence, has_genotype, has_junctions, load_engine, ptr)
+                   SvtWork, has_call, has_call_merge, has_call_split, has_callseq, has_evidence, has_genotype, has_junctions, has_rearr, load_engine, ptr)
 from .pileup import Pileup
 
 # params.h:27-32
@@ -154,6 +154,12 @@ class Engine:
             raise SvtError(SVT_EINVAL, "this backend does not export svt_load_junctions (include/svtrek_junction.h): "
                                        "calls from split alignments need the HIP engine 0.32.0 or later")
 
+    def _need_rearr(self) -> None:
+        self._need_junctions()
+        if not has_rearr(self.lib):
+            raise SvtError(SVT_EINVAL, "this backend does not export svt_call_rearr_stats_get (include/svtrek_rearr.h): "
+                                       "DUP / INV calls need the HIP engine 0.33.0 or later")
+
     def load_junctions(self, read, off, seg) -> None:
         """The segment table of the loaded pileup's records that carry an SA tag (svt_load_junctions,
         include/svtrek_junction.h): read uint64 [n] ascending pileup read indices, off uint64 [n + 1], seg
@@ -172,7 +178,7 @@ class Engine:
 
     def call(self, link: int | None = None, min_support: int | None = None, types=("DEL", "INS"),
              len_permille: int | None = None, merge_gap: int | None = None, merge_min: int | None = None,
-             junctions: bool = False) -> np.ndarray:
+             junctions: bool = False, rearrangements=()) -> np.ndarray:
         """Cluster the pileup's D > 50 / I >= 50 ops by start (svt_call_scan): CALL_DTYPE records in
         (chrom, pos, type, len) order.  link: the largest gap between neighbouring starts of one
         cluster (default 10); min_support: the fewest ops of a call (default consensus_min_count);
@@ -181,8 +187,14 @@ class Engine:
         merge_gap: 1 .. 2^20 joins a read's D (I) ops of at least merge_min bases (1 .. 50, default 20)
         that lie within merge_gap bases of each other into one item of their summed length before
         clustering -- 180D 5M 120D counts as one 300 bp deletion (default 0: single ops only);
-        junctions: the DEL / INS items of split alignments (load_junctions) join the CIGAR items."""
+        junctions: the DEL / INS items of split alignments (load_junctions) join the CIGAR items;
+        rearrangements: "DUP" and / or "INV" (a sequence or a comma string) adds the tandem duplications /
+        inversions that the split alignments of load_junctions show (include/svtrek_rearr.h) to the same
+        list; `types` keeps naming DEL / INS only and may be empty then."""
         self._need_call()
+        rearr = rearr_type_bits(rearrangements)
+        if rearr:
+            self._need_rearr()
         if junctions:
             self._need_junctions()
         if len_permille:
@@ -196,6 +208,8 @@ class Engine:
         if min_support is not None:
             p.min_support = int(min_support)
         p.types = call_type_bits(types)
+        if rearr:   # (an older engine never sees the field)
+            p.rearr = rearr
         if len_permille is not None:
             if not 0 <= int(len_permille) <= 0xffffffff:
                 raise SvtError(SVT_EINVAL, "call: len_permille in [0, 1000]")
@@ -255,6 +269,14 @@ class Engine:
         st = SvtCallJunctionStats()
         self._check(self.lib.svt_call_junction_stats_get(self._h, C.byref(st)))
         return {k: (float(getattr(st, k)) if k == "build_ms" else int(getattr(st, k))) for k, _ in SvtCallJunctionStats._fields_}
+
+    def call_rearr_stats(self) -> dict:
+        """{dup_items, inv_items, skipped, clusters, calls, build_ms} of the last call(): all zero without
+        rearrangements."""
+        self._need_rearr()
+        st = SvtCallRearrStats()
+        self._check(self.lib.svt_call_rearr_stats_get(self._h, C.byref(st)))
+        return {k: (float(getattr(st, k)) if k == "build_ms" else int(getattr(st, k))) for k, _ in SvtCallRearrStats._fields_}
 
     # ---- consensus inserted sequence of the INS calls (include/svtrek_callseq.h)
     def _need_callseq(self) -> None:
@@ -460,6 +482,18 @@ def call_type_bits(types) -> int:
     for t in names:
         if str(t).strip().upper() not in code:
             raise ValueError(f"call: unknown type {t!r} (DEL, INS)")
+        bits |= 1 << code[str(t).strip().upper()]
+    return bits
+
+
+def rearr_type_bits(types) -> int:
+    """svt_call_params.rearr of DUP / INV names (a comma-separated string or a sequence; empty: 0)."""
+    names = [t for t in types.split(",") if t.strip()] if isinstance(types, str) else list(types)
+    code = {"DUP": SVT_DUP, "INV": SVT_INV}
+    bits = 0
+    for t in names:
+        if str(t).strip().upper() not in code:
+            raise ValueError(f"call: unknown rearrangement {t!r} (DUP, INV)")
         bits |= 1 << code[str(t).strip().upper()]
     return bits
 

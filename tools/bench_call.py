@@ -30,6 +30,13 @@ svt_call_params.junctions = 1 and adds the junction statistics, the build of the
 builds, each forced by reloading the table) with its algorithmic bytes -- the base events copied once (16 B read
 + 16 B written), 24 B per segment row, 16 B per junction event -- the same process's plain scan and, for scale, the merged index's build at gap 50 on the side.  The cut is
 pure Python, one read at a time: --loci N shrinks the workload to N loci for it.
+
+--rearr SHARE cuts that share of the supporting reads the same way and then rewrites each cut read's second
+alignment in the segment table, per 4-kb stretch of the reference either onto the other strand (an inverted
+pair) or upstream of the first by the op's length + 100 (a duplicated pair), scans with svt_call_params.rearr =
+DUP | INV (include/svtrek_rearr.h) and adds the rearrangement statistics, the build of the rearrangement index
+(--merge-builds builds, each forced by reloading the table) with its algorithmic bytes -- 24 B per segment row
+read twice, 16 B per event written -- and the same process's plain scan next to the two-pass one.
 """
 from __future__ import annotations
 
@@ -180,6 +187,56 @@ def junction_out(a, eng, table) -> dict:
             "plain_events": eng.call_stats()["events"], "plain_calls": eng.call_stats()["calls"]}
 
 
+def rearr_cut(a, pl):
+    """(pileup, table) with --rearr's share of the supporting reads cut and their second alignments rewritten."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import junction_ref as J
+    keep, a.junctions = a.junctions, a.rearr
+    out, (read, off, seg) = junction_cut(a, pl)
+    a.junctions = keep
+    seg = seg.copy()
+    for k in range(len(read)):
+        r0, r1 = int(off[k]), int(off[k + 1])
+        j = J.junction(seg[r0:r1])
+        if r1 - r0 != 2 or j is None or j[0] in ("other", "none"):
+            continue
+        A, B, ln = seg[r0], seg[r0 + 1], int(j[3])
+        if (int(j[2]) >> 12) & 1:                      # an inverted pair
+            B["strand"] ^= 1
+        elif int(A["strand"]) == 0:                    # a duplicated pair: Rt = B starts ln + 100 before Lf = A ends
+            w = int(B["r_end"]) - int(B["r_beg"])
+            B["r_beg"] = max(int(A["r_end"]) - ln - 100, 0)
+            B["r_end"] = int(B["r_beg"]) + w
+        else:                                          # ... on strand -: Lf = B ends ln + 100 behind the start of Rt = A
+            w = int(B["r_end"]) - int(B["r_beg"])
+            B["r_end"] = int(A["r_beg"]) + ln + 100
+            B["r_beg"] = max(int(B["r_end"]) - w, 0)
+    return out, (read, off, seg)
+
+
+def rearr_out(a, eng, table) -> dict:
+    """The rearrangement statistics, the index build's time over --merge-builds builds, its bytes, the plain scan beside it."""
+    if not a.rearr:
+        return {}
+    rs = eng.call_rearr_stats()
+    kw = split_kw(a)
+    build = []
+    for _ in range(a.merge_builds):
+        eng.load_junctions(*table)   # the same table again: the index is dropped
+        eng.call(link=a.link, min_support=a.min_support, rearrangements=("DUP", "INV"), **kw)
+        build.append(eng.call_rearr_stats()["build_ms"])
+    plain = []
+    for k in range(a.warmup + a.repeat):
+        eng.call(link=a.link, min_support=a.min_support, **kw)
+        if k >= a.warmup:
+            plain.append(eng.call_stats()["scan_ms"])
+    return {"rearr": a.rearr, "rearr_stats": rs, "rearr_build_ms": round(float(np.median(build)), 4),
+            "rearr_build_ms_all": [round(x, 4) for x in build],
+            "rearr_build_alg_bytes": 2 * 24 * int(len(table[2])) + 16 * (rs["dup_items"] + rs["inv_items"]),
+            "plain_scan_ms": round(float(np.median(plain)), 4), "plain_scan_ms_all": [round(x, 4) for x in plain],
+            "plain_events": eng.call_stats()["events"], "plain_calls": eng.call_stats()["calls"]}
+
+
 def split_out(a, eng) -> dict:
     return {"len_permille": a.len_permille, "split_stats": eng.call_split_stats()} if a.len_permille else {}
 
@@ -197,6 +254,7 @@ def main() -> None:
     ap.add_argument("--merge-min", type=int, default=20)
     ap.add_argument("--merge-builds", type=int, default=5)
     ap.add_argument("--junctions", type=float, default=0.0)
+    ap.add_argument("--rearr", type=float, default=0.0)
     ap.add_argument("--loci", type=int, default=0)
     ap.add_argument("--hotspot", type=int, default=0)
     ap.add_argument("--hotspot-last", action="store_true")
@@ -212,8 +270,12 @@ def main() -> None:
         cfg = replace(cfg, n_loci=a.loci)
     r = sim.generate(cfg)
     table = None
+    if a.junctions and a.rearr:
+        ap.error("--junctions and --rearr each cut the workload: one at a time")
     if a.junctions:
         r.pileup, table = junction_cut(a, r.pileup)
+    if a.rearr:
+        r.pileup, table = rearr_cut(a, r.pileup)
     t_gen = time.perf_counter() - t0
     eng = Engine(Params(), device=0)
     eng.load_pileup(r.pileup)
@@ -235,7 +297,8 @@ def main() -> None:
     calls = None
     for k in range(a.warmup + a.repeat):
         t0 = time.perf_counter()
-        calls = eng.call(link=a.link, min_support=a.min_support, **split_kw(a), **({"junctions": True} if a.junctions else {}))
+        calls = eng.call(link=a.link, min_support=a.min_support, **split_kw(a), **({"junctions": True} if a.junctions else {}),
+                         **({"rearrangements": ("DUP", "INV")} if a.rearr else {}))
         t1 = time.perf_counter()
         if k >= a.warmup:
             scan_ms.append(eng.call_stats()["scan_ms"])
@@ -257,7 +320,8 @@ def main() -> None:
         js = jout["junction_stats"]
         base = keys - js["del_items"] - js["ins_items"]
         jout["junction_build_alg_bytes"] = 32 * base + 24 * js["segments"] + 16 * (js["del_items"] + js["ins_items"])
-    alg = 16 * keys + 8 * keys + 2 * 8 * keys + 48 * st["calls"]
+    rout = rearr_out(a, eng, table)
+    alg = 16 * keys + 8 * keys + 2 * 8 * keys + 48 * st["calls"] + (48 * st["calls"] if a.rearr else 0)   # (the merge of the two lists)
     print(json.dumps({
         "metric": "svt_call_scan ms (1 GPU)", "value": round(med, 4), "unit": "ms",
         "workload": a.workload, "reads": int(r.pileup.n_reads), "cigar_ops": int(r.pileup.cig_off[-1]),
@@ -268,7 +332,7 @@ def main() -> None:
                   f"{a.repeat} after {a.warmup} warm-up scans; call_wall: Engine.call with the fetch; reindex: HIP events "
                   "around svt_reindex on one stream",
         "events": st["events"], "skipped": st["skipped"], "clusters": st["clusters"], "calls": st["calls"],
-        "big_buckets": st["big_buckets"], **split_out(a, eng), **merge_out(a, eng), **jout, "events_read": keys,
+        "big_buckets": st["big_buckets"], **split_out(a, eng), **merge_out(a, eng), **jout, **rout, "events_read": keys,
         "alg_bytes_per_scan": alg, "alg_gbs": round(alg / (med * 1e-3) / 1e9, 2),
         "alg": "per event of arrays S and I (items + trailing-S markers): 16 B read + 8 B key written + 2 x 8 B key read; "
                "48 B per call",
