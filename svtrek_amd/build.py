@@ -22,6 +22,8 @@ CSRC = os.path.join(PKG, "csrc")
 INC = os.path.join(ROOT, "include")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("SVT_OFFLOAD_ARCH", "gfx950")
+PUBLIC_HDRS = [os.path.join(INC, f) for f in ("svtrek_gpu.h", "svtrek_evidence.h", "svtrek_call.h", "svtrek_genotype.h",
+                                              "svtrek_callseq.h", "svtrek_junction.h", "svtrek_rearr.h")]
 
 
 def _run(cmd: list[str], cwd: str | None = None) -> None:
@@ -41,10 +43,7 @@ def _engine_deps() -> list[str]:
     """The engine's one translation unit first, then everything it includes: every csrc/*.inc,
     svt_bamrec.h and the public headers."""
     incs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".inc"))
-    return [os.path.join(CSRC, "svt_engine.hip")] + incs + \
-        [os.path.join(CSRC, "svt_bamrec.h"), os.path.join(INC, "svtrek_gpu.h"), os.path.join(INC, "svtrek_evidence.h"),
-            os.path.join(INC, "svtrek_call.h"), os.path.join(INC, "svtrek_genotype.h"), os.path.join(INC, "svtrek_callseq.h"),
-            os.path.join(INC, "svtrek_junction.h"), os.path.join(INC, "svtrek_rearr.h")]
+    return [os.path.join(CSRC, "svt_engine.hip")] + incs + [os.path.join(CSRC, "svt_bamrec.h")] + PUBLIC_HDRS
 
 
 def build_engine(force: bool = False) -> str:
@@ -71,9 +70,7 @@ def build_test_engine(force: bool = False) -> str:
 def build_host(force: bool = False) -> str:
     out = os.path.join(PKG, "libsvtrek_host.so")
     srcs = [os.path.join(CSRC, f) for f in ("bam_ingest.cpp", "vcf_audit.cpp")]
-    hdrs = [os.path.join(CSRC, "svtrek_host.h"), os.path.join(INC, "svtrek_gpu.h"), os.path.join(INC, "svtrek_evidence.h"),
-            os.path.join(INC, "svtrek_call.h"), os.path.join(INC, "svtrek_genotype.h"), os.path.join(INC, "svtrek_callseq.h"),
-            os.path.join(INC, "svtrek_junction.h"), os.path.join(INC, "svtrek_rearr.h"), os.path.join(CSRC, "svt_bamrec.h")]
+    hdrs = [os.path.join(CSRC, "svtrek_host.h")] + PUBLIC_HDRS + [os.path.join(CSRC, "svt_bamrec.h")]
     if all(os.path.exists(s) for s in srcs) and (force or _stale(out, srcs + hdrs)):
         _run(["g++", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-pthread",
               "-I", INC, "-o", out] + srcs + ["-lz", "-ldl"])
@@ -84,9 +81,7 @@ def build_cli(force: bool = False) -> str:
     out = os.path.join(PKG, "svtrek")
     main = os.path.join(CSRC, "svtrek_main.cpp")
     srcs = [main] + [os.path.join(CSRC, f) for f in ("bam_ingest.cpp", "vcf_audit.cpp")]
-    hdrs = [os.path.join(CSRC, "svtrek_host.h"), os.path.join(INC, "svtrek_gpu.h"), os.path.join(INC, "svtrek_evidence.h"),
-            os.path.join(INC, "svtrek_call.h"), os.path.join(INC, "svtrek_genotype.h"), os.path.join(INC, "svtrek_callseq.h"),
-            os.path.join(INC, "svtrek_junction.h"), os.path.join(INC, "svtrek_rearr.h"), os.path.join(CSRC, "svt_bamrec.h")]
+    hdrs = [os.path.join(CSRC, "svtrek_host.h")] + PUBLIC_HDRS + [os.path.join(CSRC, "svt_bamrec.h")]
     eng = os.path.join(PKG, "libsvtrek_hip.so")
     if all(os.path.exists(s) for s in srcs) and (force or _stale(out, srcs + hdrs + [eng])):
         _run(["g++", "-O3", "-std=c++17", "-Wall", "-Wextra", "-pthread", "-I", INC, "-o", out] + srcs +

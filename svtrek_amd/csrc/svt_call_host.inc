@@ -6,70 +6,43 @@ namespace {
 
 constexpr const char *CALL_MEM = "svt_call_scan: device scratch";
 
-// The index a scan runs on: the value buckets, the merged index (merge_gap > 0) in their shape, or the
-// union of either with the junction events (junctions = 1).  The segments depend on the extents, so
-// each has its own; the rest of the scratch is shared and only ever grown.
+// The index a scan runs on: the value buckets, or a derived index in their shape (CallIndex) -- the
+// merged index (merge_gap > 0), the union of either with the junction events (junctions = 1), the
+// rearrangement index (the second pass of rearr != 0).  The segments depend on the extents, so each has
+// its own; the rest of the scratch is shared and only ever grown.
 struct CallView {
     BkIndex bk;
     uint64_t n_s, n_i;            // events of arrays S and I
-    bool *ready;
-    uint64_t *n_seg;
-    DevBuf<uint64_t> *d_seg;
+    CallSegs *segs;
 };
-CallView call_view(svt_ctx *c, bool merged, bool junction = false) {
-    CallScratch &k = c->call;
-    CallView v{make_args(c, nullptr, nullptr, 0, false).bk, c->bk_events[BA_S], c->bk_events[BA_I], &k.ready, &k.n_seg, &k.d_seg};
-    if (merged) {
-        v.bk.ev = k.mg.d_ev;
-        v.bk.off = k.mg.d_off;
-        v.bk.pm = nullptr;        // (the refine side's: no kernel of the scan or the genotypes reads it)
-        v.n_s = k.mg.events[0];
-        v.n_i = k.mg.events[1];
-        v.ready = &k.mg.ready;
-        v.n_seg = &k.mg.n_seg;
-        v.d_seg = &k.mg.d_seg;
-    }
-    if (junction) {               // (built on the view above: svt_junction_host.inc)
-        v.bk.ev = k.jn.d_ev;
-        v.bk.off = k.jn.d_off;
-        v.bk.pm = nullptr;
-        v.n_s = k.jn.events[0];
-        v.n_i = k.jn.events[1];
-        v.ready = &k.jn.ready;
-        v.n_seg = &k.jn.n_seg;
-        v.d_seg = &k.jn.d_seg;
-    }
+CallView plain_view(svt_ctx *c) {
+    return CallView{make_args(c, nullptr, nullptr, 0, false).bk, c->bk_events[BA_S], c->bk_events[BA_I], &c->call.segs};
+}
+CallView index_view(svt_ctx *c, CallIndex &ix) {
+    CallView v{plain_view(c).bk, ix.events[0], ix.events[1], &ix.segs};
+    v.bk.ev = ix.d_ev;
+    v.bk.off = ix.d_off;
+    v.bk.pm = nullptr;            // (the refine side's: no kernel of the scan or the genotypes reads it)
     return v;
+}
+// (the union is built on the merged index where both are asked for: svt_junction_host.inc)
+CallView call_view(svt_ctx *c, bool merged, bool junction) {
+    return junction ? index_view(c, c->call.jn) : merged ? index_view(c, c->call.mg) : plain_view(c);
 }
 
 svt_status junction_build(svt_ctx *c, uint32_t gap, uint32_t min_len);   // svt_junction_host.inc
 svt_status rearr_build(svt_ctx *c);                                      // svt_rearr_host.inc
 
-// The rearrangement index (rearr != 0; svt_rearr_host.inc builds it): rows S and I hold the DUP and the INV events.
-CallView rearr_view(svt_ctx *c) {
-    CallScratch &k = c->call;
-    CallView v = call_view(c, false);
-    v.bk.ev = k.rr.d_ev;
-    v.bk.off = k.rr.d_off;
-    v.bk.pm = nullptr;
-    v.n_s = k.rr.events[0];
-    v.n_i = k.rr.events[1];
-    v.ready = &k.rr.ready;
-    v.n_seg = &k.rr.n_seg;
-    v.d_seg = &k.rr.d_seg;
-    return v;
-}
-
 // The first scan of a loaded pileup (of a merged index): the segments (the buckets' extents are those
 // of the load for every rebuild) and the scratch that depends on the event counts alone.
 svt_status call_prepare(svt_ctx *c, const CallView &v) {
     CallScratch &k = c->call;
-    if (*v.ready) return SVT_OK;
+    if (v.segs->ready) return SVT_OK;
     const uint64_t nb2 = 2 * c->bk_n, N = v.n_s + v.n_i;
     svt_status s;
     DevBuf<uint8_t> d_flag;
-    DevBuf<uint64_t> &d_seg = *v.d_seg;
-    uint64_t &n_seg = *v.n_seg;
+    DevBuf<uint64_t> &d_seg = v.segs->d_seg;
+    uint64_t &n_seg = v.segs->n_seg;
     if ((s = nomem(c, d_flag.reserve(nb2), CALL_MEM)) || (s = nomem(c, d_seg.reserve(nb2), CALL_MEM)) ||
         (s = nomem(c, k.d_ctr.reserve(8), CALL_MEM)))
         return s;
@@ -92,7 +65,7 @@ svt_status call_prepare(svt_ctx *c, const CallView &v) {
                                                  (int)n_seg, nullptr));
     HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(nullptr, t2, k.d_cid.get(), k.d_cid.get(), (int)std::max<uint64_t>(N, 1), nullptr));
     if ((s = nomem(c, k.d_tmp.reserve(std::max(t1, t2)), CALL_MEM))) return s;
-    *v.ready = true;
+    v.segs->ready = true;
     return SVT_OK;
 }
 
@@ -155,7 +128,7 @@ svt_status call_split_1(svt_ctx *c, const CallArgs &a, uint32_t n_keys, uint32_t
     hipLaunchKernelGGL(call_unit_kernel, cg, cb, 0, nullptr, a, sp, ncl);
     if (ncand) hipLaunchKernelGGL(call_order_kernel, sg, sb, 0, nullptr, a, sp);
     HIP_TRY(c, hipGetLastError());
-    k.split.candidates += ncand;   // (zeroed when the scan began; a scan with rearr != 0 has two passes)
+    k.last.split_stats.candidates += ncand;   // (zeroed when the scan began; a scan with rearr != 0 has two passes)
     return SVT_OK;
 }
 
@@ -173,7 +146,7 @@ svt_status call_pass(svt_ctx *c, const svt_call_params *p, const CallView &v, ui
     const uint64_t N = v.n_s + v.n_i;
     svt_status s;
     if ((s = call_prepare(c, v))) return s;
-    const uint64_t n_seg = *v.n_seg;
+    const uint64_t n_seg = v.segs->n_seg;
     const KArgs ka = make_args(c, nullptr, nullptr, 0, false);
     CallArgs a{};
     a.bk = v.bk;
@@ -181,7 +154,7 @@ svt_status call_pass(svt_ctx *c, const svt_call_params *p, const CallView &v, ui
     a.nt = c->n_targets;
     a.n_s = (uint32_t)v.n_s;
     a.n_seg = n_seg;
-    a.seg = v.d_seg->get();
+    a.seg = v.segs->d_seg.get();
     a.keys = k.d_keys;
     a.cid = k.d_cid;
     a.tmax = k.d_tmax;
@@ -261,15 +234,15 @@ svt_status call_pass_stats(svt_ctx *c, const CallPass &ps, unsigned long long *s
     if (ps.split) {
         unsigned long long ss[3] = {};
         HIP_TRY(c, hipMemcpy(ss, k.d_sctr, sizeof ss, hipMemcpyDeviceToHost));
-        k.split.split += ss[0];
-        k.split.groups += ss[1];
-        k.split.big += ss[2];
+        k.last.split_stats.split += ss[0];
+        k.last.split_stats.groups += ss[1];
+        k.last.split_stats.big += ss[2];
     }
-    k.stats.events += st[0];
-    k.stats.skipped += st[1];
-    k.stats.big_buckets += st[2];
-    k.stats.clusters += ps.ncl;
-    k.stats.calls += ps.npick;
+    k.last.call_stats.events += st[0];
+    k.last.call_stats.skipped += st[1];
+    k.last.call_stats.big_buckets += st[2];
+    k.last.call_stats.clusters += ps.ncl;
+    k.last.call_stats.calls += ps.npick;
     if (skipped) *skipped = st[1];
     return SVT_OK;
 }
@@ -278,39 +251,33 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
     CallScratch &k = c->call;
     k.n_calls = 0;
     k.scanned = true;
-    k.stats = svt_call_stats{};
-    k.split = svt_call_split_stats{};
-    k.merge = svt_call_merge_stats{};
-    k.junction = svt_call_junction_stats{};
-    k.rearr = svt_call_rearr_stats{};
+    k.last = CallScratch::Last{};   // (what it ran on: set once that index is built)
     const bool merged = p->merge_gap != 0u, junction = p->junctions != 0u;
     const uint32_t rearr = p->rearr, base_types = p->types & ((1u << SVT_INS) | (1u << SVT_DEL));
-    k.last_merged = k.last_junction = false;   // (set once the index the scan runs on is built)
-    k.last_rearr = 0;
     *n_calls = 0;
     if (c->n_reads == 0) {   // (no index to build: every site of such a pileup is invalid)
-        k.last_merged = merged;
-        k.last_junction = junction;
-        k.last_rearr = rearr;
+        k.last.merged = merged;
+        k.last.junction = junction;
+        k.last.rearr = rearr;
         return SVT_OK;
     }
     svt_status s = order_on(c, nullptr);   // after every launch already issued (svt_reindex rebuilds the buckets)
     if (s) return s;
     if (merged) {   // (before the scan's clock: the build runs once per pileup and (gap, min))
         if ((s = callmerge_build(c, p->merge_gap, p->merge_min))) return s;
-        k.merge = k.mg.stats;
+        k.last.merge_stats = k.mg.stats;
     }
     if (junction) {   // (likewise: once per pileup, table and base view)
         if ((s = junction_build(c, p->merge_gap, p->merge_min))) return s;
-        k.junction = k.jn.stats;
+        k.last.junction_stats = k.jn.stats;
     }
     if (rearr) {   // (likewise: once per pileup and table)
         if ((s = rearr_build(c))) return s;
-        k.rearr = k.rr.stats;
+        k.last.rearr_stats = k.rr.stats;
     }
-    k.last_merged = merged;
-    k.last_junction = junction;
-    k.last_rearr = rearr;
+    k.last.merged = merged;
+    k.last.junction = junction;
+    k.last.rearr = rearr;
     const CallView v = call_view(c, merged, junction);
     const uint64_t N = base_types ? v.n_s + v.n_i : 0;   // (no DEL / INS bit: a rearrangement-only scan)
     if (N == 0 && !rearr) return SVT_OK;
@@ -318,15 +285,15 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
     HIP_TRY(c, e0.create());
     HIP_TRY(c, e1.create());
     HIP_TRY(c, hipEventRecord(e0, nullptr));
-    CallPass ps{};
+    CallPass ps{}, pr{};   // the pass over v, the second pass
     if (N && (s = call_pass(c, p, v, p->types, false, rearr ? k.rr.d_a : k.d_calls, &ps))) return s;
     uint64_t total = ps.npick;
+    bool second = false;
     if (rearr) {   // the second pass, over the rearrangement index, and the merge of the two lists (svt_rearr.inc)
-        if (N && (s = call_pass_stats(c, ps))) return s;
-        const CallView rv = rearr_view(c);
-        CallPass pr{};
+        if (N && (s = call_pass_stats(c, ps))) return s;   // (before the second pass reuses k.d_ctr)
+        const CallView rv = index_view(c, k.rr);
         const uint32_t rtypes = ((rearr >> SVT_DUP) & 1u) << SVT_DEL | ((rearr >> SVT_INV) & 1u) << SVT_INS;
-        const bool second = rv.n_s + rv.n_i != 0;
+        second = rv.n_s + rv.n_i != 0;
         if (second && (s = call_pass(c, p, rv, rtypes, true, k.rr.d_b, &pr))) return s;
         total += pr.npick;
         if (total > 0x7fffffffull) return fail(c, SVT_ESTATE, "%s", "svt_call_scan: more than 2^31 - 1 calls are not supported");
@@ -336,23 +303,21 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
                                ps.npick, k.rr.d_b.get(), pr.npick, k.d_calls.get());
             HIP_TRY(c, hipGetLastError());
         }
-        HIP_TRY(c, hipEventRecord(e1, nullptr));
-        HIP_TRY(c, hipEventSynchronize(e1));
-        if (second) {   // (no counters of a pass that did not run)
-            unsigned long long skipped = 0;
-            if ((s = call_pass_stats(c, pr, &skipped))) return s;
-            k.rearr.skipped = skipped;
-            k.rearr.clusters = pr.ncl;
-            k.rearr.calls = pr.npick;
-        }
-    } else {
-        HIP_TRY(c, hipEventRecord(e1, nullptr));
-        HIP_TRY(c, hipEventSynchronize(e1));
-        if ((s = call_pass_stats(c, ps))) return s;
+    }
+    HIP_TRY(c, hipEventRecord(e1, nullptr));
+    HIP_TRY(c, hipEventSynchronize(e1));
+    if (second) {   // (no counters of a pass that did not run)
+        unsigned long long skipped = 0;
+        if ((s = call_pass_stats(c, pr, &skipped))) return s;
+        k.last.rearr_stats.skipped = skipped;
+        k.last.rearr_stats.clusters = pr.ncl;
+        k.last.rearr_stats.calls = pr.npick;
+    } else if (!rearr && (s = call_pass_stats(c, ps))) {
+        return s;
     }
     float ms = 0.f;
     HIP_TRY(c, hipEventElapsedTime(&ms, e0, e1));
-    k.stats.scan_ms = ms;
+    k.last.call_stats.scan_ms = ms;
     k.n_calls = total;
     *n_calls = total;
     return SVT_OK;
@@ -417,18 +382,18 @@ svt_status svt_call_device(svt_ctx *c, const svt_call **d_calls, uint64_t *n) {
 
 svt_status svt_call_stats_get(const svt_ctx *c, svt_call_stats *out) {
     if (!c || !out) return SVT_EINVAL;
-    *out = c->call.stats;
+    *out = c->call.last.call_stats;
     return SVT_OK;
 }
 
 svt_status svt_call_split_stats_get(const svt_ctx *c, svt_call_split_stats *out) {
     if (!c || !out) return SVT_EINVAL;
-    *out = c->call.split;
+    *out = c->call.last.split_stats;
     return SVT_OK;
 }
 
 svt_status svt_call_merge_stats_get(const svt_ctx *c, svt_call_merge_stats *out) {
     if (!c || !out) return SVT_EINVAL;
-    *out = c->call.merge;
+    *out = c->call.last.merge_stats;
     return SVT_OK;
 }

@@ -1,14 +1,12 @@
 // svt_callmerge.inc -- a read's fragmented D / I ops joined into merged items (include/svtrek_call.h,
-// svt_call_params.merge_gap > 0; included by svt_engine.hip after svt_bucket_build.inc, the host side
-// is svt_callmerge_host.inc).
+// svt_call_params.merge_gap > 0; included by svt_engine.hip after svt_callindex.inc, whose BkFile,
+// bk_file and bk_stat_add it uses; the host side is svt_callmerge_host.inc).
 //
 // The merged items go into a SECOND index with the value buckets' own shape -- 16-B events {x,
 // L << 4 | OP_DEL / OP_INS, endpos, read pos} filed by x under the main index's cbase / cnb / nbk, an
 // off[BA_N][nbk + 1] table of which rows S and I are filled -- so that call_sort_kernel ..
-// call_emit_kernel, the split kernels and genotype_kernel run on it unchanged.  It is built by two
-// passes of ONE kernel over the CIGAR stream, as the load's index is: callmerge_kernel<true> counts
-// the items per (array, bucket), an exclusive sum gives the extents, callmerge_kernel<false> files
-// them through atomic cursors.  The order inside a bucket is whatever the atomics give.
+// call_emit_kernel, the split kernels and genotype_kernel run on it unchanged.  It is built by the two
+// passes of svt_callindex.inc, both of them callmerge_kernel's walk over the CIGAR stream.
 //
 // The walk, a TEAM of lanes per read and TEAM ops a trip -- the whole wave for long reads (coalesced
 // 256-B loads of the stream), 16 lanes and four reads a wave for short ones (callmerge_build picks by
@@ -28,8 +26,7 @@
 // Both types go through the same code in the same pass; a trip without a fragment of a type costs
 // that type one ballot.  No LDS, no serial loop over lanes; the loops and the per-type skip are
 // wave-uniform, the rest is predicated per lane.
-constexpr uint32_t CM_SLOTS = 1024;   // the stats are added into CM_SLOTS x 4 counters by wave number
-                                      // (same-address atomics from every wave serialise in the L2)
+constexpr int CM_NSTAT = 4;           // fragments, runs, joined items, items
 constexpr uint32_t CM_LEN_MAX = (1u << 28) - 1u;
 
 struct CallMergeArgs {
@@ -37,15 +34,7 @@ struct CallMergeArgs {
     const uint64_t *soff;         // [n_reads + 1]
     const uint4 *rec;             // {pos, endpos, n_cigar | clip << 30, contig}
     uint64_t n_reads;
-    const uint64_t *cbase;        // the main index's
-    const uint32_t *cnb;
-    uint64_t nbk;
-    uint32_t *off;                // [BA_N][nbk + 1]: COUNT the counts of rows S and I, else their extents
-    uint32_t *cur;                // [2][nbk + 1] cursors of the filing pass (zeroed)
-    uint4 *ev;
-    uint32_t n_ev;
-    unsigned long long *stat;     // [CM_SLOTS][4] fragments, runs, joined items, items (COUNT)
-    uint32_t *err;                // set when a slot falls outside its bucket's extent
+    BkFile f;                     // stat: [BK_SLOTS][CM_NSTAT]
     uint32_t gap, min_len;
 };
 
@@ -55,15 +44,7 @@ __device__ __forceinline__ bool cm_emit(const CallMergeArgs &a, int T, uint64_t 
                                         uint32_t pos, uint32_t endp) {
     if (!(T ? L >= (uint64_t)SV_MIN_LENGTH : L > (uint64_t)SV_MIN_LENGTH)) return false;
     const uint32_t x = (uint32_t)min(fx, (uint64_t)IX_SAT), len = (uint32_t)min(L, (uint64_t)CM_LEN_MAX);
-    const uint64_t row = (uint64_t)(T ? BA_I : BA_S) * (a.nbk + 1), g = cb + min(x >> BKS, nbt - 1u);
-    if (COUNT) {
-        atomicAdd(&a.off[row + g], 1u);
-    } else {
-        const uint32_t o0 = a.off[row + g], n = a.off[row + g + 1] - o0;
-        const uint32_t sl = atomicAdd(&a.cur[(uint64_t)T * (a.nbk + 1) + g], 1u);
-        if (sl >= n || o0 + sl >= a.n_ev) *a.err = 1u;
-        else a.ev[o0 + sl] = make_uint4(x, len << 4 | (T ? OP_INS : OP_DEL), endp, pos);
-    }
+    bk_file<COUNT>(a.f, T, cb + min(x >> BKS, nbt - 1u), 0u, make_uint4(x, len << 4 | (T ? OP_INS : OP_DEL), endp, pos));
     return true;
 }
 
@@ -105,8 +86,8 @@ __global__ __launch_bounds__(64 * WPB) void callmerge_kernel(CallMergeArgs a) {
     const uint4 rc = act ? a.rec[r] : make_uint4(0, 0, 0, 0);
     const uint32_t pos = cm_uni<TEAM>(rc.x), endp = cm_uni<TEAM>(rc.y), tid = cm_uni<TEAM>(rc.w);
     const uint64_t s = cm_uni64<TEAM>(act ? a.soff[r] : 0ull), e = cm_uni64<TEAM>(act ? a.soff[r + 1] : 0ull);
-    const uint64_t cb = act ? a.cbase[tid] : 0ull;
-    const uint32_t nbt = act ? a.cnb[tid] : 1u;
+    const uint64_t cb = act ? a.f.cbase[tid] : 0ull;
+    const uint32_t nbt = act ? a.f.cnb[tid] : 1u;
     const uint64_t tmask = TEAM == WAVE ? ~0ull : ((1ull << (TEAM & 63)) - 1ull) << tb;
     const uint64_t below = ((1ull << ln) - 1ull) & tmask, upto = ((2ull << ln) - 1ull) & tmask;   // (lane 63: 2 << 63 == 0, all ones)
     uint64_t carry = pos;                       // the walk position before the trip's first op
@@ -183,17 +164,7 @@ __global__ __launch_bounds__(64 * WPB) void callmerge_kernel(CallMergeArgs a) {
         }
     }
     if (COUNT && ballot(st_frag != 0u)) {
-        uint32_t v[4] = {tl == 0 ? st_frag : 0u, tl == 0 ? st_runs : 0u, st_join, st_items};
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1)
-#pragma unroll
-            for (int q = 0; q < 4; q++) v[q] += (uint32_t)__shfl_xor((int)v[q], d, WAVE);
-        if (ln == 0) {
-            unsigned long long *q = a.stat + 4u * (uint32_t)(wv & (CM_SLOTS - 1u));
-            atomicAdd(&q[0], (unsigned long long)v[0]);
-            atomicAdd(&q[1], (unsigned long long)v[1]);
-            if (v[2]) atomicAdd(&q[2], (unsigned long long)v[2]);
-            if (v[3]) atomicAdd(&q[3], (unsigned long long)v[3]);
-        }
+        uint32_t v[CM_NSTAT] = {tl == 0 ? st_frag : 0u, tl == 0 ? st_runs : 0u, st_join, st_items};
+        bk_stat_add(a.f, v);
     }
 }

@@ -122,12 +122,12 @@ svt_status svt_call_consensus(svt_ctx *c, const svt_poa_params *p, uint64_t firs
     if (!c || !p) return SVT_EINVAL;
     if (!c->loaded) return fail(c, SVT_ESTATE, "%s", "svt_load_pileup not called");
     if (!c->call.scanned) return fail(c, SVT_ESTATE, "%s", "svt_call_consensus: no svt_call_scan of the loaded pileup");
-    if (c->call.last_merged)
+    if (c->call.last.merged)
         return fail(c, SVT_ESTATE, "%s", "svt_call_consensus: the last scan merged fragments (merge_gap > 0): no inserted bases for merged calls");
-    if (c->call.last_junction)
+    if (c->call.last.junction)
         return fail(c, SVT_ESTATE, "%s", "svt_call_consensus: the last scan read split alignments (junctions = 1): no inserted bases for junction calls");
     if (!c->insseq_loaded) return fail(c, SVT_ESTATE, "%s", "svt_load_insseq not called");
-    if (c->call.last_rearr)
+    if (c->call.last.rearr)
         return fail(c, SVT_ESTATE, "%s", "svt_call_consensus: the last scan called rearrangements (rearr != 0): scan without them for inserted bases");
     if (first > c->call.n_calls || n > c->call.n_calls - first)
         return fail(c, SVT_EINVAL, "%s", "svt_call_consensus: range past the scanned calls");

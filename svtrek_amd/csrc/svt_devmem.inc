@@ -67,13 +67,30 @@ struct DevEvent {
     operator hipEvent_t() const { return e; }
 };
 
+// The segments of one index a scan runs on (call_prepare, svt_call_host.inc): they depend on the extents.
+struct CallSegs {
+    bool ready = false;
+    uint64_t n_seg = 0;
+    DevBuf<uint64_t> d_seg;
+};
+
+// One index in the value buckets' shape, derived from the loaded pileup for svt_call_scan to run on
+// (svt_callindex.inc; callindex_build, svt_callindex_host.inc, is the only code that fills one).
+struct CallIndex {
+    bool built = false;
+    DevBuf<uint4> d_ev;               // array S's events, then array I's
+    DevBuf<uint32_t> d_off;           // [BA_N][bk_n + 1], rows S and I filled
+    uint64_t events[2] = {};          // S / I events
+    CallSegs segs;                    // its own segments
+    // Not built, nothing allocated.  The caller synchronises first where a launch may still read it.
+    void drop() { *this = CallIndex{}; }
+};
+
 // svt_call_scan's scratch (svt_call.inc, svt_call_host.inc): nothing allocated before the first scan
 // of a loaded pileup, gone with the pileup.
 struct CallScratch {
-    bool ready = false;
     bool scanned = false;          // svt_call_scan ran on this pileup (svt_genotype_calls)
-    uint64_t n_seg = 0;
-    DevBuf<uint64_t> d_seg;
+    CallSegs segs;                 // the plain buckets'
     DevBuf<unsigned long long> d_keys, d_tmax, d_tprev;
     DevBuf<uint32_t> d_cid, d_pick;
     DevBuf<uint32_t> d_ctr;        // [0] picked calls, [1] the DEL calls among them, [2..8) events / skipped / big buckets (64 bits each)
@@ -82,64 +99,45 @@ struct CallScratch {
     DevBuf<uint8_t> d_flag;        // per cluster: a call
     DevBuf<svt_call> d_calls, d_raw;   // in (chrom, pos, type) order / as emitted
     uint64_t n_calls = 0;
-    svt_call_stats stats{};
     // the split by length (len_permille > 0): nothing allocated before the first such scan
     DevBuf<uint32_t> d_first, d_cand, d_kend, d_unit;   // per cluster: first key slot / candidates / their keys' ends / units
     DevBuf<uint8_t> d_cflag;       // per cluster: a candidate
     DevBuf<unsigned long long> d_skeys;   // the candidates' sorted keys
     DevBuf<unsigned long long> d_sctr;    // [0..3) split / groups / big, [3] the candidates (32 bits)
     DevBuf<CallAcc> d_gacc, d_uacc;       // per unit: the groups as accumulated / every unit in order
-    svt_call_split_stats split{};
-    // the merged index (merge_gap > 0; svt_callmerge.inc, svt_callmerge_host.inc): nothing allocated
-    // before the first such scan, rebuilt when (gap, min) change, untouched by svt_reindex
-    struct Merged {
-        bool built = false;
+    // The derived indexes: nothing allocated before the first scan that asks for one, untouched by
+    // svt_reindex; `stats` are the build's.
+    // the merged index (merge_gap > 0; svt_callmerge.inc, svt_callmerge_host.inc): rebuilt when (gap, min) change
+    struct Merged : CallIndex {
         uint32_t gap = 0, min_len = 0;    // what it was built for
-        DevBuf<uint4> d_ev;               // the merged items, array S's then array I's
-        DevBuf<uint32_t> d_off;           // [BA_N][bk_n + 1], rows S and I filled
-        uint64_t events[2] = {};          // DEL / INS items
-        bool ready = false;               // its own segments (they depend on the extents)
-        uint64_t n_seg = 0;
-        DevBuf<uint64_t> d_seg;
-        svt_call_merge_stats stats{};     // of the build
+        svt_call_merge_stats stats{};
     } mg;
-    bool last_merged = false;             // the last scan ran on the merged index (svt_genotype_calls, svt_call_consensus)
-    svt_call_merge_stats merge{};         // the last scan's (all zero after merge_gap = 0)
-    // the segment table and the union index (junctions = 1; svt_junction.inc, svt_junction_host.inc):
-    // nothing allocated before svt_load_junctions / the first such scan; the index is rebuilt when the
-    // table or the base view's (merge_gap, merge_min) change, untouched by svt_reindex
-    struct Junction {
+    // the segment table (svt_load_junctions) and the union index (junctions = 1; svt_junction.inc,
+    // svt_junction_host.inc): rebuilt when the table or the base view's (merge_gap, merge_min) change
+    struct Junction : CallIndex {
         bool loaded = false;              // a table for the loaded pileup (n == 0 included)
         uint64_t n = 0, rows = 0;         // its records and segment rows
         DevBuf<uint64_t> d_toff;          // [n + 1]
         DevBuf<svt_junction_seg> d_tseg;  // [rows]
-        bool built = false;
         uint32_t gap = 0, min_len = 0;    // the base view it was built on (gap 0: the plain buckets)
-        DevBuf<uint4> d_ev;               // the union's events, array S's then array I's
-        DevBuf<uint32_t> d_off;           // [BA_N][bk_n + 1], rows S and I filled
-        uint64_t events[2] = {};          // S / I events (the base view's non-items included)
-        bool ready = false;               // its own segments (they depend on the extents)
-        uint64_t n_seg = 0;
-        DevBuf<uint64_t> d_seg;
-        svt_call_junction_stats stats{};  // of the build
+        svt_call_junction_stats stats{};
     } jn;
-    bool last_junction = false;           // the last scan ran on the union index (svt_genotype_calls, svt_call_consensus)
-    svt_call_junction_stats junction{};   // the last scan's (all zero after junctions = 0)
-    // the rearrangement index (rearr != 0; svt_rearr.inc, svt_rearr_host.inc): nothing allocated before the
-    // first such scan; rebuilt when the table changes, untouched by svt_reindex
-    struct Rearr {
-        bool built = false;
-        DevBuf<uint4> d_ev;               // the DUP events (row S), then the INV events (row I)
-        DevBuf<uint32_t> d_off;           // [BA_N][bk_n + 1], rows S and I filled
-        uint64_t events[2] = {};          // DUP / INV items
-        bool ready = false;               // its own segments (they depend on the extents)
-        uint64_t n_seg = 0;
-        DevBuf<uint64_t> d_seg;
+    // the rearrangement index (rearr != 0; svt_rearr.inc, svt_rearr_host.inc): rebuilt when the table changes
+    struct Rearr : CallIndex {
         DevBuf<svt_call> d_a, d_b;        // the scan's two sorted lists before their merge: DEL / INS, INV / DUP
-        svt_call_rearr_stats stats{};     // of the build
+        svt_call_rearr_stats stats{};
     } rr;
-    uint32_t last_rearr = 0;              // the last scan's rearr mask (svt_call_consensus)
-    svt_call_rearr_stats rearr{};         // the last scan's (all zero after rearr = 0)
+    // What the last scan ran on (svt_genotype_calls, svt_call_consensus) and its stats: reset when a scan
+    // begins, the three set once the index the scan runs on is built.
+    struct Last {
+        bool merged = false, junction = false;
+        uint32_t rearr = 0;               // the scan's rearr mask
+        svt_call_stats call_stats{};
+        svt_call_split_stats split_stats{};
+        svt_call_merge_stats merge_stats{};         // (all zero after merge_gap = 0)
+        svt_call_junction_stats junction_stats{};   // (all zero after junctions = 0)
+        svt_call_rearr_stats rearr_stats{};         // (all zero after rearr = 0)
+    } last;
 };
 
 // svt_call_consensus's scratch (svt_callseq.inc, svt_callseq_host.inc): nothing allocated before the

@@ -29,6 +29,9 @@
 //   svt_evidence.inc      read support, depth and value range per refined breakpoint
 //   svt_call.inc          DEL / INS discovery from the value buckets (host side: svt_call_host.inc)
 //   svt_genotype.inc      genotypes of DEL / INS sites (host side: svt_genotype_host.inc)
+//   svt_callindex.inc     what the builds of svt_call_scan's derived indexes share: the filing step, the slot
+//                         counters, the table's next-segment search (host side: svt_callindex_host.inc, the
+//                         one build path of the three indexes below)
 //   svt_callmerge.inc     a read's fragmented D / I ops joined into the merged index of svt_call_scan's
 //                         merge_gap (host side: svt_callmerge_host.inc)
 //   svt_junction.inc      DEL / INS items from split alignments filed beside the base view's events into the
@@ -41,7 +44,7 @@
 //                         (host side: svt_callseq_host.inc)
 //   svt_bam.inc, svt_inflate.inc, svt_bam_host.inc   BGZF inflate and BAM decode: kernels, svt_bam_dec_*
 //   svt_devmem.inc        host only: DevBuf / DevEvent, the owners of every device allocation and event
-//                         the host code makes, and the side modes' scratch records (CallScratch, CallSeqScratch, PoaPool)
+//                         the host code makes, and the side modes' scratch records (CallScratch and its CallIndex, CallSeqScratch, PoaPool)
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -186,6 +189,7 @@ constexpr int LV_WMAX = 1023;   // band half-width for 16-bit offsets and prefix
 #include "svt_index.inc"
 #include "svt_index2.inc"
 #include "svt_bucket_build.inc"
+#include "svt_callindex.inc"
 #include "svt_callmerge.inc"
 #include "svt_junction.inc"
 #include "svt_rearr.inc"
@@ -1392,6 +1396,7 @@ svt_status svt_evidence_batch(svt_ctx *c, const svt_locus *loci, const svt_resul
 }
 
 // ---- include/svtrek_call.h
+#include "svt_callindex_host.inc"
 #include "svt_callmerge_host.inc"
 #include "svt_call_host.inc"
 #include "svt_junction_host.inc"

@@ -81,7 +81,7 @@ svt_status svt_genotype_calls(svt_ctx *c, const svt_gt_params *p, svt_gt *out, u
     DEV_GUARD(c);
     svt_status s;
     if ((s = nomem(c, c->d_gt.reserve(n_out), "svt_genotype_calls: device buffer"))) return s;
-    if ((s = gt_launch(c, p, c->call.d_calls.get(), (size_t)n_out, c->d_gt.get(), nullptr, c->call.last_merged, c->call.last_junction)))
+    if ((s = gt_launch(c, p, c->call.d_calls.get(), (size_t)n_out, c->d_gt.get(), nullptr, c->call.last.merged, c->call.last.junction)))
         return s;
     HIP_TRY(c, hipStreamSynchronize(nullptr));
     HIP_TRY(c, hipMemcpy(out, c->d_gt, n_out * sizeof(svt_gt), hipMemcpyDeviceToHost));

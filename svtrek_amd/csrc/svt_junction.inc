@@ -1,6 +1,6 @@
 // svt_junction.inc -- DEL / INS items from split alignments (include/svtrek_junction.h,
-// svt_call_params.junctions = 1; included by svt_engine.hip after svt_callmerge.inc, the host side is
-// svt_junction_host.inc).
+// svt_call_params.junctions = 1; included by svt_engine.hip after svt_callmerge.inc; BkFile, bk_file,
+// bk_stat_add, jn_less and jn_next are svt_callindex.inc's, the host side is svt_junction_host.inc).
 //
 // The junction items go into a THIRD index in the value buckets' shape: the UNION of the base view's
 // events (the plain buckets' rows S and I, or the merged index's) and the junction events, bucket by
@@ -21,7 +21,6 @@
 // The order of the junction events inside a bucket is whatever the atomics give; nothing downstream
 // reads it.  A junction x lies in its bucket's 1 kb, a contig's last bucket takes everything past the
 // others: the counting sort of a big bucket relies on both.  Integer only, no LDS, no inline assembly.
-constexpr uint32_t JN_SLOTS = 1024;   // the stats are added into JN_SLOTS x JN_NSTAT counters by wave number
 constexpr int JN_NSTAT = 5;           // junctions, DEL items, INS items, other, skipped
 constexpr uint32_t JN_MARK = 0x80000000u, JN_EXT_MAX = 0x7fffffffu;
 static_assert(sizeof(svt_junction_seg) == 24, "include/svtrek_junction.h");
@@ -30,44 +29,17 @@ struct JunctionArgs {
     const uint64_t *off;          // [n + 1] the table's rows per record
     const svt_junction_seg *seg;
     uint64_t n;                   // table records
-    const uint64_t *cbase;        // the main index's
-    const uint32_t *cnb;
-    uint64_t nbk;
     const uint32_t *boff;         // the base view's off[BA_N][nbk + 1]
-    uint32_t *uoff;               // the union's: COUNT the junction counts of rows S and I, else the extents
-    uint32_t *cur;                // [2][nbk + 1] cursors of the filing pass (zeroed)
-    uint4 *ev;                    // the union's events
-    uint32_t n_ev;
-    unsigned long long *stat;     // [JN_SLOTS][JN_NSTAT] (COUNT)
-    uint32_t *err;                // set when a slot falls outside its bucket's extent
+    BkFile f;                     // the union's: off COUNT the junction counts; stat: [BK_SLOTS][JN_NSTAT]
 };
-
-// a < b in the order of the tuple (q_beg, q_end, tid, r_beg, strand)
-__device__ __forceinline__ bool jn_less(const svt_junction_seg &a, const svt_junction_seg &b) {
-    if (a.q_beg != b.q_beg) return a.q_beg < b.q_beg;
-    if (a.q_end != b.q_end) return a.q_end < b.q_end;
-    if (a.tid != b.tid) return a.tid < b.tid;
-    if (a.r_beg != b.r_beg) return a.r_beg < b.r_beg;
-    return a.strand < b.strand;
-}
 
 template <bool COUNT>
 __global__ __launch_bounds__(64 * WPB) void junction_kernel(JunctionArgs a) {
     const uint64_t k = (uint64_t)blockIdx.x * (64 * WPB) + threadIdx.x;
     uint32_t st[JN_NSTAT] = {0u, 0u, 0u, 0u, 0u};
     if (k < a.n) {
-        const uint64_t r0 = a.off[k], r1 = a.off[k + 1];
-        const svt_junction_seg A = a.seg[r0];
-        svt_junction_seg B = A;
-        bool have = false;
-        for (uint64_t r = r0 + 1; r < r1; r++) {   // the smallest tuple strictly greater than A's
-            const svt_junction_seg t = a.seg[r];
-            if (jn_less(A, t) && (!have || jn_less(t, B))) {
-                B = t;
-                have = true;
-            }
-        }
-        if (have) {
+        svt_junction_seg A, B;
+        if (jn_next(a.off, a.seg, k, A, B)) {
             st[0] = 1u;
             int T = -1;   // 0 DEL, 1 INS
             uint32_t x = 0, len = 0, lo = 0, hi = 0;
@@ -91,34 +63,16 @@ __global__ __launch_bounds__(64 * WPB) void junction_kernel(JunctionArgs a) {
             if (T >= 0) {
                 st[1 + T] = 1u;
                 st[4] = x >= IX_SAT ? 1u : 0u;
-                const uint32_t nbt = a.cnb[A.tid];   // (>= 1: the record itself is a read of the contig)
-                const uint64_t row = (uint64_t)(T ? BA_I : BA_S) * (a.nbk + 1), g = a.cbase[A.tid] + min(x >> BKS, nbt - 1u);
-                if (COUNT) {
-                    atomicAdd(&a.uoff[row + g], 1u);
-                } else {
-                    const uint32_t o0 = a.uoff[row + g] + (a.boff[row + g + 1] - a.boff[row + g]), o1 = a.uoff[row + g + 1];
-                    const uint32_t sl = atomicAdd(&a.cur[(uint64_t)T * (a.nbk + 1) + g], 1u);
-                    if (o0 > o1 || sl >= o1 - o0 || o0 + sl >= a.n_ev) *a.err = 1u;
-                    else a.ev[o0 + sl] = make_uint4(x, len << 4 | (T ? OP_INS : OP_DEL), hi, lo | JN_MARK);
-                }
+                const uint32_t nbt = a.f.cnb[A.tid];   // (>= 1: the record itself is a read of the contig)
+                const uint64_t row = (uint64_t)(T ? BA_I : BA_S) * (a.f.nbk + 1), g = a.f.cbase[A.tid] + min(x >> BKS, nbt - 1u);
+                bk_file<COUNT>(a.f, T, g, COUNT ? 0u : a.boff[row + g + 1] - a.boff[row + g],   // (behind the bucket's base events)
+                               make_uint4(x, len << 4 | (T ? OP_INS : OP_DEL), hi, lo | JN_MARK));
             }
         }
     }
     if (COUNT) {
-        const bool any = ballot(st[0] != 0u) != 0ull;   // (wave-uniform)
-        if (any) {
-#pragma unroll
-            for (int d = 32; d > 0; d >>= 1)
-#pragma unroll
-                for (int q = 0; q < JN_NSTAT; q++) st[q] += (uint32_t)__shfl_xor((int)st[q], d, WAVE);
-            if (lane_id() == 0) {
-                const uint64_t wv = (uint64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-                unsigned long long *q = a.stat + (uint64_t)JN_NSTAT * (uint32_t)(wv & (JN_SLOTS - 1u));
-#pragma unroll
-                for (int j = 0; j < JN_NSTAT; j++)
-                    if (st[j]) atomicAdd(&q[j], (unsigned long long)st[j]);
-            }
-        }
+        if (ballot(st[0] != 0u) != 0ull)   // (wave-uniform)
+            bk_stat_add(a.f, st);
     }
 }
 

@@ -5,93 +5,45 @@
 extern "C++" {
 namespace {
 
-constexpr const char *JN_MEM = "svt_call_scan: the junction index";
-
 // The union index of the loaded pileup, its table and the base view (gap == 0: the plain buckets,
 // else the merged index, already built for (gap, min_len)): kept until one of them changes, built here
-// otherwise -- the counting pass, the extents (the base view's added, an exclusive sum per row), the
-// copy of the base events, the filing pass.
+// otherwise by callindex_build -- the base view's extents added to the counts, the base events copied
+// before the junction events are filed behind them.
 svt_status junction_build(svt_ctx *c, uint32_t gap, uint32_t min_len) {
     CallScratch::Junction &j = c->call.jn;
     if (gap == 0u) min_len = 0u;   // (ignored without a gap)
     if (j.built && j.gap == gap && j.min_len == min_len) return SVT_OK;
-    j.built = j.ready = false;
-    j.n_seg = 0;
-    j.events[0] = j.events[1] = 0;
-    j.stats = svt_call_junction_stats{};
+    static const CallIndexText text{"svt_call_scan: the junction index",
+                                    "svt_call_scan: more than 2^31 - 1 events with the junction items are not supported",
+                                    "junction index build", 0x7fffffffull};
     const CallView base = call_view(c, gap != 0u, false);
-    const uint64_t S1 = c->bk_n + 1;
-    svt_status s;
-    DevBuf<uint32_t> d_cur;
-    DevBuf<unsigned long long> d_stat;
-    DevBuf<uint8_t> d_tmp;
-    constexpr size_t NST = (size_t)JN_NSTAT * JN_SLOTS;
-    if ((s = nomem(c, j.d_off.reserve(BA_N * S1), JN_MEM)) || (s = nomem(c, d_cur.reserve(2 * S1), JN_MEM)) ||
-        (s = nomem(c, d_stat.reserve(NST + 1), JN_MEM)))
-        return s;
-    DevEvent e0, e1;
-    HIP_TRY(c, e0.create());
-    HIP_TRY(c, e1.create());
-    HIP_TRY(c, hipEventRecord(e0, nullptr));
-    HIP_TRY(c, hipMemsetAsync(j.d_off, 0, BA_N * S1 * sizeof(uint32_t), nullptr));
-    HIP_TRY(c, hipMemsetAsync(d_cur, 0, 2 * S1 * sizeof(uint32_t), nullptr));
-    HIP_TRY(c, hipMemsetAsync(d_stat, 0, (NST + 1) * sizeof(unsigned long long), nullptr));
     JunctionArgs a{};
     a.off = j.d_toff;
     a.seg = j.d_tseg;
     a.n = j.n;
-    a.cbase = c->d_bkbase;
-    a.cnb = c->d_bknb;
-    a.nbk = c->bk_n;
     a.boff = base.bk.off;
-    a.uoff = j.d_off;
-    a.cur = d_cur;
-    a.stat = d_stat;
-    a.err = reinterpret_cast<uint32_t *>(d_stat + NST);
-    const dim3 jgrid((unsigned)((a.n + 64 * WPB - 1) / (64 * WPB))), jblock(64 * WPB);
-    if (a.n) hipLaunchKernelGGL(junction_kernel<true>, jgrid, jblock, 0, nullptr, a);
-    hipLaunchKernelGGL(junction_extent_kernel, dim3((unsigned)((2 * c->bk_n + 255) / 256)), dim3(256), 0, nullptr, a.boff, a.uoff,
-                       a.nbk);
-    HIP_TRY(c, hipGetLastError());
-    std::vector<unsigned long long> st(NST);
-    HIP_TRY(c, hipMemcpy(st.data(), d_stat, NST * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    uint64_t tot[JN_NSTAT] = {};
-    for (uint32_t i = 0; i < JN_SLOTS; i++)
-        for (int q = 0; q < JN_NSTAT; q++) tot[q] += st[(size_t)JN_NSTAT * i + q];
-    const uint64_t N = base.n_s + base.n_i + tot[1] + tot[2];
-    if (N > 0x7fffffffull) return fail(c, SVT_ESTATE, "%s", "svt_call_scan: more than 2^31 - 1 events with the junction items are not supported");
-    // the extents: row S from 0, row I behind it (the counts' slot nbk is zero: the row's end)
-    uint32_t *offS = j.d_off + (size_t)BA_S * S1, *offI = j.d_off + (size_t)BA_I * S1;
-    size_t tb = 0;
-    HIP_TRY(c, hipcub::DeviceScan::ExclusiveScan(nullptr, tb, offS, offS, hipcub::Sum(), 0u, (int)S1, nullptr));
-    if ((s = nomem(c, d_tmp.reserve(tb), JN_MEM))) return s;
-    size_t t1 = d_tmp.cap();
-    HIP_TRY(c, hipcub::DeviceScan::ExclusiveScan(d_tmp.get(), t1, offS, offS, hipcub::Sum(), 0u, (int)S1, nullptr));
-    uint32_t nS = 0;
-    HIP_TRY(c, hipMemcpy(&nS, offS + c->bk_n, 4, hipMemcpyDeviceToHost));
-    t1 = d_tmp.cap();
-    HIP_TRY(c, hipcub::DeviceScan::ExclusiveScan(d_tmp.get(), t1, offI, offI, hipcub::Sum(), nS, (int)S1, nullptr));
-    const uint32_t nev = (uint32_t)N;
-    if ((uint64_t)nS != base.n_s + tot[1]) return fail(c, SVT_EDEVICE, "%s", "junction index build: the counts disagree");
-    if ((s = nomem(c, j.d_ev.reserve(std::max<uint32_t>(nev, 1u)), JN_MEM))) return s;
-    a.ev = j.d_ev;
-    a.n_ev = nev;
-    if (base.n_s + base.n_i) {
-        const uint64_t waves = 2 * ((c->bk_n + WAVE - 1) / WAVE);
-        hipLaunchKernelGGL(junction_copy_kernel, dim3((unsigned)((waves + WPB - 1) / WPB)), dim3(64 * WPB), 0, nullptr, base.bk.ev,
-                           a.boff, j.d_off.get(), a.nbk, a.ev, nev, a.err);
-    }
-    if (a.n) hipLaunchKernelGGL(junction_kernel<false>, jgrid, jblock, 0, nullptr, a);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(e1, nullptr));
-    HIP_TRY(c, hipEventSynchronize(e1));
-    uint32_t err = 0;
-    HIP_TRY(c, hipMemcpy(&err, a.err, 4, hipMemcpyDeviceToHost));
-    if (err) return fail(c, SVT_EDEVICE, "%s", "junction index build: the filing disagrees with its count");
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, e0, e1));
-    j.events[0] = nS;
-    j.events[1] = nev - nS;
+    const dim3 grid((unsigned)((a.n + 64 * WPB - 1) / (64 * WPB))), block(64 * WPB);
+    uint64_t tot[JN_NSTAT];
+    j.stats = svt_call_junction_stats{};
+    const svt_status s = callindex_build(
+        c, j, text, tot, &j.stats.build_ms,
+        [&](const BkFile &f) {
+            a.f = f;
+            if (a.n) hipLaunchKernelGGL(junction_kernel<true>, grid, block, 0, nullptr, a);
+            hipLaunchKernelGGL(junction_extent_kernel, dim3((unsigned)((2 * f.nbk + 255) / 256)), dim3(256), 0, nullptr, a.boff, f.off,
+                               f.nbk);
+        },
+        [&](const uint64_t *t) { return CallIndexExpect{base.n_s + base.n_i + t[1] + t[2], base.n_s + t[1], base.n_s + t[1]}; },
+        [&](const BkFile &f) {
+            a.f = f;
+            if (base.n_s + base.n_i) {
+                const uint64_t waves = 2 * ((f.nbk + WAVE - 1) / WAVE);
+                hipLaunchKernelGGL(junction_copy_kernel, dim3((unsigned)((waves + WPB - 1) / WPB)), dim3(64 * WPB), 0, nullptr,
+                                   base.bk.ev, a.boff, f.off, f.nbk, f.ev, f.n_ev, f.err);
+            }
+            if (a.n) hipLaunchKernelGGL(junction_kernel<false>, grid, block, 0, nullptr, a);
+        });
+    if (s) return s;
     j.stats.records = j.n;
     j.stats.segments = j.rows;
     j.stats.junctions = tot[0];
@@ -99,10 +51,8 @@ svt_status junction_build(svt_ctx *c, uint32_t gap, uint32_t min_len) {
     j.stats.ins_items = tot[2];
     j.stats.other = tot[3];
     j.stats.skipped = tot[4];
-    j.stats.build_ms = ms;
     j.gap = gap;
     j.min_len = min_len;
-    j.built = true;
     return SVT_OK;
 }
 
@@ -144,21 +94,10 @@ svt_status junction_load_1(svt_ctx *c, const svt_junction_view *v) {
     const uint64_t zero = 0;
     HIP_TRY(c, hipMemcpy(d_toff, n ? v->off : &zero, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
     if (rows) HIP_TRY(c, hipMemcpy(d_tseg, v->seg, (size_t)rows * sizeof(svt_junction_seg), hipMemcpyHostToDevice));
-    if (j.built || j.ready) {   // the index of the table before: gone with it
-        HIP_TRY(c, hipDeviceSynchronize());
-        j.d_ev.reset();
-        j.d_off.reset();
-        j.d_seg.reset();
-    }
-    j.built = j.ready = false;
-    CallScratch::Rearr &rr = c->call.rr;   // the rearrangement index of the table before (svt_rearr_host.inc): likewise
-    if (rr.built || rr.ready) {
-        HIP_TRY(c, hipDeviceSynchronize());
-        rr.d_ev.reset();
-        rr.d_off.reset();
-        rr.d_seg.reset();
-    }
-    rr.built = rr.ready = false;
+    CallScratch::Rearr &rr = c->call.rr;
+    if (j.built || rr.built) HIP_TRY(c, hipDeviceSynchronize());
+    j.drop();    // the union and the rearrangement index of the table before: gone with it
+    rr.drop();
     j.d_toff = std::move(d_toff);
     j.d_tseg = std::move(d_tseg);
     j.n = n;
@@ -180,6 +119,6 @@ svt_status svt_load_junctions(svt_ctx *c, const svt_junction_view *v) {
 
 svt_status svt_call_junction_stats_get(const svt_ctx *c, svt_call_junction_stats *out) {
     if (!c || !out) return SVT_EINVAL;
-    *out = c->call.junction;
+    *out = c->call.last.junction_stats;
     return SVT_OK;
 }

@@ -1,6 +1,6 @@
 // svt_rearr.inc -- DUP / INV items from split alignments (include/svtrek_rearr.h, svt_call_params.rearr;
-// included by svt_engine.hip after svt_junction.inc, whose JunctionArgs-style table walk, jn_less and
-// JN_MARK it shares; the host side is svt_rearr_host.inc).
+// included by svt_engine.hip after svt_junction.inc, whose JN_MARK it shares; BkFile, bk_file, bk_stat_add,
+// jn_less and jn_next are svt_callindex.inc's, the host side is svt_rearr_host.inc).
 //
 // The items go into a FOURTH index in the value buckets' shape, of the rearrangement events alone: row S
 // holds the DUP events, row I the INV events, the off[BA_N][nbk + 1] table with rows S and I filled, an
@@ -25,15 +25,7 @@ struct RearrArgs {
     const uint64_t *off;          // [n + 1] the table's rows per record
     const svt_junction_seg *seg;
     uint64_t n;                   // table records
-    const uint64_t *cbase;        // the main index's
-    const uint32_t *cnb;
-    uint64_t nbk;
-    uint32_t *roff;               // [BA_N][nbk + 1]: COUNT the counts of rows S and I, else the extents
-    uint32_t *cur;                // [2][nbk + 1] cursors of the filing pass (zeroed)
-    uint4 *ev;
-    uint32_t n_ev;
-    unsigned long long *stat;     // [JN_SLOTS][RR_NSTAT] (COUNT)
-    uint32_t *err;                // set when a slot falls outside its bucket's extent
+    BkFile f;                     // stat: [BK_SLOTS][RR_NSTAT]
 };
 
 template <bool COUNT>
@@ -41,18 +33,8 @@ __global__ __launch_bounds__(64 * WPB) void rearr_kernel(RearrArgs a) {
     const uint64_t k = (uint64_t)blockIdx.x * (64 * WPB) + threadIdx.x;
     uint32_t st[RR_NSTAT] = {0u, 0u};
     if (k < a.n) {
-        const uint64_t r0 = a.off[k], r1 = a.off[k + 1];
-        const svt_junction_seg A = a.seg[r0];
-        svt_junction_seg B = A;
-        bool have = false;
-        for (uint64_t r = r0 + 1; r < r1; r++) {   // the smallest tuple strictly greater than A's
-            const svt_junction_seg t = a.seg[r];
-            if (jn_less(A, t) && (!have || jn_less(t, B))) {
-                B = t;
-                have = true;
-            }
-        }
-        if (have && B.tid == A.tid) {
+        svt_junction_seg A, B;
+        if (jn_next(a.off, a.seg, k, A, B) && B.tid == A.tid) {
             int T = -1;   // 0 DUP, 1 INV
             int64_t x64 = 0, len64 = 0;
             uint32_t lo = 0, hi = 0;
@@ -79,34 +61,15 @@ __global__ __launch_bounds__(64 * WPB) void rearr_kernel(RearrArgs a) {
                 lo = min(min(A.r_beg, B.r_beg), JN_EXT_MAX);
                 hi = min(max(A.r_end, B.r_end), JN_EXT_MAX);
                 st[T] = 1u;
-                const uint32_t nbt = a.cnb[A.tid];   // (>= 1: the record itself is a read of the contig)
-                const uint64_t row = (uint64_t)(T ? BA_I : BA_S) * (a.nbk + 1), g = a.cbase[A.tid] + min(x >> BKS, nbt - 1u);
-                if (COUNT) {
-                    atomicAdd(&a.roff[row + g], 1u);
-                } else {
-                    const uint32_t o0 = a.roff[row + g], o1 = a.roff[row + g + 1];
-                    const uint32_t sl = atomicAdd(&a.cur[(uint64_t)T * (a.nbk + 1) + g], 1u);
-                    if (o0 > o1 || sl >= o1 - o0 || o0 + sl >= a.n_ev) *a.err = 1u;
-                    else a.ev[o0 + sl] = make_uint4(x, len << 4 | (T ? OP_INS : OP_DEL), hi, lo | JN_MARK);
-                }
+                const uint32_t nbt = a.f.cnb[A.tid];   // (>= 1: the record itself is a read of the contig)
+                bk_file<COUNT>(a.f, T, a.f.cbase[A.tid] + min(x >> BKS, nbt - 1u), 0u,
+                               make_uint4(x, len << 4 | (T ? OP_INS : OP_DEL), hi, lo | JN_MARK));
             }
         }
     }
     if (COUNT) {
-        const bool any = ballot((st[0] | st[1]) != 0u) != 0ull;   // (wave-uniform)
-        if (any) {
-#pragma unroll
-            for (int d = 32; d > 0; d >>= 1)
-#pragma unroll
-                for (int q = 0; q < RR_NSTAT; q++) st[q] += (uint32_t)__shfl_xor((int)st[q], d, WAVE);
-            if (lane_id() == 0) {
-                const uint64_t wv = (uint64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-                unsigned long long *q = a.stat + (uint64_t)RR_NSTAT * (uint32_t)(wv & (JN_SLOTS - 1u));
-#pragma unroll
-                for (int j = 0; j < RR_NSTAT; j++)
-                    if (st[j]) atomicAdd(&q[j], (unsigned long long)st[j]);
-            }
-        }
+        if (ballot((st[0] | st[1]) != 0u) != 0ull)   // (wave-uniform)
+            bk_stat_add(a.f, st);
     }
 }
 

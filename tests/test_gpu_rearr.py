@@ -292,6 +292,55 @@ def test_plain_scan_after_cached_build_new_table_and_reindex(eng):
     same(check(eng, pl, table, min_support=1, load=False)[0], full)
 
 
+def lifecycle_world():
+    """Twelve reads on two contigs, two of each: a 300D, a `180D 5M 120D` (one item for merge_gap >= 5), a
+    `100D 55M 100D` (one item for merge_gap >= 55 only), a deletion junction, a DUP and an INV -- and a second table
+    for the same pileup whose DUP starts 1100 earlier, in another bucket, and which has no INV record."""
+    cig = [(0, 1000, [(M, 1000), (D, 300), (M, 700)]), (0, 5000, [(M, 1000), (D, 180), (M, 5), (D, 120), (M, 500)]),
+           (0, 9000, [(M, 1000), (D, 100), (M, 55), (D, 100), (M, 500)])]
+    jdel = ((1, 1000, [(M, 1000), (S, 500)]), (1, 2300 + 1, "+", [(S, 1000), (M, 500)]), 0)
+    d, v = dup(20000, 400), inv(30000, 600, 0, tid=1)
+    moved = (d[0], (0, 18900 + 1, "+", d[1][3]), 0)
+    pl, table = build([plain(r) for r in cig] * 2 + [jdel, d, v] * 2, n_targets=2)
+    pl2, table2 = build([plain(r) for r in cig] * 2 + [jdel, moved, plain(v[0])] * 2, n_targets=2)
+    assert np.array_equal(pl.pos, pl2.pos) and len(table[0]) == 6 and len(table2[0]) == 4
+    return pl, table, table2
+
+
+def lifecycle_steps(table, table2):
+    """check()'s arguments of the seven scans of the ten steps: 1 .. 5 on the first table, 7 and 9 on the second."""
+    return [dict(table=table), dict(table=table, rearr=(), junctions=True, G=50), dict(table=table, rearr=(), G=60),
+            dict(table=table, rearr=(), junctions=True, G=50), dict(table=table, rearr=(), junctions=True),
+            dict(table=table2, junctions=True), dict(table=table2, rearr=())]
+
+
+def lifecycle_want(pl, steps):
+    """The models' calls of every scan, as rec() tuples (tests/test_rearr_model.py checks on the CPU that every scan
+    calls something and that the scans a stale index would confuse differ)."""
+    return [[rec(c) for c in R.call(pl, s["table"], 10, 2, (SVT_DEL, SVT_INS), tuple(NAMES[t] for t in s.get("rearr", ("DUP", "INV"))),
+                                   0, s.get("G", 0), 20, s.get("junctions", False))[0]] for s in steps]
+
+
+def test_which_index_is_rebuilt_reused_or_dropped_when(eng):
+    """One engine, one pileup, ten steps: every scan against the model, so that an index kept when its key changed, or
+    dropped segments kept when the extents changed, shows as another scan's calls."""
+    pl, table, table2 = lifecycle_world()
+    kw = dict(min_support=2, load=False)
+    steps = lifecycle_steps(table, table2)
+    want = lifecycle_want(pl, steps)
+    eng.load_pileup(pl)
+    eng.load_junctions(*table)
+    for s in steps[:5]:                                    # 1 .. 5
+        check(eng, pl, **s, **kw)
+    eng.load_junctions(*table2)                            # 6: drops the union and the rearrangement index
+    got, _, rs = check(eng, pl, **steps[5], **kw)          # 7
+    assert [rec(c) for c in got] == want[5] and rs["inv_items"] == 0
+    eng.reindex()                                          # 8
+    got, _, _ = check(eng, pl, **steps[6], **kw)           # 9: a plain scan
+    same(got, call_ref.call(pl, min_support=2)[0])
+    assert np.array_equal(eng.genotype_calls(), R.genotype(pl, table2, got))   # 10
+
+
 # ---- genotypes and status codes ------------------------------------------------------------------------
 def test_genotype_calls(eng):
     pl, table = combined()

@@ -216,3 +216,16 @@ def test_order_and_len_permille():
         [(SVT_INS, 80, 3), (SVT_DEL, 300, 3), (SVT_INV, 600, 3), (SVT_DUP, 400, 3), (SVT_DUP, 900, 3)]
     assert sp == {"candidates": 1, "split": 1, "groups": 2, "big": 0} and rst["clusters"] == 2 and rst["calls"] == 3
     assert st["events"] == 6 + 9 and st["clusters"] == 4 and st["calls"] == 5
+
+
+def test_the_lifecycle_world_tells_its_scans_apart():
+    """tests/test_gpu_rearr.py's ten-step test compares every scan of one engine with the model; a stale index shows
+    there only if the models' own calls differ between the scans it could be taken from.  Models alone, no GPU."""
+    import test_gpu_rearr as G
+    pl, table, table2 = G.lifecycle_world()
+    want = G.lifecycle_want(pl, G.lifecycle_steps(table, table2))
+    assert len(want) == 7 and all(want)                                     # every scan calls something
+    assert want[1] != want[2] and want[1] != want[4] and want[2] != want[4]  # steps 2, 3 and 5
+    assert want[3] == want[1] and want[0] != want[5] and want[4] != want[6]
+    assert (SVT_DUP, 18900, 20400, 1500, 2) in want[5] and (SVT_DUP, 20000, 20400, 400, 2) in want[0]
+    assert any(w[0] == SVT_INV for w in want[0]) and not any(w[0] == SVT_INV for w in want[5])
