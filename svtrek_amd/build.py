@@ -41,9 +41,10 @@ def _stale(out: str, deps: list[str]) -> bool:
 
 def _engine_deps() -> list[str]:
     """The engine's one translation unit first, then everything it includes: every csrc/*.inc,
-    svt_bamrec.h and the public headers."""
+    svt_bamrec.h, svt_loadprep.h and the public headers."""
     incs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".inc"))
-    return [os.path.join(CSRC, "svt_engine.hip")] + incs + [os.path.join(CSRC, "svt_bamrec.h")] + PUBLIC_HDRS
+    hdrs = [os.path.join(CSRC, f) for f in ("svt_bamrec.h", "svt_loadprep.h")]
+    return [os.path.join(CSRC, "svt_engine.hip")] + incs + hdrs + PUBLIC_HDRS
 
 
 def build_engine(force: bool = False) -> str:

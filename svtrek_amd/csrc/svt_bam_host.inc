@@ -238,21 +238,11 @@ svt_status svt_bam_dec_stats_get(const svt_bam_dec *d, svt_bam_dec_stats *out) {
     return SVT_OK;
 }
 
-svt_status svt_bam_dec_load(svt_bam_dec *d) {
-    if (!d) return SVT_EINVAL;
+namespace {
+// svt_bam_dec_load's body inside load_frame (t0: the frame's start): the decoded columns to the host,
+// then the host pass and the rest of the load by load_core.
+svt_status bd_load(svt_bam_dec *d, LoadClock::time_point t0) {
     svt_ctx *c = d->c;
-    DEV_GUARD(c);
-    using clk = std::chrono::steady_clock;
-    if (d->pend) {   // the last batch's records
-        const clk::time_point tf = clk::now();
-        const svt_status sd = bd_decode(d);
-        d->stats.feed_ms += std::chrono::duration<double, std::milli>(clk::now() - tf).count();
-        if (sd) return sd;
-    }
-    if (d->tail) return fail(c, SVT_EINVAL, "%s", "truncated BAM record at end of file");
-    const clk::time_point t0 = clk::now();
-    free_pileup(c);
-    c->load_stats = svt_load_stats{};
     const int32_t nt = d->n_ref;
     const uint64_t n = d->nkept;
     svt_status s;
@@ -285,7 +275,7 @@ svt_status svt_bam_dec_load(svt_bam_dec *d) {
         if (uns) HIP_TRY(c, hipMemcpy(tid.data(), d->d_tid, n * 4, hipMemcpyDeviceToHost));
     }
     soff[n] = d->nwords;
-    const double pre = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    const double pre = ms_since(t0);
     if (uns) {   // not coordinate-sorted: sort on the host (stable, by tid then pos), as the host ingest does
         std::vector<uint32_t> strm(d->nwords);
         if (d->nwords) HIP_TRY(c, hipMemcpy(strm.data(), d->d_stream, d->nwords * 4, hipMemcpyDeviceToHost));
@@ -308,18 +298,31 @@ svt_status svt_bam_dec_load(svt_bam_dec *d) {
         }
         o2[n] = s2.size();
         for (int32_t t = 0; t < nt; t++) toff[(size_t)t + 1] += toff[(size_t)t];
-        s = load_core(c, nt, toff.data(), p2.data(), e2.data(), n2.data(), o2.data(), s2.data(), nullptr,
-                      d->stats.cigar_ops, pre);
-    } else {
-        // the stream stays where the decode wrote it (its spare words zeroed): the context adopts it;
-        // a BAM without records never allocated one, so it gets just the spare words here
-        if ((s = bd_mem(c, d->d_stream.grow(d->nwords + STREAM_PAD, d->nwords)))) return s;
-        HIP_TRY(c, hipMemset(d->d_stream + d->nwords, 0, STREAM_PAD * 4));
-        s = load_core(c, nt, toff.data(), pos.data(), endpos.data(), nc.data(), soff.data(), nullptr, &d->d_stream,
-                      d->stats.cigar_ops, pre);
+        return load_core(c, loadprep::Reads{nt, toff.data(), p2.data(), e2.data(), n2.data(), o2.data()}, s2.data(), nullptr,
+                         d->stats.cigar_ops, pre);
     }
-    c->load_stats.total_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-    return s;
+    // the stream stays where the decode wrote it (its spare words zeroed): the context adopts it;
+    // a BAM without records never allocated one, so it gets just the spare words here
+    if ((s = bd_mem(c, d->d_stream.grow(d->nwords + STREAM_PAD, d->nwords)))) return s;
+    HIP_TRY(c, hipMemset(d->d_stream + d->nwords, 0, STREAM_PAD * 4));
+    return load_core(c, loadprep::Reads{nt, toff.data(), pos.data(), endpos.data(), nc.data(), soff.data()}, nullptr,
+                     &d->d_stream, d->stats.cigar_ops, pre);
+}
+}  // namespace
+
+svt_status svt_bam_dec_load(svt_bam_dec *d) {
+    if (!d) return SVT_EINVAL;
+    svt_ctx *c = d->c;
+    DEV_GUARD(c);
+    using clk = std::chrono::steady_clock;
+    if (d->pend) {   // the last batch's records
+        const clk::time_point tf = clk::now();
+        const svt_status sd = bd_decode(d);
+        d->stats.feed_ms += std::chrono::duration<double, std::milli>(clk::now() - tf).count();
+        if (sd) return sd;
+    }
+    if (d->tail) return fail(c, SVT_EINVAL, "%s", "truncated BAM record at end of file");
+    return load_frame(c, [&](LoadClock::time_point t0) { return bd_load(d, t0); });
 }
 
 void svt_bam_dec_close(svt_bam_dec *d) {

@@ -16,7 +16,7 @@ struct CallView {
     CallSegs *segs;
 };
 CallView plain_view(svt_ctx *c) {
-    return CallView{make_args(c, nullptr, nullptr, 0, false).bk, c->bk_events[BA_S], c->bk_events[BA_I], &c->call.segs};
+    return CallView{c->bk.view(), c->bk.events[BA_S], c->bk.events[BA_I], &c->call.segs};
 }
 CallView index_view(svt_ctx *c, CallIndex &ix) {
     CallView v{plain_view(c).bk, ix.events[0], ix.events[1], &ix.segs};
@@ -38,7 +38,7 @@ svt_status rearr_build(svt_ctx *c);                                      // svt_
 svt_status call_prepare(svt_ctx *c, const CallView &v) {
     CallScratch &k = c->call;
     if (v.segs->ready) return SVT_OK;
-    const uint64_t nb2 = 2 * c->bk_n, N = v.n_s + v.n_i;
+    const uint64_t nb2 = 2 * c->bk.n, N = v.n_s + v.n_i;
     svt_status s;
     DevBuf<uint8_t> d_flag;
     DevBuf<uint64_t> &d_seg = v.segs->d_seg;
@@ -353,10 +353,10 @@ svt_status svt_call_scan(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls
         return fail(c, SVT_ESTATE, "%s", "svt_call_scan: junctions = 1 without svt_load_junctions for the loaded pileup");
     if (p->rearr && !c->call.jn.loaded)
         return fail(c, SVT_ESTATE, "%s", "svt_call_scan: rearr != 0 without svt_load_junctions for the loaded pileup");
-    if (c->n_reads != 0 && !c->bk_ready)
+    if (c->n_reads != 0 && !c->bk.ready)
         return fail(c, SVT_ESTATE, "%s",
                     "svt_call_scan needs the value buckets (not built: SVTREK_INDEX=lists, or a pileup past 2^32 events)");
-    if (c->bk_nev >= 0x7fffffffu || 2 * c->bk_n >= 0x7fffffffull)   // (the scans' and the sort network's 32-bit counts)
+    if (c->bk.nev >= 0x7fffffffu || 2 * c->bk.n >= 0x7fffffffull)   // (the scans' and the sort network's 32-bit counts)
         return fail(c, SVT_ESTATE, "%s", "svt_call_scan: 2^31 events or buckets and more are not supported");
     DEV_GUARD(c);
     return call_scan_1(c, p, n_calls);

@@ -25,7 +25,7 @@ template <int NSTAT, class Count, class Expect, class File>
 svt_status callindex_build(svt_ctx *c, CallIndex &ix, const CallIndexText &t, uint64_t (&tot)[NSTAT], double *build_ms, Count count,
                            Expect expect, File file) {
     ix.drop();
-    const uint64_t S1 = c->bk_n + 1;
+    const uint64_t S1 = c->bk.n + 1;
     constexpr size_t NST = (size_t)NSTAT * BK_SLOTS;
     svt_status s;
     DevBuf<uint32_t> d_cur;
@@ -41,7 +41,7 @@ svt_status callindex_build(svt_ctx *c, CallIndex &ix, const CallIndexText &t, ui
     HIP_TRY(c, hipMemsetAsync(ix.d_off, 0, BA_N * S1 * sizeof(uint32_t), nullptr));
     HIP_TRY(c, hipMemsetAsync(d_cur, 0, 2 * S1 * sizeof(uint32_t), nullptr));
     HIP_TRY(c, hipMemsetAsync(d_stat, 0, (NST + 1) * sizeof(unsigned long long), nullptr));
-    BkFile f{c->d_bkbase, c->d_bknb, c->bk_n, ix.d_off, d_cur, nullptr, 0u, d_stat, reinterpret_cast<uint32_t *>(d_stat + NST)};
+    BkFile f{c->bk.d_base, c->bk.d_nb, c->bk.n, ix.d_off, d_cur, nullptr, 0u, d_stat, reinterpret_cast<uint32_t *>(d_stat + NST)};
     count(f);
     HIP_TRY(c, hipGetLastError());
     std::vector<unsigned long long> st(NST);
@@ -59,7 +59,7 @@ svt_status callindex_build(svt_ctx *c, CallIndex &ix, const CallIndexText &t, ui
     size_t t1 = d_tmp.cap();
     HIP_TRY(c, hipcub::DeviceScan::ExclusiveScan(d_tmp.get(), t1, offS, offS, hipcub::Sum(), 0u, (int)S1, nullptr));
     uint32_t nS = 0;
-    HIP_TRY(c, hipMemcpy(&nS, offS + c->bk_n, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(&nS, offS + c->bk.n, 4, hipMemcpyDeviceToHost));
     t1 = d_tmp.cap();
     HIP_TRY(c, hipcub::DeviceScan::ExclusiveScan(d_tmp.get(), t1, offI, offI, hipcub::Sum(), nS, (int)S1, nullptr));
     const uint32_t nev = (uint32_t)x.n;

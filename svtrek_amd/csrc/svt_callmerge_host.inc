@@ -13,9 +13,9 @@ svt_status callmerge_build(svt_ctx *c, uint32_t gap, uint32_t min_len) {
     static const CallIndexText text{"svt_call_scan: the merged index", "svt_call_scan: 2^31 merged events and more are not supported",
                                     "merged index build", 0x7ffffffeull};
     CallMergeArgs a{};
-    a.stream = c->d_cigar;
-    a.soff = c->d_off64;
-    a.rec = c->d_rec;
+    a.stream = c->reads.d_cigar;
+    a.soff = c->reads.d_off64;
+    a.rec = c->reads.d_rec;
     a.n_reads = (uint64_t)c->n_reads;
     a.gap = gap;
     a.min_len = min_len;

@@ -21,7 +21,7 @@ svt_status callseq_prepare(svt_ctx *c) {
     HIP_TRY(c, hipEventRecord(e0, nullptr));
     if (c->n_ins && c->n_reads) {
         CsTabArgs t{};
-        t.pile = make_args(c, nullptr, nullptr, 0, false).pile;
+        t.pile = pile_view(c);
         t.n_reads = (uint64_t)c->n_reads;
         t.n_ins = c->n_ins;
         t.tab = k.d_tab;
@@ -87,7 +87,7 @@ svt_status callseq_run(svt_ctx *c, const svt_poa_params *p, uint64_t first, size
     a.pp = PoaParams{p->match, p->mismatch, p->gap_open, p->gap_ext, p->band_b, p->band_f_permille,
                      p->max_seqs, p->max_len, p->max_nodes, p->support_radius, p->max_support};
     a.n = (uint32_t)n;
-    a.ins_base = c->d_spoffI;
+    a.ins_base = c->ix.d_spoffI;
     a.ins_off = c->d_ins_off;
     a.ins_bases = c->d_ins_bases;
     a.cap = cap;

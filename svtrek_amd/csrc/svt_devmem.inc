@@ -67,6 +67,65 @@ struct DevEvent {
     operator hipEvent_t() const { return e; }
 };
 
+// What a loaded pileup keeps on the device, by owner (svt_load_host.inc fills all three).  Each owner
+// has one function that gives the kernels' read-only view of it; the builds' argument structs
+// (ix_args, bk_args) take the same view and, for what they write, the owner's buffers.
+
+// The read columns, as uploaded from the host pass (svt_loadprep.h); nothing rebuilds them.
+struct ReadCols {
+    DevBuf<int32_t> d_pos, d_emax;
+    DevBuf<uint4> d_rec;
+    DevBuf<uint8_t> d_clip8;          // per read its clip bits (rec.z >> 30) alone: the census's 1 B instead of 16
+    DevBuf<uint64_t> d_off64;         // stream offsets [n_reads + 1]
+    DevBuf<int64_t> d_tid_off, d_bkt_off;
+    DevBuf<uint2> d_bkt;
+    DevBuf<uint32_t> d_cigar;         // CIGAR stream
+    void view(DevPileup &v) const {
+        v.pos = d_pos, v.emax = d_emax, v.rec = d_rec, v.off64 = d_off64;
+        v.tid_off = d_tid_off, v.bkt_off = d_bkt_off, v.bkt = d_bkt, v.cigar = d_cigar;
+    }
+};
+
+// The span-list index (svt_index.inc, svt_index2.inc): the lists, and the ranges, totals and scratch
+// of their build.
+struct SpanIndex {
+    DevBuf<uint64_t> d_part;          // [n_ranges + 1]
+    uint32_t n_ranges = 0;
+    DevBuf<IxTot> d_agg;              // range (group) totals
+    DevBuf<IxTot> d_bsum, d_bpre;     // their sums per block of IX_BLK, the blocks' exclusive scan
+    size_t n_bsum = 0;
+    bool bsum_dirty = false;          // a build stopped between its walk (which adds into d_bsum) and the
+                                      // scan (which zeroes it again): the next build clears it first
+    DevBuf<uint4> d_scr;              // stream walk: staged events / offsets per range, overflow flags
+    DevBuf<uint2> d_scrh;
+    DevBuf<uint32_t> d_ovf;
+    DevBuf<uint2> d_cnt;              // [n_reads] lane-per-read census -> emit (svt_index2.inc)
+    uint32_t n_groups = 0;            // 64-read groups of the lane-per-read index
+    DevBuf<uint64_t> d_tot;
+    uint64_t n_evD = 0, n_evI = 0;
+    DevBuf<uint64_t> d_spoffD, d_spoffI;   // span walk
+    DevBuf<uint4> d_spD, d_spI;
+    void view(DevPileup &v) const { v.spoffD = d_spoffD, v.spoffI = d_spoffI, v.spD = d_spD, v.spI = d_spI; }
+};
+
+// The value-bucketed event index (svt_bucket.inc, svt_bucket_build.inc).
+struct ValueBuckets {
+    bool ready = false;               // built for the loaded pileup
+    uint64_t n = 0;                   // buckets per array (every contig's)
+    DevBuf<uint32_t> d_off;           // [BA_N][n + 1] extents (indices into d_ev)
+    DevBuf<uint32_t> d_cur;           // [BA_N][n + 1] cursors of direct builds (k * count before build k)
+    DevBuf<uint32_t> d_cap;           // [BA_N][n + 1] cursors of captured builds (zeroed by the graph)
+    DevBuf<int32_t> d_pm;             // [3][n + 1] prefix max of the BELOW keys
+    DevBuf<uint4> d_ev;               // every array's events
+    uint64_t events[BA_N] = {};
+    DevBuf<uint64_t> d_base;          // [n_targets] first bucket of contig t
+    DevBuf<uint32_t> d_nb;            // [n_targets] its buckets
+    DevBuf<uint32_t> d_maxd;          // [n_targets] its longest D > 50 op
+    uint32_t builds = 0;              // filing passes so far (the cursors' epoch)
+    uint32_t nev = 0;                 // d_ev's events (every array's)
+    BkIndex view() const { return BkIndex{d_ev, d_off, d_pm, d_base, d_nb, d_maxd, n, ready ? 1 : 0}; }
+};
+
 // The segments of one index a scan runs on (call_prepare, svt_call_host.inc): they depend on the extents.
 struct CallSegs {
     bool ready = false;

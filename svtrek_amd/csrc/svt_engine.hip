@@ -44,10 +44,16 @@
 //                         (host side: svt_callseq_host.inc)
 //   svt_bam.inc, svt_inflate.inc, svt_bam_host.inc   BGZF inflate and BAM decode: kernels, svt_bam_dec_*
 //   svt_devmem.inc        host only: DevBuf / DevEvent, the owners of every device allocation and event
-//                         the host code makes, and the side modes' scratch records (CallScratch and its CallIndex, CallSeqScratch, PoaPool)
+//                         the host code makes, the pileup's three owners (ReadCols, SpanIndex, ValueBuckets) and
+//                         the side modes' scratch records (CallScratch and its CallIndex, CallSeqScratch, PoaPool)
+//   svt_loadprep.h        host only, no HIP: the load's host pass (validation, prefix-max endpos, records, read
+//                         buckets, index ranges, groups) and svt_load_pileup's preamble
+//   svt_load_host.inc     host only: the pileup load (svt_load_pileup, load_core for the BAM decoder), the
+//                         span-list and value-bucket builds, svt_reindex, svt_last_load_stats
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -70,6 +76,7 @@
 #include "../../include/svtrek_junction.h"
 #include "../../include/svtrek_rearr.h"
 #include "svt_bamrec.h"
+#include "svt_loadprep.h"
 
 #define SVT_VERSION "svtrek_amd 0.33.0 (gfx950, value-bucketed event index filed by a lane-per-read walk with a 9-B LDS stage, band + prefix-max facts, packed span walk fed by readlane, lane vote on 64 windows a wave, BGZF inflate + BAM decode, DEL/INS discovery from the value buckets, genotypes from the events' own read extents, consensus sequence of INS calls, a read's fragmented D / I ops joined before calling, DEL/INS items and DUP/INV calls from split alignments)"
 
@@ -171,9 +178,20 @@ struct KArgs {
 constexpr int W_WINDOWS = 0, W_READS = 1, W_OPS = 2, W_CANDS = 3, W_SPILLED = 4, W_QUERIES = 5, W_PROBE = 6,
               W_RANGE = 7, W_LREADS = 8, W_LENTRIES = 9, W_STOPS = 10, W_STOPCH = 11, W_SQUERIES = 12,
               W_SPAN = 13, W_BQ = 14, W_BEV = 15, W_N = 16;
-constexpr size_t CTL_BYTES = 256;   // context control words: pool head, status, work counters
-constexpr size_t CTL_REDO = 200;    // redo counters: two alternating (direct launches), one + scratch (captured)
-static_assert(16 + 8 * W_N <= CTL_REDO && CTL_REDO + 16 <= CTL_BYTES, "control block too small");
+// The context's control block (svt_ctx::d_ctl, CTL_BYTES of device memory) as the host addresses it: ctl(c)
+// points at it, and the kernels get pointers to its words.
+constexpr size_t CTL_BYTES = 256;
+struct Ctl {
+    unsigned long long pool_head;     // epoch << 40 | words handed out in that launch
+    int32_t status;                   // the launches' sticky status (bit0: spill pool exhausted)
+    uint32_t ix_status;               // the index builds' sticky status (take_ix_status)
+    unsigned long long work[W_N];     // svt_work counters of a counting launch
+    unsigned char unused[200 - 16 - 8 * W_N];
+    uint32_t redo[4];                 // left-over counters: two alternating (direct launches), one + scratch (captured)
+};
+static_assert(offsetof(Ctl, pool_head) == 0 && offsetof(Ctl, status) == 8 && offsetof(Ctl, ix_status) == 12 &&
+              offsetof(Ctl, work) == 16 && offsetof(Ctl, redo) == 200 && sizeof(Ctl) <= CTL_BYTES,
+              "the control block's layout");
 
 constexpr int LV_WMAX = 1023;   // band half-width for 16-bit offsets and prefix sums (32 * 2046 < 2^16)
 
@@ -206,49 +224,14 @@ struct Pileup {
     int32_t n_targets = 0;
     int64_t n_reads = 0;
     uint64_t n_ops = 0;
-    DevBuf<int32_t> d_pos, d_emax;
-    DevBuf<uint4> d_rec;
-    DevBuf<uint8_t> d_clip8;          // per read its clip bits (rec.z >> 30) alone: the census's 1 B instead of 16
-    DevBuf<uint64_t> d_off64;         // stream offsets [n_reads + 1]
-    DevBuf<int64_t> d_tid_off, d_bkt_off;
-    DevBuf<uint2> d_bkt;
-    DevBuf<uint32_t> d_cigar;         // CIGAR stream
-    uint64_t n_ins = 0;               // I >= 50 ops in the pileup (= I-list events; d_spoffI indexes them per read)
-    // device index (svt_index.inc)
-    DevBuf<uint64_t> d_part;          // [n_ranges + 1]
-    uint32_t n_ranges = 0;
-    DevBuf<IxTot> d_agg;              // range (group) totals
-    DevBuf<IxTot> d_bsum, d_bpre;     // their sums per block of IX_BLK, the blocks' exclusive scan
-    size_t n_bsum = 0;
-    bool bsum_dirty = false;          // a build stopped between its walk (which adds into d_bsum) and the
-                                      // scan (which zeroes it again): the next build clears it first
-    DevBuf<uint4> d_scr;              // stream walk: staged events / offsets per range, overflow flags
-    DevBuf<uint2> d_scrh;
-    DevBuf<uint32_t> d_ovf;
-    DevBuf<uint2> d_cnt;              // [n_reads] lane-per-read census -> emit (svt_index2.inc)
-    uint32_t n_groups = 0;            // 64-read groups of the lane-per-read index
-    DevBuf<uint64_t> d_tot;
-    uint64_t n_evD = 0, n_evI = 0;
-    DevBuf<uint64_t> d_spoffD, d_spoffI;   // span walk
-    DevBuf<uint4> d_spD, d_spI;
+    uint64_t n_ins = 0;               // I >= 50 ops in the pileup (= I-list events; ix.d_spoffI indexes them per read)
+    ReadCols reads;                   // the read columns
+    SpanIndex ix;                     // the span-list index
+    ValueBuckets bk;                  // the value-bucketed event index
     // allele-consensus mode: the inserted sequences (svt_load_insseq)
     DevBuf<uint64_t> d_ins_off;
     DevBuf<uint8_t> d_ins_bases;
     bool insseq_loaded = false;
-    // the value-bucketed event index (svt_bucket.inc, svt_bucket_build.inc)
-    bool bk_ready = false;            // built for the loaded pileup
-    uint64_t bk_n = 0;                // buckets per array (every contig's)
-    DevBuf<uint32_t> d_bkoff;         // [BA_N][bk_n + 1] extents (indices into d_bkev)
-    DevBuf<uint32_t> d_bkcur;         // [BA_N][bk_n + 1] cursors of direct builds (k * count before build k)
-    DevBuf<uint32_t> d_bkcap;         // [BA_N][bk_n + 1] cursors of captured builds (zeroed by the graph)
-    DevBuf<int32_t> d_bkpm;           // [3][bk_n + 1] prefix max of the BELOW keys
-    DevBuf<uint4> d_bkev;             // every array's events
-    uint64_t bk_events[BA_N] = {};
-    DevBuf<uint64_t> d_bkbase;        // [n_targets] first bucket of contig t
-    DevBuf<uint32_t> d_bknb;          // [n_targets] its buckets
-    DevBuf<uint32_t> d_bkmaxd;        // [n_targets] its longest D > 50 op
-    uint32_t bk_builds = 0;           // filing passes so far (the cursors' epoch)
-    uint32_t bk_nev = 0;              // d_bkev's events (every array's)
     CallScratch call;                 // svt_call_scan
     CallSeqScratch callseq;           // svt_call_consensus
     uint64_t dev_bytes = 0;
@@ -284,8 +267,7 @@ struct svt_ctx : Pileup {
     DevBuf<svt_gt> d_gt;          // svt_genotype_batch's / svt_genotype_calls' records
     // spill pool (d_pool.cap() words) + status + work counters
     DevBuf<int32_t> d_pool;
-    DevBuf<unsigned char> d_ctl;  // [0,8) pool head (epoch-tagged), [8,12) sticky status, [12,16) index
-                                  // build guard, [16,16+8*W_N) work, [CTL_REDO, +16) left-over counters
+    DevBuf<unsigned char> d_ctl;  // the control block (Ctl)
     uint32_t epoch = 0;           // launches so far (pool epochs cycle through 1 .. 2^24-1)
     // launches run in submission order across streams (order_on)
     hipStream_t last_stream = nullptr;
@@ -314,6 +296,22 @@ svt_status fail(svt_ctx *c, svt_status code, const char *fmt, const char *detail
         hipError_t e_ = (expr);                                                          \
         if (e_ != hipSuccess) return fail((ctx), SVT_EDEVICE, #expr ": %s", hipGetErrorString(e_)); \
     } while (0)
+
+Ctl *ctl(const svt_ctx *c) { return reinterpret_cast<Ctl *>(c->d_ctl.get()); }
+
+// The index builds' sticky status word (and, with `launch`, the launches' beside it, in the same copy), read
+// after the caller's synchronise and cleared when set: every build guard is reported once.  The
+// codes: 1 emit overran the census's sizes / a count disagreed, 2 a look-back never ended, 3 an
+// event outside its value bucket's extent; the caller words its own message.
+svt_status take_ix_status(svt_ctx *c, uint32_t *code, int32_t *launch = nullptr) {
+    static_assert(offsetof(Ctl, ix_status) == offsetof(Ctl, status) + 4, "one copy reads both status words");
+    int32_t w[2] = {0, 0};
+    HIP_TRY(c, hipMemcpy(w, &ctl(c)->status, sizeof w, hipMemcpyDeviceToHost));
+    if (w[1]) HIP_TRY(c, hipMemset(&ctl(c)->ix_status, 0, 4));
+    *code = (uint32_t)w[1];
+    if (launch) *launch = w[0];
+    return SVT_OK;
+}
 
 // A failed device allocation as the site's status: SVT_ENOMEM with its message.
 svt_status nomem(svt_ctx *c, hipError_t e, const char *what) {
@@ -357,7 +355,7 @@ svt_status order_on(svt_ctx *c, hipStream_t st) {
 svt_status grow_pool(svt_ctx *c) {
     unsigned long long head = 0;
     HIP_TRY(c, hipDeviceSynchronize());
-    HIP_TRY(c, hipMemcpy(&head, c->d_ctl, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(&head, &ctl(c)->pool_head, 8, hipMemcpyDeviceToHost));
     const uint64_t need = (uint32_t)(head >> 40) == c->epoch ? (head & ((1ull << 40) - 1ull)) : 0ull;
     const uint64_t words = std::max<uint64_t>(need + need / 8 + 1024, 2 * c->d_pool.cap());
     return nomem(c, c->d_pool.reserve(words), "growing the candidate spill pool failed");
@@ -365,10 +363,18 @@ svt_status grow_pool(svt_ctx *c) {
 
 void free_pileup(svt_ctx *c) { static_cast<Pileup &>(*c) = Pileup{}; }
 
+// The loaded pileup as the kernels read it: the read columns and the span lists.
+DevPileup pile_view(const svt_ctx *c) {
+    DevPileup v;
+    c->reads.view(v);
+    c->ix.view(v);
+    v.n_targets = c->n_targets;
+    return v;
+}
+
 KArgs make_args(svt_ctx *c, const svt_locus *d_loci, svt_result *d_out, uint32_t n, bool count) {
     KArgs a;
-    a.pile = DevPileup{c->d_pos, c->d_emax, c->d_rec, c->d_off64, c->d_tid_off, c->d_bkt_off, c->d_bkt,
-                       c->d_cigar, c->d_spoffD, c->d_spoffI, c->d_spD, c->d_spI, c->n_targets};
+    a.pile = pile_view(c);
     const svt_params &q = c->prm;
     // KParams::sent_ok: narrow + 2 >= max(range + max(ci, 0), 26) (64-bit: any int32 parameters)
     const int64_t width = std::max<int64_t>((int64_t)q.consensus_interval_range + std::max<int64_t>(q.consensus_interval, 0),
@@ -379,11 +385,11 @@ KArgs make_args(svt_ctx *c, const svt_locus *d_loci, svt_result *d_out, uint32_t
     a.out = d_out;
     a.n = n;
     a.pool = c->d_pool;
-    a.pool_head = (unsigned long long *)c->d_ctl.get();
+    a.pool_head = &ctl(c)->pool_head;
     a.pool_words = c->d_pool.cap();
     a.epoch = c->epoch;
-    a.status = (int32_t *)(c->d_ctl + 8);
-    a.work = count ? (unsigned long long *)(c->d_ctl + 16) : nullptr;
+    a.status = &ctl(c)->status;
+    a.work = count ? ctl(c)->work : nullptr;
     a.sw_sub = nullptr;
     a.sw_out = nullptr;
     a.rec_out = nullptr;
@@ -391,14 +397,7 @@ KArgs make_args(svt_ctx *c, const svt_locus *d_loci, svt_result *d_out, uint32_t
     a.rec_base = 0;
     a.redo_list = nullptr;
     a.redo_ctr = a.redo_next = nullptr;
-    a.bk.ev = c->d_bkev;
-    a.bk.off = c->d_bkoff;
-    a.bk.pm = c->d_bkpm;
-    a.bk.nbk = c->bk_n;
-    a.bk.cbase = c->d_bkbase;
-    a.bk.cnb = c->d_bknb;
-    a.bk.maxd = c->d_bkmaxd;
-    a.bk.on = c->bk_ready ? 1 : 0;
+    a.bk = c->bk.view();
     return a;
 }
 
@@ -419,9 +418,9 @@ svt_status launch(svt_ctx *c, const svt_locus *d_loci, svt_result *d_out, size_t
     // cleared once per epoch cycle
     c->epoch = c->epoch % ((1u << 24) - 1u) + 1u;
     if (c->epoch == 1 || captured) {   // a new epoch cycle (or every replay): the pool head starts from zero
-        HIP_TRY(c, hipMemsetAsync(c->d_ctl, 0, 8, st));
+        HIP_TRY(c, hipMemsetAsync(&ctl(c)->pool_head, 0, 8, st));
     }
-    if (count) HIP_TRY(c, hipMemsetAsync(c->d_ctl + 16, 0, 8 * W_N, st));
+    if (count) HIP_TRY(c, hipMemsetAsync(ctl(c)->work, 0, 8 * W_N, st));
     KArgs a = make_args(c, d_loci, d_out, (uint32_t)n, count);
     a.rec_out = reinterpret_cast<uint4 *>(rec_out);
     a.rec_index = rec_index;
@@ -443,7 +442,7 @@ svt_status launch(svt_ctx *c, const svt_locus *d_loci, svt_result *d_out, size_t
         // "next" word is the scratch ctr[3]: replays run whenever the caller likes, so they must
         // neither read nor leave state the direct launches' alternation depends on.
         a.redo_list = c->d_redo;
-        uint32_t *ctr = (uint32_t *)(c->d_ctl + CTL_REDO);
+        uint32_t *ctr = ctl(c)->redo;
         if (captured) {
             a.redo_ctr = ctr + 2;
             a.redo_next = ctr + 3;
@@ -461,10 +460,10 @@ svt_status launch(svt_ctx *c, const svt_locus *d_loci, svt_result *d_out, size_t
         const unsigned per = WPB * (wide ? 64u : 32u);
         const dim3 lgrid((unsigned)((2 * n + per - 1) / per));
         if (wide) {
-            if (c->bk_ready) hipLaunchKernelGGL((refine_lane_kernel<64, true>), lgrid, block, 0, st, a);
+            if (c->bk.ready) hipLaunchKernelGGL((refine_lane_kernel<64, true>), lgrid, block, 0, st, a);
             else hipLaunchKernelGGL((refine_lane_kernel<64, false>), lgrid, block, 0, st, a);
         } else {
-            if (c->bk_ready) hipLaunchKernelGGL((refine_lane_kernel<32, true>), lgrid, block, 0, st, a);
+            if (c->bk.ready) hipLaunchKernelGGL((refine_lane_kernel<32, true>), lgrid, block, 0, st, a);
             else hipLaunchKernelGGL((refine_lane_kernel<32, false>), lgrid, block, 0, st, a);
         }
         hipLaunchKernelGGL(refine_redo_kernel, dim3(8192), block, 0, st, a);   // ~1 left-over window per wave
@@ -563,484 +562,6 @@ svt_status svt_open_multi(const svt_params *params, int device_count, const int 
 
 int svt_device_count(const svt_ctx *c) { return c ? 1 + (int)c->subs.size() : 0; }
 
-extern "C++" {
-namespace {
-
-// Run fn(k) for k = 0 .. n-1 on up to `cap` threads (the host pass of svt_load_pileup is per contig).
-template <typename F>
-void parallel_for(size_t n, size_t cap, F fn) {
-    const size_t T = std::max<size_t>(1, std::min<size_t>({n, cap, (size_t)std::max(1u, std::thread::hardware_concurrency())}));
-    if (T <= 1) {
-        for (size_t k = 0; k < n; k++) fn(k);
-        return;
-    }
-    std::atomic<size_t> next{0};
-    std::vector<std::thread> th;
-    for (size_t t = 0; t < T; t++)
-        th.emplace_back([&] {
-            for (size_t k; (k = next.fetch_add(1)) < n;) fn(k);
-        });
-    for (auto &x : th) x.join();
-}
-
-// The device index of the loaded pileup (svt_index.inc / svt_index2.inc).  Stream walk: the walk
-// (one pass over the stream, events staged per range), an exclusive scan of the range totals, the
-// staged rows to their places.  Lane per read: census, the scan of the group totals, emit.
-// `first`: between scan and placement, size and allocate the event lists from the totals (one
-// synchronous read-back); later calls (svt_reindex) reuse them -- the totals depend on the
-// pileup only.  `ms`: the index kernels' device time (HIP events; read-back and allocations
-// excluded).
-// lane per read (svt_index2.inc) for short reads -- a wave's 64 reads then take a few steps
-// each; long reads (a lane walking thousands of ops waits on its loads) take the stream walk,
-// which spreads every slot of 256 ops over the wave; never for a group of > 2^27 ops
-bool index_lane(const svt_ctx *c, uint64_t nops, uint64_t nreads) {
-    return c->n_groups > 0 && (c->ix_mode == 1 || (c->ix_mode == 0 && nops <= 64ull * nreads));
-}
-
-IxArgs ix_args(const svt_ctx *c) {
-    IxArgs a;
-    a.stream = c->d_cigar;
-    a.soff = c->d_off64;
-    a.rec = c->d_rec;
-    a.clip8 = c->d_clip8;
-    a.part = c->d_part;
-    a.agg = c->d_agg;
-    a.bsum = c->d_bsum;
-    a.bpre = c->d_bpre;
-    a.spoffD = c->d_spoffD;
-    a.spoffI = c->d_spoffI;
-    a.spD = c->d_spD;
-    a.spI = c->d_spI;
-    a.capD = c->n_evD;
-    a.capI = c->n_evI;
-    a.err = (uint32_t *)(c->d_ctl + 12);   // sticky status word 2 (svt_sync reports it)
-    a.scr = c->d_scr;
-    a.scrh = c->d_scrh;
-    a.ovf = c->d_ovf;
-    a.n_ranges = c->n_ranges;
-    return a;
-}
-
-svt_status build_index(svt_ctx *c, hipStream_t st, bool first, double *ms) {
-    IxArgs a = ix_args(c);
-    DevEvent ev[4];
-    if (ms)
-        for (auto &e : ev) HIP_TRY(c, e.create());
-    const bool lane = index_lane(c, c->n_ops, (uint64_t)c->n_reads);
-    c->load_stats.index_kind = lane ? 1u : 2u;
-    const uint32_t nparts = lane ? c->n_groups : c->n_ranges;   // what the scan runs over
-    Ix2Args a2{a, c->d_cnt, (uint64_t)c->n_reads, c->n_groups};
-    const dim3 grid2((unsigned)((c->n_groups + IX2_WPB - 1) / IX2_WPB)), block2(64 * IX2_WPB);
-    const dim3 grid1((unsigned)((c->n_ranges + IX_WPB - 1) / IX_WPB)), block1(64 * IX_WPB);
-    if (ms) HIP_TRY(c, hipEventRecord(ev[0], st));
-    if (c->bsum_dirty) {
-        HIP_TRY(c, hipMemsetAsync(c->d_bsum, 0, c->n_bsum * sizeof(IxTot), st));
-        c->bsum_dirty = false;
-    }
-    c->bsum_dirty = true;
-    if (lane)
-        hipLaunchKernelGGL(ix2_census_kernel, grid2, block2, 0, st, a2);
-    else
-        hipLaunchKernelGGL(index_kernel, grid1, block1, 0, st, a);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) {   // the blocks' exclusive prefixes (ix_part_base adds the ranges' within a block)
-        hipLaunchKernelGGL(ix_scan_blocks_kernel, dim3(1), dim3(IX_SCAN_T), 0, st, c->d_bsum, c->d_bpre,
-                           (nparts + IX_BLK - 1) / IX_BLK, c->d_tot, c->d_spoffD, c->d_spoffI, (uint64_t)c->n_reads);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) return fail(c, SVT_EDEVICE, "index census: %s", hipGetErrorString(e));
-    c->bsum_dirty = false;   // the scan launched: it zeroes the block sums behind itself
-    if (ms) HIP_TRY(c, hipEventRecord(ev[1], st));
-    if (first) {
-        uint64_t t[IX_NTOT];
-        e = hipMemcpyAsync(t, c->d_tot, sizeof t, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return fail(c, SVT_EDEVICE, "index totals: %s", hipGetErrorString(e));
-        c->n_evD = t[IX_D];
-        c->n_evI = t[IX_I];
-        c->n_ins = t[IX_I];
-        svt_status s;
-        if ((s = upload<uint4>(c, c->d_spD, nullptr, 0, std::max<uint64_t>(c->n_evD, 1)))) return s;
-        if ((s = upload<uint4>(c, c->d_spI, nullptr, 0, std::max<uint64_t>(c->n_evI, 1)))) return s;
-        a.spD = c->d_spD;
-        a.spI = c->d_spI;
-        a.capD = c->n_evD;
-        a.capI = c->n_evI;
-        a2.a = a;
-    }
-    if (ms) HIP_TRY(c, hipEventRecord(ev[2], st));
-    if (lane) hipLaunchKernelGGL(ix2_emit_kernel, grid2, block2, 0, st, a2);
-    else hipLaunchKernelGGL(ix_copy_kernel, grid1, block1, 0, st, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(c, SVT_EDEVICE, "index emit: %s", hipGetErrorString(e));
-    if (ms) {
-        float t0 = 0.f, t1 = 0.f;
-        e = hipEventRecord(ev[3], st);
-        if (e == hipSuccess) e = hipEventSynchronize(ev[3]);
-        if (e == hipSuccess) e = hipEventElapsedTime(&t0, ev[0], ev[1]);
-        if (e == hipSuccess) e = hipEventElapsedTime(&t1, ev[2], ev[3]);
-        if (e != hipSuccess) return fail(c, SVT_EDEVICE, "index timing: %s", hipGetErrorString(e));
-        *ms = (double)t0 + (double)t1;
-    }
-    return SVT_OK;
-}
-
-// ---- the value-bucketed event index (svt_bucket_build.inc): launch arguments, one pass, the
-// first build at load
-BkBuild bk_args(const svt_ctx *c, bool count, bool captured) {
-    BkBuild b{};
-    b.ev = c->d_bkev;
-    b.off = c->d_bkoff;
-    b.cur = count ? c->d_bkoff : captured ? c->d_bkcap : c->d_bkcur;
-    b.pmx = c->d_bkpm;
-    b.nbk = c->bk_n;
-    b.maxd = c->d_bkmaxd;
-    b.cbase = c->d_bkbase;
-    b.cnb = c->d_bknb;
-    b.k = count || captured ? 0u : c->bk_builds;
-    b.n_ev = c->bk_nev;
-    b.err = (uint32_t *)(c->d_ctl + 12);   // sticky status word 2 (svt_sync reports it)
-    return b;
-}
-
-// One counting or filing pass on st: short reads walked from the CIGAR stream; long reads counted
-// from the span lists (at load) and filed from the stream walk's stage (index_kernel, which the
-// caller ran first).
-svt_status bk_pass(svt_ctx *c, hipStream_t st, bool count, bool captured) {
-    const IxArgs a = ix_args(c);
-    const BkBuild b = bk_args(c, count, captured);
-    const uint64_t nr = (uint64_t)c->n_reads;
-    if (index_lane(c, c->n_ops, nr)) {
-        const dim3 grid((unsigned)((c->n_groups + IXB_WPB - 1) / IXB_WPB)), block(64 * IXB_WPB);
-        if (count) hipLaunchKernelGGL(ixb_lane_kernel<true>, grid, block, 0, st, a, b, nr);
-        else hipLaunchKernelGGL(ixb_lane_kernel<false>, grid, block, 0, st, a, b, nr);
-    } else if (count) {   // (at load: the span lists the first build made)
-        const dim3 grid((unsigned)((nr + IXB_T - 1) / IXB_T)), block(IXB_T);
-        hipLaunchKernelGGL(ixb_lists_kernel<true>, grid, block, 0, st, a, b, nr);
-    } else {              // from the stream walk's stage (index_kernel ran just before on st)
-        const dim3 grid((unsigned)((c->n_ranges + IX_WPB - 1) / IX_WPB)), block(64 * IX_WPB);
-        hipLaunchKernelGGL(ixb_copy_kernel, grid, block, 0, st, a, b);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return SVT_OK;
-}
-
-svt_status bk_check_err(svt_ctx *c) {
-    uint32_t e = 0;
-    HIP_TRY(c, hipDeviceSynchronize());
-    HIP_TRY(c, hipMemcpy(&e, c->d_ctl + 12, 4, hipMemcpyDeviceToHost));
-    if (e) {
-        HIP_TRY(c, hipMemset(c->d_ctl + 12, 0, 4));
-        return fail(c, SVT_EDEVICE, "%s", "device index build: the value buckets disagree with their count");
-    }
-    return SVT_OK;
-}
-
-// The first build (svt_load_pileup, after the span lists): buckets per contig from the largest
-// pos / endpos (values past them -- walks lengthened by H / P / N ops -- share the contig's last
-// bucket), the counting pass, the extents and prefix maxima on the host, the filing pass.  A pileup
-// whose events or buckets pass 2^32 keeps the span lists alone (bk_ready stays false).
-svt_status bk_load(svt_ctx *c, const std::vector<int64_t> &vtop) {
-    const int32_t nt = c->n_targets;
-    std::vector<uint64_t> cbase((size_t)nt);
-    std::vector<uint32_t> cnb((size_t)nt);
-    uint64_t NB = 0;
-    for (int32_t t = 0; t < nt; t++) {
-        const uint64_t nb = (((uint64_t)std::max<int64_t>(vtop[(size_t)t], 0) + 65536u) >> BKS) + 2u;
-        cbase[(size_t)t] = NB;
-        cnb[(size_t)t] = (uint32_t)nb;
-        NB += nb;
-    }
-    if (nt == 0 || NB >= 0xffffffffull) return SVT_OK;
-    svt_status s;
-    if ((s = upload(c, c->d_bkbase, cbase.data(), cbase.size()))) return s;
-    if ((s = upload(c, c->d_bknb, cnb.data(), cnb.size()))) return s;
-    if ((s = upload<uint32_t>(c, c->d_bkmaxd, nullptr, 0, (size_t)nt))) return s;
-    const uint64_t S1 = NB + 1;   // the tables' stride per array
-    if ((s = upload<uint32_t>(c, c->d_bkoff, nullptr, 0, BA_N * S1))) return s;   // (zeroed: the counts)
-    if ((s = upload<uint32_t>(c, c->d_bkcur, nullptr, 0, BA_N * S1))) return s;
-    if ((s = upload<uint32_t>(c, c->d_bkcap, nullptr, 0, (BA_N * S1 + 3) / 4 * 4))) return s;   // (whole uint4s: bk_zero_kernel)
-    if ((s = upload<int32_t>(c, c->d_bkpm, nullptr, 0, 3 * S1))) return s;
-    HIP_TRY(c, hipMemset(c->d_bkpm, 0xff, 3 * S1 * sizeof(int32_t)));   // -1: no key
-    c->bk_n = NB;
-    if ((s = bk_pass(c, nullptr, true, false)) || (s = bk_check_err(c))) return s;
-    // the extents: every array's buckets in order, the arrays one after the other in d_bkev
-    std::vector<uint32_t> cnt((size_t)(BA_N * S1));
-    std::vector<int32_t> pm((size_t)(3 * S1));
-    HIP_TRY(c, hipMemcpy(cnt.data(), c->d_bkoff, cnt.size() * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(pm.data(), c->d_bkpm, pm.size() * 4, hipMemcpyDeviceToHost));
-    uint64_t acc = 0;
-    for (int A = 0; A < BA_N; A++) {
-        const uint64_t a0 = acc;
-        uint32_t *o = cnt.data() + (size_t)A * S1;
-        for (uint64_t g = 0; g < NB; g++) {
-            const uint32_t x = o[(size_t)g];
-            o[(size_t)g] = (uint32_t)acc;
-            acc += x;
-            if (acc >= 0xffffffffull) return SVT_OK;   // (bk_ready stays false: the span lists alone)
-        }
-        o[(size_t)NB] = (uint32_t)acc;
-        c->bk_events[A] = acc - a0;
-        if (A < 3)   // the BELOW keys' prefix maxima, within each contig
-            for (int32_t t = 0; t < nt; t++) {
-                int32_t m = -1;
-                int32_t *q = pm.data() + (size_t)A * S1;
-                for (uint64_t g = cbase[(size_t)t], g1 = g + cnb[(size_t)t]; g < g1; g++) m = q[(size_t)g] = std::max(m, q[(size_t)g]);
-            }
-    }
-    HIP_TRY(c, hipMemcpy(c->d_bkoff, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_bkpm, pm.data(), pm.size() * 4, hipMemcpyHostToDevice));
-    if ((s = upload<uint4>(c, c->d_bkev, nullptr, 0, std::max<uint64_t>(acc, 1)))) return s;
-    c->bk_nev = (uint32_t)acc;
-    c->bk_builds = 0;   // the cursors are zero: the first filing pass is epoch 0
-    if ((s = bk_pass(c, nullptr, false, false)) || (s = bk_check_err(c))) return s;
-    c->bk_builds = 1;
-    c->bk_ready = true;
-    return SVT_OK;
-}
-
-}  // namespace
-}  // extern "C++"
-
-// The pileup of a context from per-read columns in host memory -- nc[r] = n_cigar | clip << 30,
-// soff[0..nr] the reads' offsets in the CIGAR stream (a read without ops owns one 0M word) --
-// and the stream itself, in host memory (stream_h) or already on the device (stream_d, with
-// STREAM_PAD zero words after its end: moved from once validation has passed, else left alone).  The host pass
-// validates and builds the prefix-max endpos, the records, the read buckets, the index ranges;
-// then the uploads and the first device index build.
-static svt_status load_core(svt_ctx *c, int32_t nt, const int64_t *tid_off, const int32_t *pos, const int32_t *endpos,
-                            const uint32_t *nc, const uint64_t *soff, const uint32_t *stream_h, DevBuf<uint32_t> *stream_d,
-                            uint64_t nops, double t_pre_ms) {
-    using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
-    const clk::time_point t_start = clk::now();
-    const int64_t nr = nt ? tid_off[nt] : 0;
-    const uint64_t nstream = nr > 0 ? soff[nr] : 0;
-    // ---- host pass, per contig in parallel: validation, prefix-max endpos, records, buckets
-    std::vector<int32_t> emax((size_t)nr);
-    std::vector<uint4> rec((size_t)nr);
-    std::vector<std::vector<uint2>> bk((size_t)nt);
-    std::vector<const char *> bad((size_t)nt, nullptr);
-    std::vector<int64_t> vtop((size_t)nt, 0);   // per contig its largest pos / endpos (the value buckets)
-    parallel_for((size_t)nt, 16, [&](size_t t) {
-        const int64_t r0 = tid_off[t], r1 = tid_off[t + 1];
-        if (r1 - r0 > 0xffffffffll) { bad[t] = "> 2^32 reads on one contig"; return; }
-        int32_t m = INT32_MIN, maxpos = 0;
-        for (int64_t r = r0; r < r1; r++) {
-            if (r > r0 && pos[r] < pos[r - 1]) { bad[t] = "reads not sorted by pos within a contig"; return; }
-            if (pos[r] < 0 || endpos[r] <= pos[r]) { bad[t] = "pos < 0 or endpos <= pos"; return; }
-            const uint64_t w = soff[r + 1] - soff[r], n = nc[r] & NCIG_MASK;
-            if (soff[r + 1] < soff[r] || soff[r + 1] > nstream || w != std::max<uint64_t>(n, 1)) {
-                bad[t] = "bad cig_off";
-                return;
-            }
-            if (endpos[r] > m) m = endpos[r];
-            maxpos = std::max(maxpos, pos[r]);
-            emax[(size_t)r] = m;
-            rec[(size_t)r] = make_uint4((uint32_t)pos[r], (uint32_t)endpos[r], nc[r], (uint32_t)t);   // .w: the contig
-        }
-        // bucket b = 0..nb-1: {first contig-relative read with pos >= b << BKT_SHIFT, first with
-        // emax >= b << BKT_SHIFT}; the last bucket lies past every pos and endpos: {nr, nr}
-        const int64_t top = r1 > r0 ? std::max<int64_t>(maxpos, m) : 0;
-        vtop[t] = top;
-        const int64_t nb = (top >> BKT_SHIFT) + 2;
-        std::vector<uint2> &B = bk[t];
-        B.reserve((size_t)nb);
-        int64_t rp = r0, re = r0;
-        for (int64_t b = 0; b < nb; b++) {
-            const int64_t x = b << BKT_SHIFT;
-            while (rp < r1 && (int64_t)pos[rp] < x) rp++;
-            while (re < r1 && (int64_t)emax[(size_t)re] < x) re++;
-            B.push_back(make_uint2((uint32_t)(rp - r0), (uint32_t)(re - r0)));
-        }
-    });
-    for (int32_t t = 0; t < nt; t++)
-        if (bad[(size_t)t]) return fail(c, SVT_EINVAL, "pileup: %s", bad[(size_t)t]);
-    if (stream_d) c->d_cigar = std::move(*stream_d);   // the context owns it from here on (freed with the pileup)
-    std::vector<int64_t> bkt_off((size_t)nt + 1, 0);
-    for (int32_t t = 0; t < nt; t++) bkt_off[(size_t)t + 1] = bkt_off[(size_t)t] + (int64_t)bk[(size_t)t].size();
-    std::vector<uint2> bkt((size_t)bkt_off[(size_t)nt]);
-    parallel_for((size_t)nt, 16, [&](size_t t) { std::copy(bk[t].begin(), bk[t].end(), bkt.begin() + bkt_off[t]); });
-    // ---- ranges of the index build: ~T stream ops each, cut at read starts and contig starts
-    // 32 768 ranges, of at most 65 536 ops: cfg2 index 0.602 -> 0.531 ms, cfg3 2.30 -> 2.19 ms
-    // against 131 072 ranges (profiles/r05_J; fewer, longer ranges cross fewer range-boundary
-    // slots), while cfg5's 9 G ops keep ~137 K ranges (the stage's 96 events a range).
-    constexpr uint64_t IX_TMAX = 65536;
-    const uint64_t T = std::min<uint64_t>(std::max<uint64_t>(nstream / c->ix_ranges, 2048), IX_TMAX);
-    std::vector<std::vector<uint64_t>> pt((size_t)nt);
-    parallel_for((size_t)nt, 16, [&](size_t t) {
-        for (int64_t r = tid_off[t], r1 = tid_off[t + 1]; r < r1;) {
-            pt[t].push_back((uint64_t)r);
-            const uint64_t s0 = soff[r];
-            const int64_t rs = r;   // (at most IX_RCAP reads: the single-pass walk stages their offsets)
-            for (r++; r < r1 && soff[r] - s0 < T && r - rs < (int64_t)IX_RCAP; r++) {}
-        }
-    });
-    std::vector<uint64_t> part;
-    for (int32_t t = 0; t < nt; t++) part.insert(part.end(), pt[(size_t)t].begin(), pt[(size_t)t].end());
-    part.push_back((uint64_t)nr);
-    if (part.size() - 1 > 0xffffffffull) return fail(c, SVT_EINVAL, "pileup: %s", "too many index ranges");
-    c->n_ranges = (uint32_t)(part.size() - 1);
-    // the lane-per-read index's 64-read groups: each group's ops < 2^27, so that its events fit
-    // the 32-bit wave scans and buffer sizes (else the stream walk builds the index)
-    c->n_groups = (uint32_t)((nr + WAVE - 1) / WAVE);
-    for (int64_t g0 = 0; g0 < nr && c->n_groups; g0 += WAVE)
-        if (soff[std::min<int64_t>(g0 + WAVE, nr)] - soff[g0] >= (1ull << 27)) c->n_groups = 0;
-    c->load_stats.host_ms = t_pre_ms + ms_since(t_start);
-
-    const clk::time_point t_up = clk::now();
-    svt_status s;
-    if ((s = upload(c, c->d_pos, pos, (size_t)nr))) return s;
-    if ((s = upload(c, c->d_emax, emax.data(), (size_t)nr))) return s;
-    if ((s = upload(c, c->d_rec, rec.data(), (size_t)nr))) return s;
-    {
-        std::vector<uint8_t> clip8((size_t)std::max<int64_t>(nr, 1), 0);
-        for (int64_t r = 0; r < nr; r++) clip8[(size_t)r] = (uint8_t)(nc[r] >> 30);
-        if ((s = upload(c, c->d_clip8, clip8.data(), clip8.size()))) return s;
-    }
-    if ((s = upload(c, c->d_off64, soff, nr > 0 ? (size_t)nr + 1 : 0, nr > 0 ? 0 : 1))) return s;
-    if ((s = upload(c, c->d_bkt, bkt.data(), bkt.size()))) return s;
-    if ((s = upload(c, c->d_bkt_off, bkt_off.data(), bkt_off.size()))) return s;
-    if (nt > 0) { if ((s = upload(c, c->d_tid_off, tid_off, (size_t)nt + 1))) return s; }
-    else if ((s = upload<int64_t>(c, c->d_tid_off, nullptr, 0, 1))) return s;
-    if (stream_d) c->dev_bytes += (nstream + STREAM_PAD) * 4u;
-    else if ((s = upload(c, c->d_cigar, stream_h, (size_t)nstream, STREAM_PAD))) return s;
-    if ((s = upload(c, c->d_part, part.data(), part.size()))) return s;
-    const size_t S = (size_t)nr + 1;
-    if ((s = upload<uint64_t>(c, c->d_spoffD, nullptr, 0, S))) return s;
-    if ((s = upload<uint64_t>(c, c->d_spoffI, nullptr, 0, S))) return s;
-    if ((s = upload<uint2>(c, c->d_cnt, nullptr, 0, std::max<size_t>((size_t)nr, 1)))) return s;
-    const size_t NR = std::max<size_t>({(size_t)c->n_ranges, (size_t)c->n_groups, (size_t)1});
-    if ((s = upload<IxTot>(c, c->d_agg, nullptr, 0, NR))) return s;
-    const size_t NB = (NR + IX_BLK - 1) / IX_BLK;
-    if ((s = upload<IxTot>(c, c->d_bsum, nullptr, 0, NB))) return s;   // (zeroed: the first build adds into them)
-    if ((s = upload<IxTot>(c, c->d_bpre, nullptr, 0, NB))) return s;
-    HIP_TRY(c, hipMemset(c->d_bsum, 0, NB * sizeof(IxTot)));
-    c->n_bsum = NB;
-    c->bsum_dirty = false;
-    if (c->n_ranges > 0x7fffffffu) return fail(c, SVT_EINVAL, "pileup: %s", "too many index ranges");
-    if ((s = upload<uint64_t>(c, c->d_tot, nullptr, 0, IX_NTOT))) return s;
-    if (!index_lane(c, nops, (uint64_t)nr)) {   // the stream walk's scratch slots
-        const size_t RR = std::max<size_t>(c->n_ranges, 1);
-        if ((s = upload<uint4>(c, c->d_scr, nullptr, 0, RR * IX_SCAP))) return s;
-        if ((s = upload<uint2>(c, c->d_scrh, nullptr, 0, RR * IX_RCAP))) return s;
-        if ((s = upload<uint32_t>(c, c->d_ovf, nullptr, 0, RR))) return s;
-    }
-    c->load_stats.upload_ms = ms_since(t_up);
-    c->n_targets = nt;
-    c->n_reads = nr;
-    c->n_ops = nops;
-    if (nr > 0) {
-        double ims = 0;
-        if ((s = build_index(c, nullptr, true, &ims))) return s;
-        c->load_stats.index_ms = ims;
-        const uint64_t R = (uint64_t)nr;
-        c->load_stats.span_events = c->n_evD + c->n_evI;
-        c->load_stats.lead_blocks = 0;   // (no lead chunks since 0.17: refine_end's stops vote as e + 2)
-        c->load_stats.slow_reads = 0;    // (no slow reads since 0.17: walks saturate at 2^30)
-        // lane per read: census stream + soff + rec (24 B/read), cnt written (8 B/read); emit cnt
-        // + soff + rec (32 B/read) + stream, the per-read offsets (16 B/read) written; the events
-        // written.  Stream walk (one pass): stream + soff + rec (24 B/read); the staged offsets
-        // (8 B/read) and events written to scratch, read back, written to their places (16 B/read
-        // of offsets, 3 x 16 B/event).
-        if (c->load_stats.index_kind == 1)
-            c->load_stats.index_bytes = 8ull * nstream + 65ull * R + 16ull * (c->n_evD + c->n_evI);
-        else
-            c->load_stats.index_bytes = 4ull * nstream + 56ull * R + 48ull * (c->n_evD + c->n_evI);
-        if (c->bk_on) {   // the value buckets, filed from the stream (short reads) or the span lists
-            if ((s = bk_load(c, vtop))) return s;
-            if (c->bk_ready) {
-                uint64_t placed = 0;
-                for (int A = 0; A < BA_N; A++) placed += c->bk_events[A];
-                c->load_stats.bucket_index = 1;
-                c->load_stats.buckets = c->bk_n;
-                c->load_stats.bucket_events = placed;
-                c->load_stats.bucket_bytes = c->load_stats.index_kind == 1
-                    ? 4ull * nstream + 24ull * R + 28ull * placed
-                    : 4ull * nstream + 32ull * R + 32ull * (c->n_evD + c->n_evI) + 28ull * placed;
-            }
-        }
-    } else {
-        for (auto *pp : {&c->d_spD, &c->d_spI})
-            if ((s = upload<uint4>(c, *pp, nullptr, 0, 1))) return s;
-    }
-    HIP_TRY(c, hipDeviceSynchronize());
-    {
-        uint32_t ixerr = 0;
-        HIP_TRY(c, hipMemcpy(&ixerr, c->d_ctl + 12, 4, hipMemcpyDeviceToHost));
-        if (ixerr) {
-            HIP_TRY(c, hipMemset(c->d_ctl + 12, 0, 4));
-            return fail(c, SVT_EDEVICE, "%s", "device index build: emit overran the census's sizes");
-        }
-    }
-    c->loaded = true;
-    return SVT_OK;
-}
-
-static svt_status load_1(svt_ctx *c, const svt_pileup_view *p) {
-    if (!c || !p) return SVT_EINVAL;
-    if (p->n_targets < 0 || (p->n_targets > 0 && !p->tid_off))
-        return fail(c, SVT_EINVAL, "pileup: %s", "bad n_targets / tid_off");
-    DEV_GUARD(c);
-    free_pileup(c);
-    using clk = std::chrono::steady_clock;
-    const clk::time_point t_start = clk::now();
-    c->load_stats = svt_load_stats{};
-    const int32_t nt = p->n_targets;
-    const int64_t nr = nt ? p->tid_off[nt] : 0;
-    if (nt && p->tid_off[0] != 0) return fail(c, SVT_EINVAL, "pileup: %s", "tid_off[0] != 0");
-    for (int32_t t = 0; t < nt; t++)
-        if (p->tid_off[t + 1] < p->tid_off[t]) return fail(c, SVT_EINVAL, "pileup: %s", "tid_off not monotone");
-    if (nr > 0 && (!p->pos || !p->endpos || !p->cig_off || (!p->cigar && p->cig_off[nr] > 0)))
-        return fail(c, SVT_EINVAL, "pileup: %s", "missing arrays");
-    const uint64_t nops = nr > 0 ? p->cig_off[nr] : 0;
-    if (nr > 0 && p->cig_off[0] != 0) return fail(c, SVT_EINVAL, "pileup: %s", "cig_off[0] != 0");
-    // per read n_cigar | clip << 30 (clip from the caller, or from the CIGAR words)
-    std::vector<uint32_t> nc((size_t)nr);
-    std::vector<int64_t> zeros((size_t)std::max(nt, 1), 0);   // reads with n_cigar == 0 per contig
-    std::vector<const char *> bad((size_t)std::max(nt, 1), nullptr);
-    parallel_for((size_t)nt, 16, [&](size_t t) {
-        for (int64_t r = p->tid_off[t], r1 = p->tid_off[t + 1]; r < r1; r++) {
-            const uint64_t o0 = p->cig_off[r], o1 = p->cig_off[r + 1];
-            if (o1 < o0 || o1 > nops || o1 - o0 > NCIG_MASK) { bad[t] = "bad cig_off"; return; }
-            const uint32_t ncig = (uint32_t)(o1 - o0);
-            uint32_t clip;
-            if (p->clip) clip = p->clip[r] & 3u;
-            else clip = ncig ? (((p->cigar[o1 - 1] & 0xfu) == OP_SOFT ? 1u : 0u) |
-                                ((p->cigar[o0] & 0xfu) == OP_SOFT ? 2u : 0u)) : 0u;
-            zeros[t] += ncig == 0;
-            nc[(size_t)r] = ncig | clip << 30;
-        }
-    });
-    for (int32_t t = 0; t < nt; t++)
-        if (bad[(size_t)t]) return fail(c, SVT_EINVAL, "pileup: %s", bad[(size_t)t]);
-    // ---- the CIGAR stream: the caller's words; a read with n_cigar == 0 gets one 0M word (no
-    // advance, never a candidate) so that every read owns a stream op (svt_index.inc)
-    int64_t nzero = 0;
-    for (int32_t t = 0; t < nt; t++) nzero += zeros[(size_t)t];
-    const uint64_t *soff = p->cig_off;
-    const uint32_t *strm = p->cigar;
-    std::vector<uint64_t> soff2;
-    std::vector<uint32_t> strm2;
-    if (nzero > 0) {
-        soff2.resize((size_t)nr + 1);
-        strm2.reserve(nops + (uint64_t)nzero);
-        for (int64_t r = 0; r < nr; r++) {
-            soff2[(size_t)r] = strm2.size();
-            const uint64_t o0 = p->cig_off[r], o1 = p->cig_off[r + 1];
-            if (o1 == o0) strm2.push_back(0u);
-            else strm2.insert(strm2.end(), p->cigar + o0, p->cigar + o1);
-        }
-        soff2[(size_t)nr] = strm2.size();
-        soff = soff2.data();
-        strm = strm2.data();
-    }
-    const double pre = std::chrono::duration<double, std::milli>(clk::now() - t_start).count();
-    svt_status s = load_core(c, nt, p->tid_off, p->pos, p->endpos, nc.data(), soff, strm, nullptr, nops, pre);
-    c->load_stats.total_ms = std::chrono::duration<double, std::milli>(clk::now() - t_start).count();
-    return s;
-}
-
 // svt_open_multi: run fn(ctx_d, lo_d, hi_d) for the contiguous slices [lo_d, hi_d) of n items,
 // one per device, concurrently (one host thread per extra device); the first failure's
 // status and message are reported on the parent context.
@@ -1063,54 +584,6 @@ static svt_status for_devices(svt_ctx *c, size_t n, F fn) {
             if (d) snprintf(c->err, sizeof c->err, "device %d: %s", ctx[d]->device, ctx[d]->err);
             return st[d];
         }
-    return SVT_OK;
-}
-
-svt_status svt_load_pileup(svt_ctx *c, const svt_pileup_view *p) {
-    if (!c || !p) return SVT_EINVAL;
-    if (c->subs.empty()) return load_1(c, p);
-    // every device gets the whole pileup (n = device count: one "item" per device)
-    const size_t D = 1 + c->subs.size();
-    return for_devices(c, D, [&](svt_ctx *x, size_t lo, size_t hi) { return lo < hi ? load_1(x, p) : SVT_OK; });
-}
-
-svt_status svt_reindex(svt_ctx *c, void *stream) {
-    if (!c) return SVT_EINVAL;
-    if (!c->loaded) return fail(c, SVT_ESTATE, "%s", "svt_load_pileup not called");
-    DEV_GUARD(c);
-    if (c->n_reads == 0) return SVT_OK;
-    const hipStream_t st = (hipStream_t)stream;
-    svt_status s = order_on(c, st);   // after every launch already issued (they read the index)
-    if (s) return s;
-    if (!c->bk_ready) return build_index(c, st, false, nullptr);
-    // the value buckets: short reads filed straight from the CIGAR stream (ixb_lane_kernel); long
-    // reads walked by index_kernel and filed from its stage (ixb_copy_kernel).  The span lists stay
-    // as built at load.  A captured build files through its own cursors (zeroed by the graph), a
-    // direct one through the epoch cursors (svt_bucket_build.inc).
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (st) HIP_TRY(c, hipStreamIsCapturing(st, &cap));
-    const bool captured = cap == hipStreamCaptureStatusActive;
-    if (!index_lane(c, c->n_ops, (uint64_t)c->n_reads)) {   // long reads: the stream walk stages the events
-        const IxArgs a = ix_args(c);
-        hipLaunchKernelGGL(index_kernel, dim3((unsigned)((c->n_ranges + IX_WPB - 1) / IX_WPB)), dim3(64 * IX_WPB), 0, st, a);
-        HIP_TRY(c, hipGetLastError());
-        c->bsum_dirty = true;   // (its block sums are not scanned: the next span-list build clears them)
-    }
-    if (captured)
-    {   // (the buffer is allocated in whole uint4s: upload's size below rounds it up)
-        const uint64_t n4 = (BA_N * (c->bk_n + 1) + 3) / 4;
-        hipLaunchKernelGGL(bk_zero_kernel, dim3((unsigned)std::min<uint64_t>((n4 + 255) / 256, 4096)), dim3(256), 0, st,
-                           reinterpret_cast<uint4 *>(c->d_bkcap.get()), n4);
-        HIP_TRY(c, hipGetLastError());
-    }
-    if ((s = bk_pass(c, st, false, captured))) return s;
-    if (!captured) c->bk_builds++;
-    return SVT_OK;
-}
-
-svt_status svt_last_load_stats(const svt_ctx *c, svt_load_stats *out) {
-    if (!c || !out) return SVT_EINVAL;
-    *out = c->load_stats;
     return SVT_OK;
 }
 
@@ -1138,18 +611,16 @@ svt_status svt_sync(svt_ctx *c, void *stream) {
     DEV_GUARD(c);
     HIP_TRY(c, hipStreamSynchronize((hipStream_t)stream));
     if (c->have_last && c->last_stream != (hipStream_t)stream) HIP_TRY(c, hipStreamSynchronize(c->last_stream));
-    int32_t st2[2] = {0, 0};
-    HIP_TRY(c, hipMemcpy(st2, c->d_ctl + 8, 8, hipMemcpyDeviceToHost));
-    int32_t status = st2[0];
-    if (st2[1]) {   // the index build's guard fired: census and emit disagreed (an engine bug)
-        HIP_TRY(c, hipMemset(c->d_ctl + 12, 0, 4));
+    int32_t status = 0;
+    uint32_t ixerr = 0;
+    if (svt_status s = take_ix_status(c, &ixerr, &status)) return s;
+    if (ixerr)   // the index build's guard fired: census and emit disagreed (an engine bug)
         return fail(c, SVT_EDEVICE, "%s",
-                    st2[1] == 2   ? "device index build: a look-back never ended (results invalid)"
-                    : st2[1] == 3 ? "device index build: an event outside its value bucket's extent (results invalid)"
-                                  : "device index build: emit overran the census's sizes (results invalid)");
-    }
+                    ixerr == 2   ? "device index build: a look-back never ended (results invalid)"
+                    : ixerr == 3 ? "device index build: an event outside its value bucket's extent (results invalid)"
+                                 : "device index build: emit overran the census's sizes (results invalid)");
     if (status & 1) {
-        HIP_TRY(c, hipMemset(c->d_ctl + 8, 0, 4));   // sticky until reported
+        HIP_TRY(c, hipMemset(&ctl(c)->status, 0, 4));   // sticky until reported
         const svt_status g = grow_pool(c);            // a re-run of the batch now fits
         if (g) return g;
         return fail(c, SVT_EOVERFLOW, "%s", "candidate spill pool exhausted (pool grown; re-run the batch)");
@@ -1175,7 +646,7 @@ static svt_status run_batch_1(svt_ctx *c, const svt_locus *loci, size_t n, svt_r
     if (out) HIP_TRY(c, hipMemcpy(out, c->d_out, n * sizeof(svt_result), hipMemcpyDeviceToHost));
     if (w) {
         unsigned long long k[W_N];
-        HIP_TRY(c, hipMemcpy(k, c->d_ctl + 16, sizeof k, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(k, ctl(c)->work, sizeof k, hipMemcpyDeviceToHost));
         w->windows = k[W_WINDOWS]; w->reads = k[W_READS]; w->ops_walked = k[W_OPS]; w->candidates = k[W_CANDS];
         w->spilled_windows = k[W_SPILLED]; w->queries = k[W_QUERIES]; w->probe_entries = k[W_PROBE];
         w->range_reads = k[W_RANGE]; w->list_reads = k[W_LREADS]; w->list_entries = k[W_LENTRIES];
@@ -1192,7 +663,7 @@ static svt_status run_batch_1(svt_ctx *c, const svt_locus *loci, size_t n, svt_r
         // the value buckets (svt_bucket.inc): locus in + result out, per window two bucket offsets
         // and one prefix-max key, the 16-B events of its band's buckets and of the walks for ABOVE
         // (windows the buckets do not take -- none at the default parameters -- are not priced)
-        if (c->bk_ready) w->event_bytes = 24ull * n + 12ull * w->bucket_queries + 16ull * w->bucket_events;
+        if (c->bk.ready) w->event_bytes = 24ull * n + 12ull * w->bucket_queries + 16ull * w->bucket_events;
     }
     return SVT_OK;
 }
@@ -1394,6 +865,9 @@ svt_status svt_evidence_batch(svt_ctx *c, const svt_locus *loci, const svt_resul
         return evidence_1(x, loci + lo, refined + lo, hi - lo, out + 2 * lo);
     });
 }
+
+// ---- the pileup load and the index builds
+#include "svt_load_host.inc"
 
 // ---- include/svtrek_call.h
 #include "svt_callindex_host.inc"

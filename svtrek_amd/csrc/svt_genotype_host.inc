@@ -10,7 +10,7 @@ svt_status gt_check(svt_ctx *c, const svt_gt_params *p, size_t n) {
     if (p->flank < 0 || p->flank > (1 << 20)) return fail(c, SVT_EINVAL, "%s", "svt_genotype: flank in [0, 2^20]");
     if (n > 0x3fffffffull) return fail(c, SVT_EINVAL, "batch too large (%s)", "n > 2^30-1");
     if (!c->loaded) return fail(c, SVT_ESTATE, "%s", "svt_load_pileup not called");
-    if (c->n_reads != 0 && !c->bk_ready)
+    if (c->n_reads != 0 && !c->bk.ready)
         return fail(c, SVT_ESTATE, "%s",
                     "svt_genotype needs the value buckets (not built: SVTREK_INDEX=lists, or a pileup past 2^32 events)");
     return SVT_OK;

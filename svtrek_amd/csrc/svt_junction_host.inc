@@ -76,7 +76,7 @@ svt_status junction_load_1(svt_ctx *c, const svt_junction_view *v) {
     }
     if (n) {   // the own segments against the pileup's records
         std::vector<uint4> rec((size_t)nr);
-        HIP_TRY(c, hipMemcpy(rec.data(), c->d_rec, (size_t)nr * sizeof(uint4), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(rec.data(), c->reads.d_rec, (size_t)nr * sizeof(uint4), hipMemcpyDeviceToHost));
         for (uint64_t k = 0; k < n; k++) {
             const svt_junction_seg &g = v->seg[v->off[k]];
             const uint4 &q = rec[(size_t)v->read[k]];

@@ -135,7 +135,7 @@ svt_status poa_run(svt_ctx *c, const svt_poa_params *p, const svt_locus *loci, c
     a.loci = d_loci;
     a.refined = d_ref;
     a.n = (uint32_t)n;
-    a.ins_base = c->d_spoffI;
+    a.ins_base = c->ix.d_spoffI;
     a.ins_off = c->d_ins_off;
     a.ins_bases = c->d_ins_bases;
     a.cap = cap;

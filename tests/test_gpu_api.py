@@ -181,14 +181,25 @@ def test_reindex_keeps_results(engine_factory):
     _same(eng.refine(r.loci), want)
 
 
-def test_graph_replay_reindex(engine_factory):
+@functools.lru_cache(maxsize=None)
+def _replay_workload():
+    r = _workload(n_loci=3000, seed=71)
+    return r, O.refine_batch(r.pileup, r.loci, threads=8)
+
+
+@pytest.mark.parametrize("env", [None, {"SVTREK_IX": "stream"}, {"SVTREK_IX": "lane"}], ids=["auto", "stream", "lane"])
+def test_graph_replay_reindex(engine_factory, env):
     """svt_reindex + svt_refine_device captured into a HIP graph (torch.cuda.graph) replay with
     the oracle's results every time: the capture takes the two-pass index build (a replayed
-    single-pass build would carry its capture's epoch) and the refine resets its own counters."""
-    r = _workload(n_loci=3000, seed=71)
-    eng = engine_factory()
+    single-pass build would carry its capture's epoch) and the refine resets its own counters.
+    Both captured rebuilds, whichever the engine picks for this pileup by itself: SVTREK_IX=stream,
+    the long-read one (bk_zero_kernel, index_kernel and ixb_copy_kernel in the graph), and
+    SVTREK_IX=lane, the short-read one (bk_zero_kernel and ixb_lane_kernel)."""
+    r, want = _replay_workload()
+    eng = engine_factory(env=env)
     eng.load_pileup(r.pileup)
-    want = O.refine_batch(r.pileup, r.loci, threads=8)
+    if env:
+        assert eng.load_stats()["index_kind"] == {"lane": 1, "stream": 2}[env["SVTREK_IX"]]
     n = len(r.loci)
     d_loci = torch.from_numpy(r.loci.view(np.uint8).copy()).cuda()
     d_out = torch.zeros(n * RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
