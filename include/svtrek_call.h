@@ -84,7 +84,7 @@
  * Status codes: svt_call_scan is SVT_ESTATE before svt_load_pileup and when the value buckets are
  * not built (SVTREK_INDEX=lists, or a pileup too large for them); SVT_EINVAL on NULL arguments,
  * link < 0, link > 2^20, min_support < 1, len_permille > 1000, merge_gap > 2^20, merge_gap > 0 with
- * merge_min outside 1 .. 50, or no known type bit (unless rearr != 0: svtrek_rearr.h); SVT_ESTATE for more than 2^31 - 1 merged items.  svt_call_fetch is SVT_EINVAL for a
+ * merge_min outside 1 .. 50, or no known type bit (unless rearr != 0: svtrek_rearr.h, or bnd = 1: svtrek_bnd.h); SVT_ESTATE for more than 2^31 - 1 merged items.  svt_call_fetch is SVT_EINVAL for a
  * range past the scanned count (n == 0 is SVT_OK).  svt_call_scan is ordered after every launch the
  * context has issued (svt_reindex included), selects / restores the device as the other entry
  * points do, acts on the first device of an svt_open_multi context, synchronises, and must not be
@@ -102,7 +102,7 @@ extern "C" {
 #endif
 
 typedef struct svt_call {            /* 48 B */
-    int32_t type, chrom;             /* SVT_DEL / SVT_INS (SVT_DUP / SVT_INV with rearr != 0: svtrek_rearr.h); chrom = tid + 1 (svt_locus's) */
+    int32_t type, chrom;             /* SVT_DEL / SVT_INS (SVT_DUP / SVT_INV with rearr != 0: svtrek_rearr.h; SVT_BND with bnd = 1: svtrek_bnd.h); chrom = tid + 1 (svt_locus's) */
     uint32_t pos, end, support, depth, len, len_lo, len_hi, x_lo, x_hi, pad;
 } svt_call;
 
@@ -113,6 +113,7 @@ typedef struct svt_call_params {
     uint32_t merge_gap, merge_min;   /* 0: single ops as items; 1 .. 2^20: join a read's fragments of len >= merge_min (above) */
     uint32_t junctions;              /* 0: CIGAR items alone; 1: plus the items of split alignments (svtrek_junction.h) */
     uint32_t rearr;                  /* 0, or bits (1u << SVT_DUP) | (1u << SVT_INV): DUP / INV calls from split alignments (svtrek_rearr.h) */
+    uint32_t bnd;                    /* 0, or 1: translocation breakends from split alignments, SVT_BND calls (svtrek_bnd.h) */
 } svt_call_params;
 
 typedef struct svt_call_stats {
@@ -139,7 +140,7 @@ typedef struct svt_call_merge_stats {   /* all zero after a scan with merge_gap 
 } svt_call_merge_stats;
 
 /* link 10, min_support = the context's consensus_min_count (at least 1), both types, len_permille 0,
- * merge_gap 0, merge_min 20, junctions 0, rearr 0 */
+ * merge_gap 0, merge_min 20, junctions 0, rearr 0, bnd 0 */
 void svt_call_default_params(const svt_ctx *ctx, svt_call_params *out);
 
 /* Synchronous; the calls stay on the device. */

@@ -74,7 +74,8 @@
  * svt_load_pileup drops it) and for more than 2^31 - 1 union items.  svt_call_consensus after a scan
  * with junctions = 1 is SVT_ESTATE.
  * Out of scope: inversions and duplications (counted in other here; include/svtrek_rearr.h calls them
- * from the same table), translocations and BND records (counted in other), MAPQ or
+ * from the same table), translocations and BND records (counted in other here; include/svtrek_bnd.h
+ * calls them from the same table), MAPQ or
  * flag filters, a per-call count of junction support, inserted bases of junction calls, SA in the device
  * BAM decoder, several devices and the CPU backend.
  */

@@ -60,7 +60,7 @@
  *
  * Status codes.  svt_call_scan: SVT_EINVAL for any other bit in rearr; SVT_ESTATE for rearr != 0 without
  * a table for the loaded pileup; types without a DEL / INS bit stays SVT_EINVAL when rearr == 0.
- * Out of scope: translocations and BND records, genotypes of DUP / INV, rearrangement items combined
+ * Out of scope: translocations and BND records (include/svtrek_bnd.h calls them from the same table), genotypes of DUP / INV, rearrangement items combined
  * with CIGAR items, several devices, the CPU backend, SA in the device BAM decoder.
  */
 #ifndef SVTREK_REARR_H

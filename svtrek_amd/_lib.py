@@ -47,7 +47,8 @@ class SvtGtParams(C.Structure):
 class SvtCallParams(C.Structure):
     _fields_ = [("link", C.c_int32), ("min_support", C.c_int32), ("types", C.c_uint32), ("len_permille", C.c_uint32),
                 ("merge_gap", C.c_uint32), ("merge_min", C.c_uint32), ("junctions", C.c_uint32),
-                ("rearr", C.c_uint32)]   # (rearr: engine 0.33.0; an older engine neither sets nor reads it)
+                ("rearr", C.c_uint32),   # (rearr: engine 0.33.0; an older engine neither sets nor reads it)
+                ("bnd", C.c_uint32)]     # (bnd: engine 0.34.0; likewise)
 
 
 class SvtCallSplitStats(C.Structure):
@@ -65,6 +66,17 @@ class SvtCallJunctionStats(C.Structure):   # svt_call_junction_stats
 
 class SvtCallRearrStats(C.Structure):   # svt_call_rearr_stats
     _fields_ = [(n, C.c_uint64) for n in ("dup_items", "inv_items", "skipped", "clusters", "calls")] + [("build_ms", C.c_double)]
+
+
+class SvtCallBndStats(C.Structure):   # svt_call_bnd_stats
+    _fields_ = [(n, C.c_uint64) for n in ("items", "skipped", "classes", "clusters", "groups", "calls")] + [("build_ms", C.c_double)]
+
+
+def call_mate(calls):
+    """(mate chrom, o) of CALL_DTYPE records of type SVT_BND (include/svtrek_bnd.h's SVT_CALL_MATE_CHROM /
+    SVT_CALL_MATE_ORIENT): pad = (tid_hi + 1) << 2 | o."""
+    pad = np.asarray(calls["pad"], dtype=np.uint32)
+    return (pad >> 2).astype(np.int32), pad & 3
 
 
 class SvtJunctionView(C.Structure):   # svt_junction_view
@@ -191,6 +203,8 @@ CALL_MERGE_SYMBOLS = ("svt_call_merge_stats_get",)
 JUNCTION_SYMBOLS = ("svt_load_junctions", "svt_call_junction_stats_get")
 # include/svtrek_rearr.h (svt_call_params.rearr), added with engine 0.33.0: Engine.call(rearrangements=...) raises without it
 REARR_SYMBOLS = ("svt_call_rearr_stats_get",)
+# include/svtrek_bnd.h (svt_call_params.bnd), added with engine 0.34.0: Engine.call(breakends=True) raises without it
+BND_SYMBOLS = ("svt_call_bnd_stats_get",)
 # include/svtrek_genotype.h: likewise (Engine.genotype raises on a backend without it)
 GENOTYPE_SYMBOLS = ("svt_genotype_default_params", "svt_genotype_batch", "svt_genotype_device", "svt_genotype_calls")
 # include/svtrek_callseq.h: likewise (Engine.call_consensus raises on a backend without it)
@@ -308,6 +322,9 @@ def bind_abi(lib: C.CDLL) -> C.CDLL:
     if has_rearr(lib):
         lib.svt_call_rearr_stats_get.argtypes = [P, C.POINTER(SvtCallRearrStats)]
         lib.svt_call_rearr_stats_get.restype = C.c_int32
+    if has_bnd(lib):
+        lib.svt_call_bnd_stats_get.argtypes = [P, C.POINTER(SvtCallBndStats)]
+        lib.svt_call_bnd_stats_get.restype = C.c_int32
     if has_genotype(lib):
         lib.svt_genotype_default_params.argtypes = [P, C.POINTER(SvtGtParams)]
         lib.svt_genotype_default_params.restype = None
@@ -342,6 +359,11 @@ def has_junctions(lib: C.CDLL) -> bool:
 def has_rearr(lib: C.CDLL) -> bool:
     """Does the library export include/svtrek_rearr.h's entry point (svt_call_params.rearr)?"""
     return has_junctions(lib) and all(hasattr(lib, name) for name in REARR_SYMBOLS)
+
+
+def has_bnd(lib: C.CDLL) -> bool:
+    """Does the library export include/svtrek_bnd.h's entry point (svt_call_params.bnd)?"""
+    return has_junctions(lib) and all(hasattr(lib, name) for name in BND_SYMBOLS)
 
 
 def has_call_merge(lib: C.CDLL) -> bool:

@@ -23,7 +23,7 @@ INC = os.path.join(ROOT, "include")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("SVT_OFFLOAD_ARCH", "gfx950")
 PUBLIC_HDRS = [os.path.join(INC, f) for f in ("svtrek_gpu.h", "svtrek_evidence.h", "svtrek_call.h", "svtrek_genotype.h",
-                                              "svtrek_callseq.h", "svtrek_junction.h", "svtrek_rearr.h")]
+                                              "svtrek_callseq.h", "svtrek_junction.h", "svtrek_rearr.h", "svtrek_bnd.h")]
 
 
 def _run(cmd: list[str], cwd: str | None = None) -> None:

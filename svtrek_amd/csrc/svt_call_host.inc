@@ -32,6 +32,8 @@ CallView call_view(svt_ctx *c, bool merged, bool junction) {
 
 svt_status junction_build(svt_ctx *c, uint32_t gap, uint32_t min_len);   // svt_junction_host.inc
 svt_status rearr_build(svt_ctx *c);                                      // svt_rearr_host.inc
+svt_status bnd_build(svt_ctx *c);                                        // svt_bnd_host.inc
+svt_status bnd_stage(svt_ctx *c, const svt_call_params *p, uint32_t n_other, uint64_t *total);
 
 // The first scan of a loaded pileup (of a merged index): the segments (the buckets' extents are those
 // of the load for every rebuild) and the scratch that depends on the event counts alone.
@@ -259,6 +261,7 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
         k.last.merged = merged;
         k.last.junction = junction;
         k.last.rearr = rearr;
+        k.last.bnd = p->bnd;   // (and its table has no record)
         return SVT_OK;
     }
     svt_status s = order_on(c, nullptr);   // after every launch already issued (svt_reindex rebuilds the buckets)
@@ -275,18 +278,27 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
         if ((s = rearr_build(c))) return s;
         k.last.rearr_stats = k.rr.stats;
     }
+    if (p->bnd) {   // (likewise: once per pileup and table; svt_bnd_host.inc)
+        if ((s = bnd_build(c))) return s;
+        k.last.bnd_stats = k.bn.stats;
+        k.last.call_stats.events += k.bn.stats.items;
+        k.last.call_stats.skipped += k.bn.stats.skipped;
+    }
     k.last.merged = merged;
     k.last.junction = junction;
     k.last.rearr = rearr;
+    k.last.bnd = p->bnd;
+    const bool bnd = p->bnd && k.bn.n_items != 0;   // the BND stage runs: the scan's other calls go to k.bn.d_other first
     const CallView v = call_view(c, merged, junction);
-    const uint64_t N = base_types ? v.n_s + v.n_i : 0;   // (no DEL / INS bit: a rearrangement-only scan)
-    if (N == 0 && !rearr) return SVT_OK;
+    const uint64_t N = base_types ? v.n_s + v.n_i : 0;   // (no DEL / INS bit: a rearrangement- or breakend-only scan)
+    if (N == 0 && !rearr && !bnd) return SVT_OK;
     DevEvent e0, e1;
     HIP_TRY(c, e0.create());
     HIP_TRY(c, e1.create());
     HIP_TRY(c, hipEventRecord(e0, nullptr));
     CallPass ps{}, pr{};   // the pass over v, the second pass
-    if (N && (s = call_pass(c, p, v, p->types, false, rearr ? k.rr.d_a : k.d_calls, &ps))) return s;
+    DevBuf<svt_call> &others = bnd ? k.bn.d_other : k.d_calls;   // where the calls of the passes end up
+    if (N && (s = call_pass(c, p, v, p->types, false, rearr ? k.rr.d_a : others, &ps))) return s;
     uint64_t total = ps.npick;
     bool second = false;
     if (rearr) {   // the second pass, over the rearrangement index, and the merge of the two lists (svt_rearr.inc)
@@ -298,11 +310,14 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
         total += pr.npick;
         if (total > 0x7fffffffull) return fail(c, SVT_ESTATE, "%s", "svt_call_scan: more than 2^31 - 1 calls are not supported");
         if (total) {
-            if ((s = nomem(c, k.d_calls.reserve(total), CALL_MEM))) return s;
+            if ((s = nomem(c, others.reserve(total), CALL_MEM))) return s;
             hipLaunchKernelGGL(rearr_merge_kernel, dim3((unsigned)((total + 255u) / 256u)), dim3(256), 0, nullptr, k.rr.d_a.get(),
-                               ps.npick, k.rr.d_b.get(), pr.npick, k.d_calls.get());
+                               ps.npick, k.rr.d_b.get(), pr.npick, others.get());
             HIP_TRY(c, hipGetLastError());
         }
+    }
+    if (bnd) {   // one more stage behind whatever the passes did: its own scratch, none of k.d_ctr / k.d_sctr (svt_bnd_host.inc)
+        if ((s = bnd_stage(c, p, (uint32_t)total, &total))) return s;
     }
     HIP_TRY(c, hipEventRecord(e1, nullptr));
     HIP_TRY(c, hipEventSynchronize(e1));
@@ -312,7 +327,7 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
         k.last.rearr_stats.skipped = skipped;
         k.last.rearr_stats.clusters = pr.ncl;
         k.last.rearr_stats.calls = pr.npick;
-    } else if (!rearr && (s = call_pass_stats(c, ps))) {
+    } else if (!rearr && N && (s = call_pass_stats(c, ps))) {
         return s;
     }
     float ms = 0.f;
@@ -336,13 +351,15 @@ void svt_call_default_params(const svt_ctx *c, svt_call_params *out) {
     out->merge_min = 20;
     out->junctions = 0;
     out->rearr = 0;
+    out->bnd = 0;
 }
 
 svt_status svt_call_scan(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) {
     if (!c) return SVT_EINVAL;
     if (!p || !n_calls) return fail(c, SVT_EINVAL, "%s", "null params/n_calls");
     if (p->rearr & ~((1u << SVT_DUP) | (1u << SVT_INV))) return fail(c, SVT_EINVAL, "%s", "svt_call_scan: rearr is a mask of the DUP and INV bits");
-    if (p->link < 0 || p->link > (1 << 20) || p->min_support < 1 || (!(p->types & ((1u << SVT_INS) | (1u << SVT_DEL))) && !p->rearr))
+    if (p->bnd > 1u) return fail(c, SVT_EINVAL, "%s", "svt_call_scan: bnd is 0 or 1");
+    if (p->link < 0 || p->link > (1 << 20) || p->min_support < 1 || (!(p->types & ((1u << SVT_INS) | (1u << SVT_DEL))) && !p->rearr && !p->bnd))
         return fail(c, SVT_EINVAL, "%s", "svt_call_scan: link in [0, 2^20], min_support >= 1 and a type bit of DEL / INS");
     if (p->len_permille > 1000u) return fail(c, SVT_EINVAL, "%s", "svt_call_scan: len_permille in [0, 1000]");
     if (p->merge_gap > (1u << 20) || (p->merge_gap != 0u && (p->merge_min < 1u || p->merge_min > (uint32_t)SV_MIN_LENGTH)))
@@ -353,6 +370,10 @@ svt_status svt_call_scan(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls
         return fail(c, SVT_ESTATE, "%s", "svt_call_scan: junctions = 1 without svt_load_junctions for the loaded pileup");
     if (p->rearr && !c->call.jn.loaded)
         return fail(c, SVT_ESTATE, "%s", "svt_call_scan: rearr != 0 without svt_load_junctions for the loaded pileup");
+    if (p->bnd && !c->call.jn.loaded)
+        return fail(c, SVT_ESTATE, "%s", "svt_call_scan: bnd = 1 without svt_load_junctions for the loaded pileup");
+    if (p->bnd && (int64_t)c->n_targets >= (int64_t)(1 << 30) - 1)
+        return fail(c, SVT_ESTATE, "%s", "svt_call_scan: bnd = 1 with 2^30 - 1 targets or more is not supported");
     if (c->n_reads != 0 && !c->bk.ready)
         return fail(c, SVT_ESTATE, "%s",
                     "svt_call_scan needs the value buckets (not built: SVTREK_INDEX=lists, or a pileup past 2^32 events)");

@@ -129,6 +129,8 @@ svt_status svt_call_consensus(svt_ctx *c, const svt_poa_params *p, uint64_t firs
     if (!c->insseq_loaded) return fail(c, SVT_ESTATE, "%s", "svt_load_insseq not called");
     if (c->call.last.rearr)
         return fail(c, SVT_ESTATE, "%s", "svt_call_consensus: the last scan called rearrangements (rearr != 0): scan without them for inserted bases");
+    if (c->call.last.bnd)
+        return fail(c, SVT_ESTATE, "%s", "svt_call_consensus: the last scan called breakends (bnd = 1): scan without them for inserted bases");
     if (first > c->call.n_calls || n > c->call.n_calls - first)
         return fail(c, SVT_EINVAL, "%s", "svt_call_consensus: range past the scanned calls");
     if (n == 0) return SVT_OK;

@@ -186,11 +186,34 @@ struct CallScratch {
         DevBuf<svt_call> d_a, d_b;        // the scan's two sorted lists before their merge: DEL / INS, INV / DUP
         svt_call_rearr_stats stats{};
     } rr;
+    // the BND item list (bnd = 1; svt_bnd.inc, svt_bnd_host.inc): no buckets, one list in (class, x) order;
+    // rebuilt when the table changes.  The scratch of its scans lives and dies with it.
+    struct Bnd {
+        bool built = false;
+        uint64_t n_items = 0;             // kept items
+        DevBuf<unsigned long long> d_cls, d_xy;   // [n_items] tid_lo << 33 | tid_hi << 2 | o;  x << 32 | y
+        svt_call_bnd_stats stats{};       // of the build: items, skipped, classes, build_ms
+        // per scan
+        DevBuf<uint32_t> d_cid, d_gid;    // [n_items] head marks, then start cluster / group numbers (1-based)
+        DevBuf<unsigned long long> d_key, d_key2, d_ccls;   // cluster << 30 | y, as built / by y; [clusters] class words
+        DevBuf<uint32_t> d_x, d_x2;       // x beside the keys
+        DevBuf<BndAcc> d_acc;             // [groups]
+        DevBuf<uint8_t> d_flag;           // per group: a call
+        DevBuf<uint32_t> d_pick, d_ctr;   // the called groups; [0..2) the build's counters, [2] the picked calls
+        DevBuf<svt_call> d_raw, d_sorted; // the BND calls as emitted / in order
+        DevBuf<unsigned long long> d_k, d_k2;   // the order keys of the calls
+        DevBuf<uint32_t> d_idx, d_idx2;   // the call indices they carry
+        DevBuf<svt_call> d_other;         // the scan's other calls before the merge with d_sorted
+        // Not built, nothing allocated.  The caller synchronises first where a launch may still read it.
+        void drop() { *this = Bnd{}; }
+    } bn;
     // What the last scan ran on (svt_genotype_calls, svt_call_consensus) and its stats: reset when a scan
     // begins, the three set once the index the scan runs on is built.
     struct Last {
         bool merged = false, junction = false;
         uint32_t rearr = 0;               // the scan's rearr mask
+        uint32_t bnd = 0;                 // the scan's bnd
+        svt_call_bnd_stats bnd_stats{};   // (all zero after bnd = 0)
         svt_call_stats call_stats{};
         svt_call_split_stats split_stats{};
         svt_call_merge_stats merge_stats{};         // (all zero after merge_gap = 0)

@@ -38,6 +38,8 @@
 //                         union index of svt_call_scan's junctions (host side: svt_junction_host.inc)
 //   svt_rearr.inc         DUP / INV items from the same table in an index of their own, the scan's second
 //                         pass over it and the merge of the two call lists (host side: svt_rearr_host.inc)
+//   svt_bnd.inc           translocation breakends from the same table: an item list without buckets, radix
+//                         sorts by (class, x) and by y, the BND calls (host side: svt_bnd_host.inc)
 //   svt_index.inc, svt_index2.inc, svt_bucket_build.inc   the index builds (span lists, value buckets)
 //   svt_poa.inc, svt_poa_host.inc      allele consensus (POA): kernels, slot pools and poa_run
 //   svt_callseq.inc       consensus sequence of discovered INS calls: item table and support gather
@@ -75,10 +77,11 @@
 #include "../../include/svtrek_callseq.h"
 #include "../../include/svtrek_junction.h"
 #include "../../include/svtrek_rearr.h"
+#include "../../include/svtrek_bnd.h"
 #include "svt_bamrec.h"
 #include "svt_loadprep.h"
 
-#define SVT_VERSION "svtrek_amd 0.33.0 (gfx950, value-bucketed event index filed by a lane-per-read walk with a 9-B LDS stage, band + prefix-max facts, packed span walk fed by readlane, lane vote on 64 windows a wave, BGZF inflate + BAM decode, DEL/INS discovery from the value buckets, genotypes from the events' own read extents, consensus sequence of INS calls, a read's fragmented D / I ops joined before calling, DEL/INS items and DUP/INV calls from split alignments)"
+#define SVT_VERSION "svtrek_amd 0.34.0 (gfx950, value-bucketed event index filed by a lane-per-read walk with a 9-B LDS stage, band + prefix-max facts, packed span walk fed by readlane, lane vote on 64 windows a wave, BGZF inflate + BAM decode, DEL/INS discovery from the value buckets, genotypes from the events' own read extents, consensus sequence of INS calls, a read's fragmented D / I ops joined before calling, DEL/INS items, DUP/INV calls and translocation breakends from split alignments)"
 
 namespace {
 
@@ -211,6 +214,7 @@ constexpr int LV_WMAX = 1023;   // band half-width for 16-bit offsets and prefix
 #include "svt_callmerge.inc"
 #include "svt_junction.inc"
 #include "svt_rearr.inc"
+#include "svt_bnd.inc"
 #include "svt_poa.inc"
 #include "svt_callseq.inc"
 #include "svt_bam.inc"
@@ -875,6 +879,7 @@ svt_status svt_evidence_batch(svt_ctx *c, const svt_locus *loci, const svt_resul
 #include "svt_call_host.inc"
 #include "svt_junction_host.inc"
 #include "svt_rearr_host.inc"
+#include "svt_bnd_host.inc"
 
 // ---- include/svtrek_genotype.h
 #include "svt_genotype_host.inc"

@@ -95,9 +95,10 @@ svt_status junction_load_1(svt_ctx *c, const svt_junction_view *v) {
     HIP_TRY(c, hipMemcpy(d_toff, n ? v->off : &zero, (size_t)(n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
     if (rows) HIP_TRY(c, hipMemcpy(d_tseg, v->seg, (size_t)rows * sizeof(svt_junction_seg), hipMemcpyHostToDevice));
     CallScratch::Rearr &rr = c->call.rr;
-    if (j.built || rr.built) HIP_TRY(c, hipDeviceSynchronize());
-    j.drop();    // the union and the rearrangement index of the table before: gone with it
+    if (j.built || rr.built || c->call.bn.built) HIP_TRY(c, hipDeviceSynchronize());
+    j.drop();    // the union, the rearrangement index and the breakend list of the table before: gone with it
     rr.drop();
+    c->call.bn.drop();
     j.d_toff = std::move(d_toff);
     j.d_tseg = std::move(d_tseg);
     j.n = n;

@@ -21,6 +21,7 @@
 #include "svtrek_callseq.h"
 #include "svtrek_junction.h"
 #include "svtrek_rearr.h"
+#include "svtrek_bnd.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -173,6 +174,17 @@ char *svth_format_calls_seq(const svt_call *calls, const svt_gt *gts, const svt_
 char *svth_format_calls_rearr(const svt_call *calls, const svt_gt *gts, const svt_poa_result *cons, const uint8_t *bases,
                               int32_t cap, size_t n, const char *const *names, size_t n_names, const char *sample, int header,
                               int threads, uint32_t rearr, size_t *len);
+/* The same for a scan that asked for breakends too (include/svtrek_bnd.h), bnd = the scan's svt_call_params.bnd: a call
+ * of type SVT_BND is written as ONE record,
+ *   name  pos  svtrek.BND.<k>  N  ALT  .  PASS  SVTYPE=BND;CHR2=mate;POS2=end;SUPPORT=c;DEPTH=d;XRANGE=lo,hi;X2RANGE=lo,hi
+ * with ALT by o = SVT_CALL_MATE_ORIENT: 0 N]mate:end], 1 N[mate:end[, 2 ]mate:end]N, 3 [mate:end[N (s_lo = 0 puts the base
+ * first, s_hi = 1 uses '['), mate named by the rule of CHROM, positions printed as the record holds them, k its rank among
+ * the BND calls, X2RANGE = len_lo, len_hi, and ./. in the genotype column, if any.  There is no END key.  The header gains the
+ * ##INFO lines of CHR2, POS2 and X2RANGE behind LENRANGE and no ##ALT line.  bnd == 0: svth_format_calls_rearr, byte for
+ * byte, which forwards here. */
+char *svth_format_calls_bnd(const svt_call *calls, const svt_gt *gts, const svt_poa_result *cons, const uint8_t *bases,
+                            int32_t cap, size_t n, const char *const *names, size_t n_names, const char *sample, int header,
+                            int threads, uint32_t rearr, uint32_t bnd, size_t *len);
 void  svth_free(void *p);
 
 /* A11: stdout text for one refined record; returns bytes written (0 = prints nothing:

@@ -44,6 +44,8 @@ extern "C" __typeof__(svt_load_junctions) svt_load_junctions __attribute__((weak
 extern "C" __typeof__(svt_call_junction_stats_get) svt_call_junction_stats_get __attribute__((weak));
 // include/svtrek_rearr.h likewise (`svtrek call --rearrangements`)
 extern "C" __typeof__(svt_call_rearr_stats_get) svt_call_rearr_stats_get __attribute__((weak));
+// include/svtrek_bnd.h likewise (`svtrek call --breakends`)
+extern "C" __typeof__(svt_call_bnd_stats_get) svt_call_bnd_stats_get __attribute__((weak));
 // include/svtrek_genotype.h likewise (`svtrek call --genotype`)
 extern "C" __typeof__(svt_genotype_default_params) svt_genotype_default_params __attribute__((weak));
 extern "C" __typeof__(svt_genotype_calls) svt_genotype_calls __attribute__((weak));
@@ -87,6 +89,10 @@ void call_usage() {
     printf("                                      a second alignment upstream of the first (DUP) or on the other strand (INV);\n");
     printf("                                      <DUP> / <INV> records in the same VCF, never genotyped (./.); with or without\n");
     printf("                                      --split-reads; not with --ins-seq [Default: none]\n");
+    printf("    --breakends                       Also call translocations from split alignments: a second alignment on\n");
+    printf("                                      another contig; one BND record a breakend pair (CHR2 / POS2) in the same\n");
+    printf("                                      VCF, never genotyped (./.); with or without --split-reads and\n");
+    printf("                                      --rearrangements; not with --ins-seq [Default: none]\n");
     printf("    --genotype                        Genotype every call: a FORMAT and a sample column with GT:GQ:DR:DV:PL\n");
     printf("                                      [Default: a sites-only VCF]\n");
     printf("    --flank <num>                     Bases a read must cover on both sides of a call to count [Default: 50]\n");
@@ -593,7 +599,7 @@ int audit(int argc, char **argv) {
 int call_mode(int argc, char **argv) {
     const char *bam_path = nullptr, *out_path = nullptr, *sample = "SAMPLE";
     int threads = THREADS, verbose = 0, device = 0, gpu_inflate = -1, link = -1, min_support = -1, genotype = 0, flank = -1, len_permille = 0;
-    int ins_seq = 0, ins_cap = 4096, merge_gap = 0, merge_min = -1, split_reads = 0;
+    int ins_seq = 0, ins_cap = 4096, merge_gap = 0, merge_min = -1, split_reads = 0, breakends = 0;
     uint32_t types = (1u << SVT_INS) | (1u << SVT_DEL), rearr = 0;
     static const option opts[] = {
         {"bam", required_argument, nullptr, 1}, {"output", required_argument, nullptr, 3},
@@ -605,7 +611,7 @@ int call_mode(int argc, char **argv) {
         {"len-permille", required_argument, nullptr, 36}, {"ins-seq", no_argument, nullptr, 37},
         {"ins-seq-cap", required_argument, nullptr, 38}, {"merge-gap", required_argument, nullptr, 39},
         {"merge-min", required_argument, nullptr, 40}, {"split-reads", no_argument, nullptr, 41},
-        {"rearrangements", required_argument, nullptr, 42}, {nullptr, 0, nullptr, 0}};
+        {"rearrangements", required_argument, nullptr, 42}, {"breakends", no_argument, nullptr, 43}, {nullptr, 0, nullptr, 0}};
     int opt, li;
     while ((opt = getopt_long(argc, argv, "b:o:t:h", opts, &li)) != -1) {
         switch (opt) {
@@ -659,6 +665,7 @@ int call_mode(int argc, char **argv) {
             }
             break;
         }
+        case 43: breakends = 1; break;
         default:
             printf("[ERROR] Option %d is invalid.\n", opt);
             call_usage();
@@ -677,6 +684,14 @@ int call_mode(int argc, char **argv) {
     }
     if (rearr && ins_seq) {   // (before any ingest: svt_call_consensus refuses the calls of such a scan)
         fprintf(stderr, "[ERROR] --rearrangements cannot be combined with --ins-seq: scan without them for the consensus sequences\n");
+        return 1;
+    }
+    if (breakends && ins_seq) {   // (likewise)
+        fprintf(stderr, "[ERROR] --breakends cannot be combined with --ins-seq: scan without them for the consensus sequences\n");
+        return 1;
+    }
+    if (breakends && (!svt_load_junctions || !svt_call_bnd_stats_get)) {
+        fprintf(stderr, "[ERROR] breakends: not supported by this backend\n");
         return 1;
     }
     if (rearr && (!svt_load_junctions || !svt_call_rearr_stats_get)) {
@@ -719,7 +734,7 @@ int call_mode(int argc, char **argv) {
     });
     char err[512];
     const svth_inflater dev_inf{device_inflate, device_host_alloc, device_host_free, &dinf, (size_t)1024 << 20};
-    svth_bam *bam = (ins_seq ? svth_bam_read_seq : split_reads || rearr ? svth_bam_read_sa : svth_bam_read_ex)(bam_path, threads, -1, 0, -1, 0,
+    svth_bam *bam = (ins_seq ? svth_bam_read_seq : split_reads || rearr || breakends ? svth_bam_read_sa : svth_bam_read_ex)(bam_path, threads, -1, 0, -1, 0,
                                                                     gpu_inflate ? &dev_inf : nullptr, err, sizeof err);
     ot.join();
     auto done = [&](int rc) {
@@ -749,15 +764,16 @@ int call_mode(int argc, char **argv) {
         if (!svth_bam_insseq(bam, &sv)) { fprintf(stderr, "[ERROR] --ins-seq: the ingest kept no sequences\n"); return done(1); }
         s = svt_load_insseq(ctx, &sv);
     }
-    if (!s && (split_reads || rearr)) {   // the segment table the ingest kept (a backend without it is refused above)
+    if (!s && (split_reads || rearr || breakends)) {   // the segment table the ingest kept (a backend without it is refused above)
         svt_junction_view jv{};
         if (!svth_bam_junctions(bam, &jv)) {
-            fprintf(stderr, "[ERROR] %s: the ingest kept no segment table\n", split_reads ? "--split-reads" : "--rearrangements");
+            fprintf(stderr, "[ERROR] %s: the ingest kept no segment table\n", split_reads ? "--split-reads" : rearr ? "--rearrangements" : "--breakends");
             return done(1);
         }
         s = svt_load_junctions(ctx, &jv);
         if (split_reads) cp.junctions = 1;
         if (rearr) cp.rearr = rearr;   // (a backend without them is refused above and never sees the field)
+        if (breakends) cp.bnd = 1;     // (likewise)
     }
     const double t_load = now_s();
     if (!s) s = svt_call_scan(ctx, &cp, &n);
@@ -792,9 +808,9 @@ int call_mode(int argc, char **argv) {
     for (size_t t = 0; t < names.size(); t++) names[t] = svth_bam_target_name(bam, (int32_t)t);
     size_t olen = 0;
     static const svt_gt no_gt{};   // (no calls: the header still has to say FORMAT)
-    char *text = svth_format_calls_rearr(calls.data(), genotype ? (gts.empty() ? &no_gt : gts.data()) : nullptr,
-                                         ins_seq ? cons.data() : nullptr, ins_seq ? cons_bases.data() : nullptr, ins_cap, calls.size(),
-                                         names.data(), names.size(), sample, 1, threads, rearr, &olen);
+    char *text = svth_format_calls_bnd(calls.data(), genotype ? (gts.empty() ? &no_gt : gts.data()) : nullptr,
+                                       ins_seq ? cons.data() : nullptr, ins_seq ? cons_bases.data() : nullptr, ins_cap, calls.size(),
+                                       names.data(), names.size(), sample, 1, threads, rearr, (uint32_t)breakends, &olen);
     if (!text) { fprintf(stderr, "[ERROR] out of host memory\n"); return done(1); }
     FILE *of = out_path ? fopen(out_path, "wb") : stdout;
     bool ok = of && fwrite(text, 1, olen, of) == olen;
@@ -838,6 +854,11 @@ int call_mode(int argc, char **argv) {
                         "build %.3f ms\n", rearr & (1u << SVT_DUP) ? "DUP" : "", rearr == ((1u << SVT_DUP) | (1u << SVT_INV)) ? "," : "",
                 rearr & (1u << SVT_INV) ? "INV" : "", (unsigned long long)rs.dup_items, (unsigned long long)rs.inv_items,
                 (unsigned long long)rs.skipped, (unsigned long long)rs.clusters, (unsigned long long)rs.calls, rs.build_ms);
+    svt_call_bnd_stats bs{};
+    if (verbose && breakends && !svt_call_bnd_stats_get(ctx, &bs))
+        fprintf(stderr, "[svtrek_amd] call: breakends  items %llu  skipped %llu  classes %llu  clusters %llu  groups %llu  calls %llu  "
+                        "build %.3f ms\n", (unsigned long long)bs.items, (unsigned long long)bs.skipped, (unsigned long long)bs.classes,
+                (unsigned long long)bs.clusters, (unsigned long long)bs.groups, (unsigned long long)bs.calls, bs.build_ms);
     return done(0);
 }
 

@@ -247,30 +247,38 @@ char *svth_format_calls_seq(const svt_call *c, const svt_gt *gts, const svt_poa_
 char *svth_format_calls_rearr(const svt_call *c, const svt_gt *gts, const svt_poa_result *cons, const uint8_t *bases, int32_t cap,
                               size_t n, const char *const *names, size_t n_names, const char *sample, int header, int threads,
                               uint32_t rearr, size_t *len) {
+    return svth_format_calls_bnd(c, gts, cons, bases, cap, n, names, n_names, sample, header, threads, rearr, 0u, len);
+}
+
+char *svth_format_calls_bnd(const svt_call *c, const svt_gt *gts, const svt_poa_result *cons, const uint8_t *bases, int32_t cap,
+                            size_t n, const char *const *names, size_t n_names, const char *sample, int header, int threads,
+                            uint32_t rearr, uint32_t bnd, size_t *len) {
     const int T = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(threads, 1), n / 16384 + 1));
-    // a call's class: 0 DEL, 1 INS (and, with rearr == 0, every other type, as ever), 2 DUP, 3 INV
-    auto cls = [rearr](const svt_call &x) {
+    // a call's class: 0 DEL, 1 INS (and every type not asked for, as ever), 2 DUP, 3 INV (rearr != 0), 4 BND (bnd != 0)
+    auto cls = [rearr, bnd](const svt_call &x) {
         if (x.type == SVT_DEL) return 0;
         if (rearr && x.type == SVT_DUP) return 2;
         if (rearr && x.type == SVT_INV) return 3;
+        if (bnd && x.type == SVT_BND) return 4;
         return 1;
     };
-    static const char *const TY[4] = {"DEL", "INS", "DUP", "INV"};
+    constexpr int NC = 5;
+    static const char *const TY[NC] = {"DEL", "INS", "DUP", "INV", "BND"};
     // the ID's k: the call's rank among the calls of its type (1-based)
-    std::vector<size_t> first_k((size_t)T * 4 + 4, 0);
+    std::vector<size_t> first_k((size_t)T * NC + NC, 0);
     for (int t = 0; t < T; t++) {
-        size_t cnt[4] = {0, 0, 0, 0};
+        size_t cnt[NC] = {0, 0, 0, 0, 0};
         for (size_t k = n * (size_t)t / (size_t)T, e = n * (size_t)(t + 1) / (size_t)T; k < e; k++) cnt[cls(c[k])]++;
-        for (int q = 0; q < 4; q++) first_k[4 * (size_t)t + 4 + (size_t)q] = first_k[4 * (size_t)t + (size_t)q] + cnt[q];
+        for (int q = 0; q < NC; q++) first_k[NC * (size_t)t + NC + (size_t)q] = first_k[NC * (size_t)t + (size_t)q] + cnt[q];
     }
     std::vector<std::string> part((size_t)T);
     run_parts(T, [&](int t) {
         std::string &o = part[(size_t)t];
         const size_t b = n * (size_t)t / (size_t)T, e = n * (size_t)(t + 1) / (size_t)T;
         o.reserve((e - b) * 160);
-        size_t rank[4];
-        for (int q = 0; q < 4; q++) rank[q] = first_k[4 * (size_t)t + (size_t)q];
-        char buf[320], num[16];
+        size_t rank[NC];
+        for (int q = 0; q < NC; q++) rank[q] = first_k[NC * (size_t)t + (size_t)q];
+        char buf[320], num[16], num2[16];
         for (size_t k = b; k < e; k++) {
             const svt_call &x = c[k];
             const int cl = cls(x);
@@ -282,6 +290,28 @@ char *svth_format_calls_rearr(const svt_call *c, const svt_gt *gts, const svt_po
             o += name;
             int m = snprintf(buf, sizeof buf, "\t%u\tsvtrek.%s.%zu\tN\t", x.pos, ty, ++rank[cl]);
             o.append(buf, (size_t)m);
+            if (cl == 4) {   // one record a breakend pair: ALT by o = 2 * s_lo + s_hi, the partner named as CHROM is
+                const int32_t mc = SVT_CALL_MATE_CHROM(x);
+                const uint32_t ori = SVT_CALL_MATE_ORIENT(x);
+                const char *mate = num2;
+                if (mc >= 1 && (size_t)mc <= n_names && names && names[mc - 1]) mate = names[mc - 1];
+                else snprintf(num2, sizeof num2, "%d", mc);
+                const char br = ori & 1u ? '[' : ']';
+                if (!(ori & 2u)) o += 'N';
+                o += br;
+                o += mate;
+                m = snprintf(buf, sizeof buf, ":%u%c", x.end, br);
+                o.append(buf, (size_t)m);
+                if (ori & 2u) o += 'N';
+                o += "\t.\tPASS\tSVTYPE=BND;CHR2=";
+                o += mate;
+                m = snprintf(buf, sizeof buf, ";POS2=%u;SUPPORT=%u;DEPTH=%u;XRANGE=%u,%u;X2RANGE=%u,%u", x.end, x.support, x.depth, x.x_lo,
+                             x.x_hi, x.len_lo, x.len_hi);
+                o.append(buf, (size_t)m);
+                if (gts) o += "\tGT:GQ:DR:DV:PL\t./.:0:0:0:0,0,0";   // (never genotyped)
+                o += '\n';
+                continue;
+            }
             const bool ins_cons = cons && cl == 1;
             if (ins_cons && cons[k].len >= 1 && cons[k].len <= cap && bases) {   // ALT: the base before + the consensus
                 const uint8_t *q = bases + k * (size_t)cap;
@@ -325,6 +355,10 @@ char *svth_format_calls_rearr(const svt_call *c, const svt_gt *gts, const svt_po
                 "##INFO=<ID=DEPTH,Number=1,Type=Integer,Description=\"Reads covering POS\">\n"
                 "##INFO=<ID=XRANGE,Number=2,Type=Integer,Description=\"Smallest and largest start of the supporting ops\">\n"
                 "##INFO=<ID=LENRANGE,Number=2,Type=Integer,Description=\"Smallest and largest length of the supporting ops\">\n";
+        if (bnd)
+            head += "##INFO=<ID=CHR2,Number=1,Type=String,Description=\"BND: the partner breakend's contig\">\n"
+                    "##INFO=<ID=POS2,Number=1,Type=Integer,Description=\"BND: rounded mean of the partner breakend's position\">\n"
+                    "##INFO=<ID=X2RANGE,Number=2,Type=Integer,Description=\"BND: smallest and largest partner position of the supporting reads\">\n";
         if (cons)
             head += "##INFO=<ID=CONSLEN,Number=1,Type=Integer,Description=\"INS: length of the consensus inserted sequence (0: none)\">\n"
                     "##INFO=<ID=CONSREADS,Number=1,Type=Integer,Description=\"INS: inserted sequences fused into the consensus\">\n";

@@ -14,9 +14,9 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._lib import (CALL_DTYPE, EVIDENCE_DTYPE, GT_DTYPE, GT_SITE_DTYPE, JUNCTION_SEG_DTYPE, LOCUS_DTYPE, POA_RESULT_DTYPE, RESULT_DTYPE,
-                   STATUS_NAMES, SVT_DEL, SVT_DUP, SVT_EINVAL, SVT_INS, SVT_INV, SVT_NA, SW_QUERY_DTYPE, SW_WINDOW_DTYPE, SvtCallConsensusStats, SvtCallRearrStats,
+                   STATUS_NAMES, SVT_DEL, SVT_DUP, SVT_EINVAL, SVT_INS, SVT_INV, SVT_NA, SW_QUERY_DTYPE, SW_WINDOW_DTYPE, SvtCallBndStats, SvtCallConsensusStats, SvtCallRearrStats,
                    SvtCallJunctionStats, SvtCallMergeStats, SvtCallParams, SvtCallSplitStats, SvtCallStats, SvtGtParams, SvtInsseqView, SvtJunctionView, SvtLoadStats, SvtParams, SvtPoaParams,
-                   SvtWork, has_call, has_call_merge, has_call_split, has_callseq, has_evidence, has_genotype, has_junctions, has_rearr, load_engine, ptr)
+                   SvtWork, has_call, has_call_merge, has_call_split, has_callseq, has_evidence, has_bnd, has_genotype, has_junctions, has_rearr, load_engine, ptr)
 from .pileup import Pileup
 
 # params.h:27-32
@@ -160,6 +160,12 @@ class Engine:
             raise SvtError(SVT_EINVAL, "this backend does not export svt_call_rearr_stats_get (include/svtrek_rearr.h): "
                                        "DUP / INV calls need the HIP engine 0.33.0 or later")
 
+    def _need_bnd(self) -> None:
+        self._need_junctions()
+        if not has_bnd(self.lib):
+            raise SvtError(SVT_EINVAL, "this backend does not export svt_call_bnd_stats_get (include/svtrek_bnd.h): "
+                                       "BND calls need the HIP engine 0.34.0 or later")
+
     def load_junctions(self, read, off, seg) -> None:
         """The segment table of the loaded pileup's records that carry an SA tag (svt_load_junctions,
         include/svtrek_junction.h): read uint64 [n] ascending pileup read indices, off uint64 [n + 1], seg
@@ -178,7 +184,7 @@ class Engine:
 
     def call(self, link: int | None = None, min_support: int | None = None, types=("DEL", "INS"),
              len_permille: int | None = None, merge_gap: int | None = None, merge_min: int | None = None,
-             junctions: bool = False, rearrangements=()) -> np.ndarray:
+             junctions: bool = False, rearrangements=(), breakends: bool = False) -> np.ndarray:
         """Cluster the pileup's D > 50 / I >= 50 ops by start (svt_call_scan): CALL_DTYPE records in
         (chrom, pos, type, len) order.  link: the largest gap between neighbouring starts of one
         cluster (default 10); min_support: the fewest ops of a call (default consensus_min_count);
@@ -190,8 +196,13 @@ class Engine:
         junctions: the DEL / INS items of split alignments (load_junctions) join the CIGAR items;
         rearrangements: "DUP" and / or "INV" (a sequence or a comma string) adds the tandem duplications /
         inversions that the split alignments of load_junctions show (include/svtrek_rearr.h) to the same
-        list; `types` keeps naming DEL / INS only and may be empty then."""
+        list; `types` keeps naming DEL / INS only and may be empty then;
+        breakends: adds the translocation breakends those split alignments show -- a next alignment on another
+        contig -- as records of type SVT_BND (include/svtrek_bnd.h: end is the partner's position, _lib.call_mate
+        reads the partner's chrom and the orientation from pad); `types` may be empty then too."""
         self._need_call()
+        if breakends:
+            self._need_bnd()
         rearr = rearr_type_bits(rearrangements)
         if rearr:
             self._need_rearr()
@@ -210,6 +221,8 @@ class Engine:
         p.types = call_type_bits(types)
         if rearr:   # (an older engine never sees the field)
             p.rearr = rearr
+        if breakends:   # (likewise)
+            p.bnd = 1
         if len_permille is not None:
             if not 0 <= int(len_permille) <= 0xffffffff:
                 raise SvtError(SVT_EINVAL, "call: len_permille in [0, 1000]")
@@ -277,6 +290,14 @@ class Engine:
         st = SvtCallRearrStats()
         self._check(self.lib.svt_call_rearr_stats_get(self._h, C.byref(st)))
         return {k: (float(getattr(st, k)) if k == "build_ms" else int(getattr(st, k))) for k, _ in SvtCallRearrStats._fields_}
+
+    def call_bnd_stats(self) -> dict:
+        """{items, skipped, classes, clusters, groups, calls, build_ms} of the last call(): all zero without
+        breakends."""
+        self._need_bnd()
+        st = SvtCallBndStats()
+        self._check(self.lib.svt_call_bnd_stats_get(self._h, C.byref(st)))
+        return {k: (float(getattr(st, k)) if k == "build_ms" else int(getattr(st, k))) for k, _ in SvtCallBndStats._fields_}
 
     # ---- consensus inserted sequence of the INS calls (include/svtrek_callseq.h)
     def _need_callseq(self) -> None:
@@ -508,7 +529,8 @@ def calls_to_loci(calls: np.ndarray) -> np.ndarray:
 
 
 def calls_to_sites(calls: np.ndarray) -> np.ndarray:
-    """CALL_DTYPE records as GT_SITE_DTYPE sites: the fields of the same names."""
+    """CALL_DTYPE records as GT_SITE_DTYPE sites: the fields of the same names (a BND call passes through as a
+    site of type SVT_BND, which no genotyper takes: the invalid record)."""
     calls = np.asarray(calls, dtype=CALL_DTYPE)
     sites = np.empty(len(calls), dtype=GT_SITE_DTYPE)
     for f in GT_SITE_DTYPE.names:

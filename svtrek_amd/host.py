@@ -44,6 +44,9 @@ def load_host() -> C.CDLL:
         L.svth_format_calls_rearr.argtypes = [P, P, P, P, C.c_int32, C.c_size_t, P, C.c_size_t, C.c_char_p, C.c_int, C.c_int,
                                               C.c_uint32, C.POINTER(C.c_size_t)]
         L.svth_format_calls_rearr.restype = P
+        L.svth_format_calls_bnd.argtypes = [P, P, P, P, C.c_int32, C.c_size_t, P, C.c_size_t, C.c_char_p, C.c_int, C.c_int,
+                                            C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]
+        L.svth_format_calls_bnd.restype = P
         L.svth_bam_read_device.argtypes = [C.c_char_p, C.c_int, P, P, P, C.c_char_p, C.c_size_t]
         L.svth_bam_read_device.restype = C.c_int
         L.svth_vcf_parse.argtypes = [C.c_char_p, C.c_size_t, C.c_int]
@@ -305,14 +308,17 @@ def format_evidence(loci: np.ndarray, res: np.ndarray, ev: np.ndarray, header: b
 
 
 def format_calls(calls: np.ndarray, names, genotypes: np.ndarray | None = None, sample: str = "SAMPLE",
-                 header: bool = True, threads: int = 4, consensus=None, rearrangements=()) -> str:
+                 header: bool = True, threads: int = 4, consensus=None, rearrangements=(),
+                 breakends: bool = False) -> str:
     """`svtrek call`'s VCF text of CALL_DTYPE records (svth_format_calls_gt); names: the BAM's reference
     names, names[chrom - 1] is a call's CHROM.  genotypes: one GT_DTYPE record per call
     (`svtrek call --genotype`: FORMAT and a column named `sample`), or None for the sites-only VCF.
     consensus: Engine.call_consensus's (res, bases) of all the calls (`svtrek call --ins-seq`,
     svth_format_calls_seq: sequence ALTs, CONSLEN and CONSREADS), or None.
     rearrangements: what the scan asked for, "DUP" and / or "INV" (`svtrek call --rearrangements`,
-    svth_format_calls_rearr: <DUP> / <INV> records and their ##ALT lines); empty: the text as before."""
+    svth_format_calls_rearr: <DUP> / <INV> records and their ##ALT lines); empty: the text as before.
+    breakends: the scan asked for them (`svtrek call --breakends`, svth_format_calls_bnd: one BND record a call
+    of type SVT_BND, the ##INFO lines of CHR2, POS2 and X2RANGE); False: the text as before."""
     from ._lib import CALL_DTYPE, GT_DTYPE, POA_RESULT_DTYPE
     from .engine import rearr_type_bits
     rearr = rearr_type_bits(rearrangements)
@@ -326,7 +332,13 @@ def format_calls(calls: np.ndarray, names, genotypes: np.ndarray | None = None, 
             raise ValueError(f"format_calls: {len(calls)} calls but {len(genotypes)} genotypes")
         gts = np.ascontiguousarray(genotypes, dtype=GT_DTYPE) if len(calls) else np.zeros(1, dtype=GT_DTYPE)
     n = C.c_size_t(0)
-    if rearr:
+    if breakends:
+        if consensus is not None:
+            raise ValueError("format_calls: no consensus sequences for a scan with breakends")
+        p = L.svth_format_calls_bnd(calls.ctypes.data if len(calls) else None, None if gts is None else gts.ctypes.data,
+                                    None, None, 0, len(calls), arr, len(enc), str(sample).encode(), int(header), threads,
+                                    rearr, 1, C.byref(n))
+    elif rearr:
         if consensus is not None:
             raise ValueError("format_calls: no consensus sequences for a scan with rearrangements")
         p = L.svth_format_calls_rearr(calls.ctypes.data if len(calls) else None, None if gts is None else gts.ctypes.data,

@@ -37,6 +37,13 @@ pair) or upstream of the first by the op's length + 100 (a duplicated pair), sca
 DUP | INV (include/svtrek_rearr.h) and adds the rearrangement statistics, the build of the rearrangement index
 (--merge-builds builds, each forced by reloading the table) with its algorithmic bytes -- 24 B per segment row
 read twice, 16 B per event written -- and the same process's plain scan next to the two-pass one.
+
+--bnd SHARE cuts that share of the supporting reads the same way and then rewrites each cut read's second
+alignment in the segment table onto the next contig (the last one's onto the first), scans with
+svt_call_params.bnd = 1 (include/svtrek_bnd.h) and adds the breakend statistics, the build of the item list
+(--merge-builds builds, each forced by reloading the table) with its algorithmic bytes -- 24 B per segment row
+read once, 16 B per item written -- and the same process's scan without bnd next to the one with it.  The cut
+limits the workload as it does for --rearr: use the same --loci.
 """
 from __future__ import annotations
 
@@ -237,6 +244,45 @@ def rearr_out(a, eng, table) -> dict:
             "plain_events": eng.call_stats()["events"], "plain_calls": eng.call_stats()["calls"]}
 
 
+def bnd_cut(a, pl):
+    """(pileup, table) with --bnd's share of the supporting reads cut and their second alignments moved to the next contig."""
+    keep, a.junctions = a.junctions, a.bnd
+    out, (read, off, seg) = junction_cut(a, pl)
+    a.junctions = keep
+    seg = seg.copy()
+    nt = len(out.tid_off) - 1
+    if nt < 2:
+        raise SystemExit("--bnd needs a workload of two contigs or more")
+    for k in range(len(read)):
+        r0, r1 = int(off[k]), int(off[k + 1])
+        if r1 - r0 == 2:
+            seg[r0 + 1]["tid"] = (int(seg[r0 + 1]["tid"]) + 1) % nt
+    return out, (read, off, seg)
+
+
+def bnd_out(a, eng, table) -> dict:
+    """The breakend statistics, the list build's time over --merge-builds builds, its bytes, the scan without bnd beside it."""
+    if not a.bnd:
+        return {}
+    bs = eng.call_bnd_stats()
+    kw = split_kw(a)
+    build = []
+    for _ in range(a.merge_builds):
+        eng.load_junctions(*table)   # the same table again: the list is dropped
+        eng.call(link=a.link, min_support=a.min_support, breakends=True, **kw)
+        build.append(eng.call_bnd_stats()["build_ms"])
+    plain = []
+    for k in range(a.warmup + a.repeat):
+        eng.call(link=a.link, min_support=a.min_support, **kw)
+        if k >= a.warmup:
+            plain.append(eng.call_stats()["scan_ms"])
+    return {"bnd": a.bnd, "bnd_stats": bs, "bnd_build_ms": round(float(np.median(build)), 4),
+            "bnd_build_ms_all": [round(x, 4) for x in build],
+            "bnd_build_alg_bytes": 24 * int(len(table[2])) + 16 * bs["items"],
+            "plain_scan_ms": round(float(np.median(plain)), 4), "plain_scan_ms_all": [round(x, 4) for x in plain],
+            "plain_events": eng.call_stats()["events"], "plain_calls": eng.call_stats()["calls"]}
+
+
 def split_out(a, eng) -> dict:
     return {"len_permille": a.len_permille, "split_stats": eng.call_split_stats()} if a.len_permille else {}
 
@@ -255,6 +301,7 @@ def main() -> None:
     ap.add_argument("--merge-builds", type=int, default=5)
     ap.add_argument("--junctions", type=float, default=0.0)
     ap.add_argument("--rearr", type=float, default=0.0)
+    ap.add_argument("--bnd", type=float, default=0.0)
     ap.add_argument("--loci", type=int, default=0)
     ap.add_argument("--hotspot", type=int, default=0)
     ap.add_argument("--hotspot-last", action="store_true")
@@ -270,12 +317,14 @@ def main() -> None:
         cfg = replace(cfg, n_loci=a.loci)
     r = sim.generate(cfg)
     table = None
-    if a.junctions and a.rearr:
-        ap.error("--junctions and --rearr each cut the workload: one at a time")
+    if (a.junctions != 0) + (a.rearr != 0) + (a.bnd != 0) > 1:
+        ap.error("--junctions, --rearr and --bnd each cut the workload: one at a time")
     if a.junctions:
         r.pileup, table = junction_cut(a, r.pileup)
     if a.rearr:
         r.pileup, table = rearr_cut(a, r.pileup)
+    if a.bnd:
+        r.pileup, table = bnd_cut(a, r.pileup)
     t_gen = time.perf_counter() - t0
     eng = Engine(Params(), device=0)
     eng.load_pileup(r.pileup)
@@ -298,7 +347,7 @@ def main() -> None:
     for k in range(a.warmup + a.repeat):
         t0 = time.perf_counter()
         calls = eng.call(link=a.link, min_support=a.min_support, **split_kw(a), **({"junctions": True} if a.junctions else {}),
-                         **({"rearrangements": ("DUP", "INV")} if a.rearr else {}))
+                         **({"rearrangements": ("DUP", "INV")} if a.rearr else {}), **({"breakends": True} if a.bnd else {}))
         t1 = time.perf_counter()
         if k >= a.warmup:
             scan_ms.append(eng.call_stats()["scan_ms"])
@@ -315,12 +364,14 @@ def main() -> None:
         last = pl.cig_off[1:].astype(np.int64)[nops > 0] - 1
         markers = int(((pl.cigar[last] & 15) == 4).sum())
     keys = st["events"] + (0 if a.merge_gap else markers)   # (the merged index holds items alone)
+    if a.bnd:   # (the breakend items are no events of the buckets: the scan's bytes below are its passes over the buckets alone)
+        keys -= eng.call_bnd_stats()["items"]
     jout = junction_out(a, eng, table)
     if jout:   # the union's build: the base events copied once, the table's rows read, the junction events written
         js = jout["junction_stats"]
         base = keys - js["del_items"] - js["ins_items"]
         jout["junction_build_alg_bytes"] = 32 * base + 24 * js["segments"] + 16 * (js["del_items"] + js["ins_items"])
-    rout = rearr_out(a, eng, table)
+    rout = {**rearr_out(a, eng, table), **bnd_out(a, eng, table)}
     alg = 16 * keys + 8 * keys + 2 * 8 * keys + 48 * st["calls"] + (48 * st["calls"] if a.rearr else 0)   # (the merge of the two lists)
     print(json.dumps({
         "metric": "svt_call_scan ms (1 GPU)", "value": round(med, 4), "unit": "ms",
