@@ -41,9 +41,9 @@ def _stale(out: str, deps: list[str]) -> bool:
 
 def _engine_deps() -> list[str]:
     """The engine's one translation unit first, then everything it includes: every csrc/*.inc,
-    svt_bamrec.h, svt_loadprep.h and the public headers."""
+    svt_bamrec.h, svt_loadprep.h, svt_jnclass.h and the public headers."""
     incs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".inc"))
-    hdrs = [os.path.join(CSRC, f) for f in ("svt_bamrec.h", "svt_loadprep.h")]
+    hdrs = [os.path.join(CSRC, f) for f in ("svt_bamrec.h", "svt_loadprep.h", "svt_jnclass.h")]
     return [os.path.join(CSRC, "svt_engine.hip")] + incs + hdrs + PUBLIC_HDRS
 
 

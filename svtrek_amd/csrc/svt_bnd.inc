@@ -1,6 +1,7 @@
 // svt_bnd.inc -- translocation breakends from split alignments (include/svtrek_bnd.h, svt_call_params.bnd;
-// included by svt_engine.hip after svt_rearr.inc, whose rearr_merge_kernel puts the BND calls behind the
-// scan's other calls; jn_next is svt_callindex.inc's, ev_depth svt_evidence.inc's, the host side is
+// included by svt_engine.hip after svt_rearr.inc; svt_call.inc's merge_lists_kernel puts the BND calls behind
+// the scan's other calls, call_store and call_copy are its too; jn_next and jn_classify -- the header's rule --
+// are svt_jnclass.h's, jn_limits svt_callindex.inc's, ev_depth svt_evidence.inc's, the host side is
 // svt_bnd_host.inc).
 //
 // No buckets: a breakend's x may be an SA row's coordinate on a contig without a single read, so the items
@@ -45,18 +46,12 @@ __global__ __launch_bounds__(64 * WPB) void bnd_kernel(BndBuild a) {
     unsigned long long cls = 0, xy = 0;
     if (k < a.n) {
         svt_junction_seg A, B;
-        if (jn_next(a.off, a.seg, k, A, B) && B.tid != A.tid) {
-            const int64_t p = A.strand ? (int64_t)A.r_beg : (int64_t)A.r_end;
-            const int64_t q = B.strand ? (int64_t)B.r_end : (int64_t)B.r_beg;
-            const uint32_t sa = A.strand, sb = 1u - B.strand;
-            const bool a_lo = A.tid < B.tid;
-            const int64_t x = a_lo ? p : q, y = a_lo ? q : p;
-            const uint64_t t_lo = (uint64_t)(uint32_t)(a_lo ? A.tid : B.tid), t_hi = (uint64_t)(uint32_t)(a_lo ? B.tid : A.tid);
-            const uint32_t o = a_lo ? 2u * sa + sb : 2u * sb + sa;
-            skip = x >= (int64_t)BND_SAT || y >= (int64_t)BND_SAT;
-            keep = !skip;
-            cls = t_lo << 33 | t_hi << 2 | o;
-            xy = (unsigned long long)x << 32 | (unsigned long long)(uint32_t)y;
+        if (jn_next(a.off, a.seg, k, A, B)) {
+            const JnItem it = jn_classify<1u << JN_BND>(A, B, jn_limits());
+            skip = it.kind == JN_BND && it.past;
+            keep = it.kind == JN_BND && !it.past;
+            cls = (uint64_t)(uint32_t)it.tid << 33 | (uint64_t)(uint32_t)it.tid_hi << 2 | it.o;
+            xy = (unsigned long long)it.x << 32 | it.y;
         }
     }
     const uint64_t mk = ballot(keep), ms = ballot(skip);   // (wave-uniform)
@@ -149,12 +144,8 @@ __global__ __launch_bounds__(64 * WPB) void bnd_emit_kernel(DevPileup pile, cons
     const uint32_t depth = ev_depth(pile, tid, pos);
     const uint32_t w[12] = {(uint32_t)SVT_BND, (uint32_t)(tid + 1), pos, end, q.cnt, depth, 0u, ~q.ny_lo, q.y_hi, ~q.nx_lo, q.x_hi,
                             mate << 2 | o};
-    const int ln = lane_id();
-    uint32_t word = 0;
-#pragma unroll
-    for (int i = 0; i < 12; i++) word = ln == i ? w[i] : word;
-    if (ln < 12) reinterpret_cast<uint32_t *>(out + g)[ln] = word;
-    if (ln == 0) {
+    call_store(out + g, w);
+    if (lane_id() == 0) {
         klo[g] = (unsigned long long)mate << 32 | (unsigned long long)o << 30 | end;
         idx[g] = g;
     }
@@ -170,10 +161,5 @@ __global__ __launch_bounds__(256) void bnd_hikey_kernel(const svt_call *raw, con
 
 __global__ __launch_bounds__(256) void bnd_gather_kernel(const svt_call *raw, const uint32_t *idx, uint32_t n, svt_call *out) {
     const uint32_t j = blockIdx.x * 256u + threadIdx.x;
-    if (j >= n) return;
-    const uint4 *src = reinterpret_cast<const uint4 *>(raw + idx[j]);
-    uint4 *dst = reinterpret_cast<uint4 *>(out + j);
-    dst[0] = src[0];
-    dst[1] = src[1];
-    dst[2] = src[2];
+    if (j < n) call_copy(out + j, raw + idx[j]);
 }

@@ -96,10 +96,10 @@ svt_status bnd_build(svt_ctx *c) {
     return SVT_OK;
 }
 
-// The BND stage of a scan, behind whatever its other passes did: the n_other calls of k.bn.d_other (in
-// order) and the BND calls of the built list into k.d_calls; *total = their number.  Adds its counts to
-// the scan's stats.
-svt_status bnd_stage(svt_ctx *c, const svt_call_params *p, uint32_t n_other, uint64_t *total) {
+// The BND stage of a scan, behind whatever its other passes did: their n_other calls `others` (in order)
+// and the BND calls of the built list into k.d_calls; *total = their number.  Adds its counts to the
+// scan's stats.
+svt_status bnd_stage(svt_ctx *c, const svt_call_params *p, const svt_call *others, uint32_t n_other, uint64_t *total) {
     CallScratch &k = c->call;
     CallScratch::Bnd &b = k.bn;
     const uint32_t m = (uint32_t)b.n_items, link = (uint32_t)p->link;
@@ -160,12 +160,7 @@ svt_status bnd_stage(svt_ctx *c, const svt_call_params *p, uint32_t n_other, uin
         hipLaunchKernelGGL(bnd_gather_kernel, cg, cb, 0, nullptr, b.d_raw.get(), b.d_idx.get(), npick, b.d_sorted.get());
         HIP_TRY(c, hipGetLastError());
     }
-    if (*total) {
-        if ((s = nomem(c, k.d_calls.reserve(*total), CALL_MEM))) return s;
-        hipLaunchKernelGGL(rearr_merge_kernel, dim3((unsigned)((*total + 255u) / 256u)), dim3(256), 0, nullptr, b.d_other.get(), n_other,
-                           b.d_sorted.get(), npick, k.d_calls.get());
-        HIP_TRY(c, hipGetLastError());
-    }
+    if ((s = call_merge(c, others, n_other, b.d_sorted.get(), npick, k.d_calls))) return s;
     k.last.call_stats.clusters += ncl;
     k.last.call_stats.calls += npick;
     k.last.bnd_stats.clusters = ncl;

@@ -28,8 +28,8 @@
 //              adds every item into its cluster's record with integer atomics (exact in any
 //              order); call_pick_kernel + one select list the clusters with c >= min_support.
 //   emit       (call_emit_kernel, one wave per call) the rounded means, the depth as evidence's
-//              one-base region query (ev_depth), the 48-B record in 12 lanes' stores;
-//              call_merge_kernel then merges the DEL and the INS list, each in (chrom, pos) order
+//              one-base region query (ev_depth), the 48-B record in 12 lanes' stores (call_store);
+//              merge_lists_kernel then merges the DEL and the INS list, each in (chrom, pos) order
 //              as it comes, into (chrom, pos, type) order -- a binary search per call.
 // No two calls compare equal (clusters of one type and contig have disjoint x ranges, so their
 // rounded means differ), and no step depends on the order of the events inside a bucket.
@@ -293,48 +293,57 @@ __global__ __launch_bounds__(256) void call_pick_kernel(CallArgs a, uint32_t n_c
     if (m && lane_id() == 0) atomicAdd(n_del, (uint32_t)__popcll(m));
 }
 
+// A call record's twelve words, one store each from the wave's first twelve lanes.
+__device__ __forceinline__ void call_store(svt_call *dst, const uint32_t (&w)[12]) {
+    const int ln = lane_id();
+    uint32_t word = 0;
+#pragma unroll
+    for (int i = 0; i < 12; i++) word = ln == i ? w[i] : word;
+    if (ln < 12) reinterpret_cast<uint32_t *>(dst)[ln] = word;
+}
+// One thread copies a record: three 16-B words.
+__device__ __forceinline__ void call_copy(svt_call *dst, const svt_call *src) {
+    const uint4 *s = reinterpret_cast<const uint4 *>(src);
+    uint4 *d = reinterpret_cast<uint4 *>(dst);
+    d[0] = s[0], d[1] = s[1], d[2] = s[2];
+}
+
+// One wave per call.  REARR: the rearrangement index's rows S / I are DUP / INV, both ending at mean(x + len).
+template <bool REARR>
 __global__ __launch_bounds__(64 * WPB) void call_emit_kernel(CallArgs a, uint32_t n_calls, svt_call *out) {
     const uint32_t g = blockIdx.x * WPB + (threadIdx.x >> 6);
     if (g >= n_calls) return;
     const CallAcc q = a.acc[(uint32_t)uniform_i((int32_t)a.pick[g])];
     const unsigned long long c = q.cnt, h = c / 2;
-    const int ins = q.seg >= (uint32_t)a.nt ? 1 : 0, tid = (int)(q.seg - (ins ? (uint32_t)a.nt : 0u));
+    const int ri = q.seg >= (uint32_t)a.nt ? 1 : 0, tid = (int)(q.seg - (ri ? (uint32_t)a.nt : 0u));   // (ri: a cluster of row I)
     const uint32_t pos = (uint32_t)uniform_i((int32_t)(uint32_t)((q.sx + h) / c));
     const uint32_t len = (uint32_t)((q.slen + h) / c);
-    const uint32_t end = ins ? pos + 1u : (uint32_t)((q.sx + q.slen + c + h) / c);
+    const uint32_t end = REARR ? (uint32_t)((q.sx + q.slen + h) / c) : ri ? pos + 1u : (uint32_t)((q.sx + q.slen + c + h) / c);
     const uint32_t depth = ev_depth(a.pile, tid, pos);
-    const uint32_t w[12] = {(uint32_t)(ins ? SVT_INS : SVT_DEL), (uint32_t)(tid + 1), pos, end, q.cnt, depth, len,
-                            ~q.nlen_lo, q.len_hi, ~q.nx_lo, q.x_hi, 0u};
-    const int ln = lane_id();
-    uint32_t word = 0;
-#pragma unroll
-    for (int i = 0; i < 12; i++) word = ln == i ? w[i] : word;
-    if (ln < 12) reinterpret_cast<uint32_t *>(out + g)[ln] = word;
+    const uint32_t w[12] = {(uint32_t)(REARR ? (ri ? SVT_INV : SVT_DUP) : (ri ? SVT_INS : SVT_DEL)), (uint32_t)(tid + 1), pos, end, q.cnt,
+                            depth, len, ~q.nlen_lo, q.len_hi, ~q.nx_lo, q.x_hi, 0u};
+    call_store(out + g, w);
 }
 
-// The picked clusters are numbered in scan order: the n_del DEL calls first, then the INS calls, each
-// list in (chrom, pos) order already.  One thread per call merges the two lists: a DEL call goes behind
-// the INS calls at or before its (chrom, pos), an INS call behind the DEL calls strictly before it.
-__global__ __launch_bounds__(256) void call_merge_kernel(const svt_call *in, uint32_t n_calls, uint32_t n_del, svt_call *out) {
+// Two sorted lists into one: la[0 .. na) and lb[0 .. nb), each in (chrom, pos, type code[, len]) order, every
+// type code of la below every one of lb, so (chrom, pos) alone decides: a call of la goes behind the calls of lb
+// strictly before it, a call of lb behind those of la at or before it.  One thread per call.  (la, lb) = a pass's
+// (INS, DEL) calls, the (DEL / INS, INV / DUP) lists of a scan with rearr != 0, (the others, the BND calls).
+__global__ __launch_bounds__(256) void merge_lists_kernel(const svt_call *la, uint32_t na, const svt_call *lb, uint32_t nb, svt_call *out) {
     const uint32_t g = blockIdx.x * 256u + threadIdx.x;
-    if (g >= n_calls) return;
-    const bool del = g < n_del;
-    auto key = [&](uint32_t i) { return (unsigned long long)(uint32_t)in[i].chrom << 32 | in[i].pos; };
-    const unsigned long long k = key(g);
-    uint32_t lo = del ? n_del : 0u, hi = del ? n_calls : n_del;
-    const uint32_t base = lo;
+    if (g >= na + nb) return;
+    const bool first = g < na;
+    const svt_call *mine = first ? la + g : lb + (g - na), *other = first ? lb : la;
+    auto key = [](const svt_call &c) { return (unsigned long long)(uint32_t)c.chrom << 32 | c.pos; };
+    const unsigned long long k = key(*mine);
+    uint32_t lo = 0, hi = first ? nb : na;
     while (lo < hi) {
         const uint32_t m = lo + (hi - lo) / 2;
-        const unsigned long long o = key(m);
-        if (del ? o <= k : o < k) lo = m + 1;
+        const unsigned long long o = key(other[m]);
+        if (first ? o < k : o <= k) lo = m + 1;
         else hi = m;
     }
-    const uint32_t rank = (del ? g : g - n_del) + (lo - base);
-    const uint4 *src = reinterpret_cast<const uint4 *>(in + g);
-    uint4 *dst = reinterpret_cast<uint4 *>(out + rank);
-    dst[0] = src[0];
-    dst[1] = src[1];
-    dst[2] = src[2];
+    call_copy(out + (first ? g : g - na) + lo, mine);
 }
 
 // ---- splitting the start clusters by length (svt_call_params.len_permille = P > 0) ----------------
@@ -356,7 +365,7 @@ __global__ __launch_bounds__(256) void call_merge_kernel(const svt_call *in, uin
 //   order      (call_order_kernel, one workgroup per candidate) the groups come in len order; their
 //              keys pos << 32 | group go through the same network and the records to the candidate's
 //              units in (pos, len) order.  call_unit_kernel copies the other clusters' records.
-// call_pick_kernel, call_emit_kernel and call_merge_kernel then run on the units as they do on the
+// call_pick_kernel, call_emit_kernel and merge_lists_kernel then run on the units as they do on the
 // clusters: units of different clusters keep the clusters' order, so both lists are in (chrom, pos,
 // len) order and the merge gives (chrom, pos, type, len).  Groups of one cluster have disjoint len
 // ranges more than link apart, so their rounded mean len differ: no two calls compare equal.

@@ -6,6 +6,16 @@ namespace {
 
 constexpr const char *CALL_MEM = "svt_call_scan: device scratch";
 
+// A pass's counters as they lie in k.d_ctr: zeroed when the pass begins, read back once at its end.
+struct CallCtr {
+    uint32_t picked, picked_del;                       // calls, the DEL calls among them
+    unsigned long long events, skipped, big_buckets;   // call_sort_kernel's
+    unsigned long long split, groups, split_big;       // call_split_kernel's (len_permille > 0)
+    uint32_t candidates, pad;                          // call_split_1's select
+};
+constexpr size_t CALL_NCTR = sizeof(CallCtr) / sizeof(uint32_t);
+static_assert(sizeof(CallCtr) == 64 && offsetof(CallCtr, events) == 8 && offsetof(CallCtr, split) == 32, "addressed by word");
+
 // The index a scan runs on: the value buckets, or a derived index in their shape (CallIndex) -- the
 // merged index (merge_gap > 0), the union of either with the junction events (junctions = 1), the
 // rearrangement index (the second pass of rearr != 0).  The segments depend on the extents, so each has
@@ -33,7 +43,7 @@ CallView call_view(svt_ctx *c, bool merged, bool junction) {
 svt_status junction_build(svt_ctx *c, uint32_t gap, uint32_t min_len);   // svt_junction_host.inc
 svt_status rearr_build(svt_ctx *c);                                      // svt_rearr_host.inc
 svt_status bnd_build(svt_ctx *c);                                        // svt_bnd_host.inc
-svt_status bnd_stage(svt_ctx *c, const svt_call_params *p, uint32_t n_other, uint64_t *total);
+svt_status bnd_stage(svt_ctx *c, const svt_call_params *p, const svt_call *others, uint32_t n_other, uint64_t *total);
 
 // The first scan of a loaded pileup (of a merged index): the segments (the buckets' extents are those
 // of the load for every rebuild) and the scratch that depends on the event counts alone.
@@ -46,7 +56,7 @@ svt_status call_prepare(svt_ctx *c, const CallView &v) {
     DevBuf<uint64_t> &d_seg = v.segs->d_seg;
     uint64_t &n_seg = v.segs->n_seg;
     if ((s = nomem(c, d_flag.reserve(nb2), CALL_MEM)) || (s = nomem(c, d_seg.reserve(nb2), CALL_MEM)) ||
-        (s = nomem(c, k.d_ctr.reserve(8), CALL_MEM)))
+        (s = nomem(c, k.d_ctr.reserve(CALL_NCTR), CALL_MEM)))
         return s;
     const BkIndex &B = v.bk;
     hipLaunchKernelGGL(call_flag_kernel, dim3((unsigned)((nb2 + 255) / 256)), dim3(256), 0, nullptr, B, c->n_targets, d_flag);
@@ -78,16 +88,14 @@ svt_status call_split_1(svt_ctx *c, const CallArgs &a, uint32_t n_keys, uint32_t
     CallScratch &k = c->call;
     svt_status s;
     if ((s = nomem(c, k.d_cflag.reserve(ncl), CALL_MEM)) || (s = nomem(c, k.d_cand.reserve(ncl), CALL_MEM)) ||
-        (s = nomem(c, k.d_kend.reserve(ncl), CALL_MEM)) || (s = nomem(c, k.d_unit.reserve(ncl), CALL_MEM)) ||
-        (s = nomem(c, k.d_sctr.reserve(4), CALL_MEM)))
+        (s = nomem(c, k.d_kend.reserve(ncl), CALL_MEM)) || (s = nomem(c, k.d_unit.reserve(ncl), CALL_MEM)))
         return s;
-    uint32_t *d_ncand = reinterpret_cast<uint32_t *>(k.d_sctr + 3);
+    uint32_t *d_ncand = k.d_ctr + offsetof(CallCtr, candidates) / 4;
     hipcub::CountingInputIterator<uint32_t> it(0);
     size_t t1 = 0, t2 = 0;
     HIP_TRY(c, hipcub::DeviceSelect::Flagged(nullptr, t1, it, k.d_cflag.get(), k.d_cand.get(), d_ncand, (int)ncl, nullptr));
     HIP_TRY(c, hipcub::DeviceScan::InclusiveSum(nullptr, t2, k.d_kend.get(), k.d_kend.get(), (int)ncl, nullptr));
     if ((s = nomem(c, k.d_tmp.reserve(std::max(t1, t2)), CALL_MEM))) return s;
-    HIP_TRY(c, hipMemsetAsync(k.d_sctr, 0, 4 * sizeof(unsigned long long), nullptr));
     const dim3 cg((ncl + 255u) / 256u), cb(256);
     hipLaunchKernelGGL(call_cand_kernel, cg, cb, 0, nullptr, a, ncl, k.d_cflag, k.d_kend, k.d_unit);
     size_t tb = k.d_tmp.cap();
@@ -103,7 +111,7 @@ svt_status call_split_1(svt_ctx *c, const CallArgs &a, uint32_t n_keys, uint32_t
     sp.cand = k.d_cand;
     sp.kend = k.d_kend;
     sp.unit = k.d_unit;
-    sp.stats = k.d_sctr;
+    sp.stats = reinterpret_cast<unsigned long long *>(k.d_ctr + offsetof(CallCtr, split) / 4);
     sp.n_keys = n_keys;
     const dim3 sg(ncand), sb(CALL_T);
     if (ncand) {
@@ -130,17 +138,25 @@ svt_status call_split_1(svt_ctx *c, const CallArgs &a, uint32_t n_keys, uint32_t
     hipLaunchKernelGGL(call_unit_kernel, cg, cb, 0, nullptr, a, sp, ncl);
     if (ncand) hipLaunchKernelGGL(call_order_kernel, sg, sb, 0, nullptr, a, sp);
     HIP_TRY(c, hipGetLastError());
-    k.last.split_stats.candidates += ncand;   // (zeroed when the scan began; a scan with rearr != 0 has two passes)
+    return SVT_OK;
+}
+
+// la[0 .. na) and lb[0 .. nb) merged into dst (merge_lists_kernel): the destination reserved, the launch checked.
+svt_status call_merge(svt_ctx *c, const svt_call *la, uint32_t na, const svt_call *lb, uint32_t nb, DevBuf<svt_call> &dst) {
+    const uint64_t n = (uint64_t)na + nb;
+    if (n == 0) return SVT_OK;
+    if (svt_status s = nomem(c, dst.reserve(n), CALL_MEM)) return s;
+    hipLaunchKernelGGL(merge_lists_kernel, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, nullptr, la, na, lb, nb, dst.get());
+    HIP_TRY(c, hipGetLastError());
     return SVT_OK;
 }
 
 // One pass of the scan over view v: the sort, the link, the accumulation, the split by length and the pick,
-// then the records -- call_emit_kernel's, or rearr_emit_kernel's for the rearrangement index (svt_rearr.inc) --
-// and the merge of the pass's two lists into dst.  The pass's counters stay in k.d_ctr / k.d_sctr for
-// call_pass_stats.
+// then the records -- call_emit_kernel's for the view, or for the rearrangement index (svt_rearr.inc) -- and
+// the merge of the pass's two lists into dst.  What it counted comes back in *out.
 struct CallPass {
     uint32_t ncl = 0, npick = 0;
-    bool split = false;           // the split ran: its counters are in k.d_sctr
+    CallCtr ctr{};
 };
 svt_status call_pass(svt_ctx *c, const svt_call_params *p, const CallView &v, uint32_t types, bool rearr, DevBuf<svt_call> &dst,
                      CallPass *out) {
@@ -168,7 +184,7 @@ svt_status call_pass(svt_ctx *c, const svt_call_params *p, const CallView &v, ui
     a.types = types;
     a.permille = p->len_permille;
     const dim3 sg((unsigned)n_seg), sb(CALL_T);
-    HIP_TRY(c, hipMemsetAsync(k.d_ctr, 0, 8 * sizeof(uint32_t), nullptr));
+    HIP_TRY(c, hipMemsetAsync(k.d_ctr, 0, sizeof(CallCtr), nullptr));
     hipLaunchKernelGGL(call_sort_kernel, sg, sb, 0, nullptr, a);
     size_t tb = k.d_tmp.cap();
     HIP_TRY(c, hipcub::DeviceScan::ExclusiveScan(k.d_tmp.get(), tb, k.d_tmax.get(), k.d_tprev.get(), hipcub::Max(), 0ull,
@@ -180,7 +196,6 @@ svt_status call_pass(svt_ctx *c, const svt_call_params *p, const CallView &v, ui
     uint32_t ncl = 0, ncl_s = 0;   // clusters; those of array S (the DEL clusters come first)
     HIP_TRY(c, hipMemcpy(&ncl, k.d_cid + (N - 1), 4, hipMemcpyDeviceToHost));
     if (a.n_s) HIP_TRY(c, hipMemcpy(&ncl_s, k.d_cid + (a.n_s - 1), 4, hipMemcpyDeviceToHost));
-    uint32_t picked[2] = {0, 0};   // calls, the DEL calls among them
     if (ncl) {
         size_t need = 0;
         hipcub::CountingInputIterator<uint32_t> it(0);
@@ -210,43 +225,33 @@ svt_status call_pass(svt_ctx *c, const svt_call_params *p, const CallView &v, ui
         tb = k.d_tmp.cap();
         HIP_TRY(c, hipcub::DeviceSelect::Flagged(k.d_tmp.get(), tb, it, k.d_flag.get(), k.d_pick.get(), k.d_ctr.get(), (int)nu, nullptr));
         HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpy(picked, k.d_ctr, sizeof picked, hipMemcpyDeviceToHost));
     }
-    const uint32_t npick = picked[0], ndel = std::min(picked[1], picked[0]);
+    CallCtr &ctr = out->ctr;   // (behind every kernel of the pass that counts)
+    HIP_TRY(c, hipMemcpy(&ctr, k.d_ctr, sizeof ctr, hipMemcpyDeviceToHost));
+    const uint32_t npick = ctr.picked, ndel = std::min(ctr.picked_del, ctr.picked);
     if (npick) {
-        if ((s = nomem(c, dst.reserve(npick), CALL_MEM)) || (s = nomem(c, k.d_raw.reserve(npick), CALL_MEM))) return s;
+        if ((s = nomem(c, k.d_raw.reserve(npick), CALL_MEM))) return s;
         const dim3 eg((npick + WPB - 1) / WPB), eb(64 * WPB);
-        if (rearr) hipLaunchKernelGGL(rearr_emit_kernel, eg, eb, 0, nullptr, a, npick, k.d_raw);
-        else hipLaunchKernelGGL(call_emit_kernel, eg, eb, 0, nullptr, a, npick, k.d_raw);
-        hipLaunchKernelGGL(call_merge_kernel, dim3((npick + 255u) / 256u), dim3(256), 0, nullptr, k.d_raw, npick, ndel,
-                           dst.get());
-        HIP_TRY(c, hipGetLastError());
+        if (rearr) hipLaunchKernelGGL(call_emit_kernel<true>, eg, eb, 0, nullptr, a, npick, k.d_raw);
+        else hipLaunchKernelGGL(call_emit_kernel<false>, eg, eb, 0, nullptr, a, npick, k.d_raw);
+        if ((s = call_merge(c, k.d_raw + ndel, npick - ndel, k.d_raw, ndel, dst))) return s;   // (la: the INS calls, behind the ndel DEL calls)
     }
     out->ncl = ncl;
     out->npick = npick;
-    out->split = a.permille && ncl;
     return SVT_OK;
 }
 
-// The counters of the pass that ran last, added to the scan's stats (zeroed when the scan began).
-svt_status call_pass_stats(svt_ctx *c, const CallPass &ps, unsigned long long *skipped = nullptr) {
-    CallScratch &k = c->call;
-    unsigned long long st[3] = {};
-    HIP_TRY(c, hipMemcpy(st, k.d_ctr + 2, sizeof st, hipMemcpyDeviceToHost));
-    if (ps.split) {
-        unsigned long long ss[3] = {};
-        HIP_TRY(c, hipMemcpy(ss, k.d_sctr, sizeof ss, hipMemcpyDeviceToHost));
-        k.last.split_stats.split += ss[0];
-        k.last.split_stats.groups += ss[1];
-        k.last.split_stats.big += ss[2];
-    }
-    k.last.call_stats.events += st[0];
-    k.last.call_stats.skipped += st[1];
-    k.last.call_stats.big_buckets += st[2];
-    k.last.call_stats.clusters += ps.ncl;
-    k.last.call_stats.calls += ps.npick;
-    if (skipped) *skipped = st[1];
-    return SVT_OK;
+// A pass's counts added to the scan's stats (zeroed when the scan began).
+void call_pass_stats(CallScratch::Last &l, const CallPass &ps) {
+    l.call_stats.events += ps.ctr.events;
+    l.call_stats.skipped += ps.ctr.skipped;
+    l.call_stats.big_buckets += ps.ctr.big_buckets;
+    l.call_stats.clusters += ps.ncl;
+    l.call_stats.calls += ps.npick;
+    l.split_stats.candidates += ps.ctr.candidates;
+    l.split_stats.split += ps.ctr.split;
+    l.split_stats.groups += ps.ctr.groups;
+    l.split_stats.big += ps.ctr.split_big;
 }
 
 svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) {
@@ -288,7 +293,7 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
     k.last.junction = junction;
     k.last.rearr = rearr;
     k.last.bnd = p->bnd;
-    const bool bnd = p->bnd && k.bn.n_items != 0;   // the BND stage runs: the scan's other calls go to k.bn.d_other first
+    const bool bnd = p->bnd && k.bn.n_items != 0;   // the BND stage runs
     const CallView v = call_view(c, merged, junction);
     const uint64_t N = base_types ? v.n_s + v.n_i : 0;   // (no DEL / INS bit: a rearrangement- or breakend-only scan)
     if (N == 0 && !rearr && !bnd) return SVT_OK;
@@ -296,40 +301,35 @@ svt_status call_scan_1(svt_ctx *c, const svt_call_params *p, uint64_t *n_calls) 
     HIP_TRY(c, e0.create());
     HIP_TRY(c, e1.create());
     HIP_TRY(c, hipEventRecord(e0, nullptr));
-    CallPass ps{}, pr{};   // the pass over v, the second pass
-    DevBuf<svt_call> &others = bnd ? k.bn.d_other : k.d_calls;   // where the calls of the passes end up
-    if (N && (s = call_pass(c, p, v, p->types, false, rearr ? k.rr.d_a : others, &ps))) return s;
-    uint64_t total = ps.npick;
-    bool second = false;
-    if (rearr) {   // the second pass, over the rearrangement index, and the merge of the two lists (svt_rearr.inc)
-        if (N && (s = call_pass_stats(c, ps))) return s;   // (before the second pass reuses k.d_ctr)
+    // Three stages, each handing its sorted list (list, total) to the next; the last one's lands in k.d_calls.
+    const svt_call *list = nullptr;
+    uint64_t total = 0;
+    if (N) {   // the pass over the view
+        DevBuf<svt_call> &dst = rearr || bnd ? k.d_list1 : k.d_calls;
+        CallPass ps{};
+        if ((s = call_pass(c, p, v, p->types, false, dst, &ps))) return s;
+        call_pass_stats(k.last, ps);
+        list = dst.get(), total = ps.npick;
+    }
+    if (rearr) {   // the pass over the rearrangement index (svt_rearr.inc), its list merged behind the first
+        DevBuf<svt_call> &dst = bnd ? k.d_list2 : k.d_calls;
         const CallView rv = index_view(c, k.rr);
         const uint32_t rtypes = ((rearr >> SVT_DUP) & 1u) << SVT_DEL | ((rearr >> SVT_INV) & 1u) << SVT_INS;
-        second = rv.n_s + rv.n_i != 0;
-        if (second && (s = call_pass(c, p, rv, rtypes, true, k.rr.d_b, &pr))) return s;
-        total += pr.npick;
-        if (total > 0x7fffffffull) return fail(c, SVT_ESTATE, "%s", "svt_call_scan: more than 2^31 - 1 calls are not supported");
-        if (total) {
-            if ((s = nomem(c, others.reserve(total), CALL_MEM))) return s;
-            hipLaunchKernelGGL(rearr_merge_kernel, dim3((unsigned)((total + 255u) / 256u)), dim3(256), 0, nullptr, k.rr.d_a.get(),
-                               ps.npick, k.rr.d_b.get(), pr.npick, others.get());
-            HIP_TRY(c, hipGetLastError());
+        CallPass pr{};
+        if (rv.n_s + rv.n_i != 0) {   // (no counters of a pass that does not run)
+            if ((s = call_pass(c, p, rv, rtypes, true, k.rr.d_calls, &pr))) return s;
+            call_pass_stats(k.last, pr);
+            k.last.rearr_stats.skipped = pr.ctr.skipped;
+            k.last.rearr_stats.clusters = pr.ncl;
+            k.last.rearr_stats.calls = pr.npick;
         }
+        if (total + pr.npick > 0x7fffffffull) return fail(c, SVT_ESTATE, "%s", "svt_call_scan: more than 2^31 - 1 calls are not supported");
+        if ((s = call_merge(c, list, (uint32_t)total, k.rr.d_calls.get(), pr.npick, dst))) return s;
+        list = dst.get(), total += pr.npick;
     }
-    if (bnd) {   // one more stage behind whatever the passes did: its own scratch, none of k.d_ctr / k.d_sctr (svt_bnd_host.inc)
-        if ((s = bnd_stage(c, p, (uint32_t)total, &total))) return s;
-    }
+    if (bnd && (s = bnd_stage(c, p, list, (uint32_t)total, &total))) return s;   // its list merged behind the others (svt_bnd_host.inc)
     HIP_TRY(c, hipEventRecord(e1, nullptr));
     HIP_TRY(c, hipEventSynchronize(e1));
-    if (second) {   // (no counters of a pass that did not run)
-        unsigned long long skipped = 0;
-        if ((s = call_pass_stats(c, pr, &skipped))) return s;
-        k.last.rearr_stats.skipped = skipped;
-        k.last.rearr_stats.clusters = pr.ncl;
-        k.last.rearr_stats.calls = pr.npick;
-    } else if (!rearr && N && (s = call_pass_stats(c, ps))) {
-        return s;
-    }
     float ms = 0.f;
     HIP_TRY(c, hipEventElapsedTime(&ms, e0, e1));
     k.last.call_stats.scan_ms = ms;

@@ -1,6 +1,7 @@
 // svt_callindex.inc -- what the builds of svt_call_scan's derived indexes share on the device (included
 // by svt_engine.hip before svt_callmerge.inc, svt_junction.inc and svt_rearr.inc; the host side is
-// svt_callindex_host.inc).
+// svt_callindex_host.inc).  The segment table's junctions -- jn_next, jn_classify -- live in svt_jnclass.h,
+// free of HIP and tested on the CPU; their limits are set at the end of this file.
 //
 // Each of those indexes has the value buckets' shape -- 16-B events filed by x under the main index's
 // cbase / cnb / nbk, an off[BA_N][nbk + 1] table of which rows S and I are filled -- and is built by two
@@ -25,7 +26,7 @@ struct BkFile {
 
 // One item of row T (false: S, true: I) in bucket g: counted, or filed behind the bucket's first `skip`
 // events (the union's base events; 0 elsewhere).  The check is the strictest the three builds had; on a
-// consistent count none of its terms fires.  (T is a bool and jn_next walks a pointer because the other
+// consistent count none of its terms fires.  (T is a bool and svt_jnclass.h's jn_next walks a pointer because the other
 // spellings cost rearr_kernel and junction_kernel up to three VGPRs: profiles/call_index/README.md.)
 template <bool COUNT>
 __device__ __forceinline__ void bk_file(const BkFile &f, bool T, uint64_t g, uint32_t skip, const uint4 &e) {
@@ -57,30 +58,9 @@ __device__ __forceinline__ void bk_stat_add(const BkFile &f, uint32_t (&v)[N]) {
     }
 }
 
-// a < b in the order of the tuple (q_beg, q_end, tid, r_beg, strand)
-__device__ __forceinline__ bool jn_less(const svt_junction_seg &a, const svt_junction_seg &b) {
-    if (a.q_beg != b.q_beg) return a.q_beg < b.q_beg;
-    if (a.q_end != b.q_end) return a.q_end < b.q_end;
-    if (a.tid != b.tid) return a.tid < b.tid;
-    if (a.r_beg != b.r_beg) return a.r_beg < b.r_beg;
-    return a.strand < b.strand;
-}
-
-// The junction of table record k (include/svtrek_junction.h): A its first row, B the smallest tuple
-// strictly greater than A's among the others, by one pass over the record's rows.  Returns whether
-// there is one.
-__device__ __forceinline__ bool jn_next(const uint64_t *off, const svt_junction_seg *seg, uint64_t k, svt_junction_seg &A,
-                                        svt_junction_seg &B) {
-    const uint64_t r0 = off[k], r1 = off[k + 1];
-    A = seg[r0];
-    B = A;
-    bool have = false;
-    for (const svt_junction_seg *p = seg + r0 + 1, *e = seg + r1; p < e; p++) {
-        const svt_junction_seg t = *p;
-        if (jn_less(A, t) && (!have || jn_less(t, B))) {
-            B = t;
-            have = true;
-        }
-    }
-    return have;
-}
+// What jn_classify (svt_jnclass.h) is given: the engine's thresholds and clamps.  A junction event is
+// {x, len << 4 | op, extent end, extent begin | JN_MARK}: bit 31 of the word in which a CIGAR event keeps its
+// read's pos (< 2^31) marks it, so both extent words stop at JN_EXT_MAX.
+constexpr uint32_t JN_MARK = 0x80000000u, JN_EXT_MAX = 0x7fffffffu;
+constexpr uint32_t CM_LEN_MAX = (1u << 28) - 1u;   // an event's len field
+__device__ __forceinline__ JnLimits jn_limits() { return JnLimits{SV_MIN_LENGTH, IX_SAT, CM_LEN_MAX, JN_EXT_MAX}; }

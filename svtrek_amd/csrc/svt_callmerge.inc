@@ -27,7 +27,6 @@
 // that type one ballot.  No LDS, no serial loop over lanes; the loops and the per-type skip are
 // wave-uniform, the rest is predicated per lane.
 constexpr int CM_NSTAT = 4;           // fragments, runs, joined items, items
-constexpr uint32_t CM_LEN_MAX = (1u << 28) - 1u;
 
 struct CallMergeArgs {
     const uint32_t *stream;       // the CIGAR stream

@@ -152,17 +152,18 @@ struct CallScratch {
     CallSegs segs;                 // the plain buckets'
     DevBuf<unsigned long long> d_keys, d_tmax, d_tprev;
     DevBuf<uint32_t> d_cid, d_pick;
-    DevBuf<uint32_t> d_ctr;        // [0] picked calls, [1] the DEL calls among them, [2..8) events / skipped / big buckets (64 bits each)
+    DevBuf<uint32_t> d_ctr;        // a pass's counters, CALL_NCTR words zeroed when it begins: the device side of CallCtr
     DevBuf<CallAcc> d_acc;
     DevBuf<uint8_t> d_tmp;         // hipcub's temporary storage
     DevBuf<uint8_t> d_flag;        // per cluster: a call
-    DevBuf<svt_call> d_calls, d_raw;   // in (chrom, pos, type) order / as emitted
+    DevBuf<svt_call> d_calls, d_raw;   // the scan's calls in order / a pass's as emitted
+    // (a scan's stages -- the view's pass, the rearrangement pass, the BND stage -- each hand a sorted list on)
+    DevBuf<svt_call> d_list1, d_list2; // the list after the first / second stage where another follows; the last one's is d_calls
     uint64_t n_calls = 0;
     // the split by length (len_permille > 0): nothing allocated before the first such scan
     DevBuf<uint32_t> d_first, d_cand, d_kend, d_unit;   // per cluster: first key slot / candidates / their keys' ends / units
     DevBuf<uint8_t> d_cflag;       // per cluster: a candidate
     DevBuf<unsigned long long> d_skeys;   // the candidates' sorted keys
-    DevBuf<unsigned long long> d_sctr;    // [0..3) split / groups / big, [3] the candidates (32 bits)
     DevBuf<CallAcc> d_gacc, d_uacc;       // per unit: the groups as accumulated / every unit in order
     // The derived indexes: nothing allocated before the first scan that asks for one, untouched by
     // svt_reindex; `stats` are the build's.
@@ -183,7 +184,7 @@ struct CallScratch {
     } jn;
     // the rearrangement index (rearr != 0; svt_rearr.inc, svt_rearr_host.inc): rebuilt when the table changes
     struct Rearr : CallIndex {
-        DevBuf<svt_call> d_a, d_b;        // the scan's two sorted lists before their merge: DEL / INS, INV / DUP
+        DevBuf<svt_call> d_calls;         // the second pass's INV / DUP calls before their merge with the first stage's list
         svt_call_rearr_stats stats{};
     } rr;
     // the BND item list (bnd = 1; svt_bnd.inc, svt_bnd_host.inc): no buckets, one list in (class, x) order;
@@ -203,7 +204,6 @@ struct CallScratch {
         DevBuf<svt_call> d_raw, d_sorted; // the BND calls as emitted / in order
         DevBuf<unsigned long long> d_k, d_k2;   // the order keys of the calls
         DevBuf<uint32_t> d_idx, d_idx2;   // the call indices they carry
-        DevBuf<svt_call> d_other;         // the scan's other calls before the merge with d_sorted
         // Not built, nothing allocated.  The caller synchronises first where a launch may still read it.
         void drop() { *this = Bnd{}; }
     } bn;

@@ -80,6 +80,7 @@
 #include "../../include/svtrek_bnd.h"
 #include "svt_bamrec.h"
 #include "svt_loadprep.h"
+#include "svt_jnclass.h"
 
 #define SVT_VERSION "svtrek_amd 0.34.0 (gfx950, value-bucketed event index filed by a lane-per-read walk with a 9-B LDS stage, band + prefix-max facts, packed span walk fed by readlane, lane vote on 64 windows a wave, BGZF inflate + BAM decode, DEL/INS discovery from the value buckets, genotypes from the events' own read extents, consensus sequence of INS calls, a read's fragmented D / I ops joined before calling, DEL/INS items, DUP/INV calls and translocation breakends from split alignments)"
 

@@ -1,6 +1,7 @@
 // svt_junction.inc -- DEL / INS items from split alignments (include/svtrek_junction.h,
 // svt_call_params.junctions = 1; included by svt_engine.hip after svt_callmerge.inc; BkFile, bk_file,
-// bk_stat_add, jn_less and jn_next are svt_callindex.inc's, the host side is svt_junction_host.inc).
+// bk_stat_add, JN_MARK and jn_limits are svt_callindex.inc's, jn_next and jn_classify -- the header's
+// rules -- svt_jnclass.h's, the host side is svt_junction_host.inc).
 //
 // The junction items go into a THIRD index in the value buckets' shape: the UNION of the base view's
 // events (the plain buckets' rows S and I, or the merged index's) and the junction events, bucket by
@@ -22,7 +23,6 @@
 // reads it.  A junction x lies in its bucket's 1 kb, a contig's last bucket takes everything past the
 // others: the counting sort of a big bucket relies on both.  Integer only, no LDS, no inline assembly.
 constexpr int JN_NSTAT = 5;           // junctions, DEL items, INS items, other, skipped
-constexpr uint32_t JN_MARK = 0x80000000u, JN_EXT_MAX = 0x7fffffffu;
 static_assert(sizeof(svt_junction_seg) == 24, "include/svtrek_junction.h");
 
 struct JunctionArgs {
@@ -40,33 +40,17 @@ __global__ __launch_bounds__(64 * WPB) void junction_kernel(JunctionArgs a) {
     if (k < a.n) {
         svt_junction_seg A, B;
         if (jn_next(a.off, a.seg, k, A, B)) {
+            const JnItem it = jn_classify<1u << JN_DEL | 1u << JN_INS>(A, B, jn_limits());
             st[0] = 1u;
-            int T = -1;   // 0 DEL, 1 INS
-            uint32_t x = 0, len = 0, lo = 0, hi = 0;
-            if (B.tid != A.tid || B.strand != A.strand) {
-                st[3] = 1u;
-            } else {
-                const svt_junction_seg &Lf = A.strand ? B : A, &Rt = A.strand ? A : B;
-                const int64_t dr = (int64_t)Rt.r_beg - (int64_t)Lf.r_end, dq = (int64_t)B.q_beg - (int64_t)A.q_end, d = dr - dq;
-                if (d > (int64_t)SV_MIN_LENGTH && dr > 0) T = 0;
-                else if (-d >= (int64_t)SV_MIN_LENGTH && dq > 0) {
-                    if (dr >= -(int64_t)SV_MIN_LENGTH) T = 1;
-                    else st[3] = 1u;
-                }
-                if (T >= 0) {
-                    x = min(Lf.r_end, IX_SAT);
-                    len = (uint32_t)min(T ? -d : d, (int64_t)CM_LEN_MAX);
-                    lo = min(min(Lf.r_beg, Rt.r_beg), JN_EXT_MAX);
-                    hi = min(max(Lf.r_end, Rt.r_end), JN_EXT_MAX);
-                }
-            }
-            if (T >= 0) {
+            st[3] = it.other ? 1u : 0u;
+            if (it.kind != JN_NONE) {
+                const bool T = it.kind == JN_INS;   // row S: DEL, row I: INS
                 st[1 + T] = 1u;
-                st[4] = x >= IX_SAT ? 1u : 0u;
-                const uint32_t nbt = a.f.cnb[A.tid];   // (>= 1: the record itself is a read of the contig)
-                const uint64_t row = (uint64_t)(T ? BA_I : BA_S) * (a.f.nbk + 1), g = a.f.cbase[A.tid] + min(x >> BKS, nbt - 1u);
+                st[4] = it.past ? 1u : 0u;
+                const uint32_t nbt = a.f.cnb[it.tid];   // (>= 1: the record itself is a read of the contig)
+                const uint64_t row = (uint64_t)(T ? BA_I : BA_S) * (a.f.nbk + 1), g = a.f.cbase[it.tid] + min(it.x >> BKS, nbt - 1u);
                 bk_file<COUNT>(a.f, T, g, COUNT ? 0u : a.boff[row + g + 1] - a.boff[row + g],   // (behind the bucket's base events)
-                               make_uint4(x, len << 4 | (T ? OP_INS : OP_DEL), hi, lo | JN_MARK));
+                               make_uint4(it.x, it.len << 4 | (T ? OP_INS : OP_DEL), it.hi, it.lo | JN_MARK));
             }
         }
     }
