@@ -145,6 +145,15 @@ def build_sanitizers(force: bool = False) -> dict[str, str]:
             _run(["gcc", "-O1", "-g", "-std=gnu11", "-pthread", *fl, "-I", CSRC, "-I", os.path.join(ROOT, "oracle"),
                   "-o", out] + orc_src + ["-lz", "-lm"])
         arts[f"oracle_{kind}"] = out
+    # the reader's error exits under ASan+UBSan with the leak checker (tests/test_ingest_err_san.py); like the CLI in
+    # build_all, built where its source is: the artefacts above do not depend on this driver being in the tree
+    out = os.path.join(out_dir, "ingest_err_asan")
+    err_src = [os.path.join(ROOT, "tests", "san", "ingest_err_san.cpp"), os.path.join(CSRC, "bam_ingest.cpp")]
+    if os.path.exists(err_src[0]):
+        if force or _stale(out, err_src + hdrs + [os.path.join(CSRC, "svt_bamrec.h")]):
+            _run(["g++", "-O1", "-g", "-std=c++17", "-pthread", *SAN_FLAGS["asan"], "-I", INC, "-I", CSRC, "-o", out] + err_src +
+                 ["-lz", "-ldl"])
+        arts["ingest_err_asan"] = out
     return arts
 
 

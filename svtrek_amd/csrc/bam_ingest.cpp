@@ -14,7 +14,13 @@
 //      copies into the final arrays at prefix-summed offsets).
 // A coordinate-sorted BAM (the only kind that has a BAI) needs no reordering; other
 // files are stably sorted by (tid, pos) at the end.  SEQ/QUAL/aux are never copied -- except, for
-// svth_bam_read_seq, the SEQ bases under every I >= 50 op (the allele-consensus mode's sequences).
+// svth_bam_read_seq, the SEQ bases under every I >= 50 op (the allele-consensus mode's sequences),
+// and, for svth_bam_read_sa, the SA:Z values as a segment table.
+//
+// In reading order: bgzf_scan and ZlibRaw (the one block-header scan, the one zlib inflate of a block);
+// BgzfReader (the opened file and its inflated byte stream); parse_header (the one BAM header parse); InsSeq
+// and SaTable (the two optional products: size per chunk, extract per record, finish in the final read
+// order); Ingest (the read as stages); svth_bam_read_device (compressed batches handed to a device sink).
 #include <dlfcn.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -24,6 +30,7 @@
 #include <atomic>
 #include <chrono>
 #include <future>
+#include <memory>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -38,10 +45,8 @@
 
 namespace {
 
-
-
-inline uint32_t rd32(const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; }
-inline uint16_t rd16(const uint8_t *p) { uint16_t v; memcpy(&v, p, 2); return v; }
+using bamrec::rd16;
+using bamrec::rd32;
 
 template <typename F>
 void parallel_for(int threads, size_t n, F &&f) {   // f(begin, end) over contiguous slices
@@ -77,50 +82,111 @@ const Inflater &inflater() {
     return inf;
 }
 
-// Growable byte buffer without value-initialisation; view() points it at a buffer owned by the
-// reader (the device-inflated batches are handed over without a copy).
-struct Bytes {
-    uint8_t *p = nullptr;
+// Growable array without value-initialisation; large blocks grow by realloc (mremap on
+// glibc), so appending a chunk never re-copies or zero-fills what is already there.
+template <typename T>
+struct RawVec {
+    T *p = nullptr;
     size_t n = 0, cap = 0;
-    Bytes() = default;
-    Bytes(const Bytes &) = delete;
-    Bytes &operator=(const Bytes &) = delete;
-    ~Bytes() {
-        if (owned) free(p);
-    }
-    size_t size() const { return n; }
-    uint8_t *data() { return p; }
-    const uint8_t *data() const { return p; }
+    RawVec() = default;
+    RawVec(const RawVec &) = delete;
+    RawVec &operator=(const RawVec &) = delete;
+    ~RawVec() { free(p); }
     bool resize(size_t m) {
         if (m > cap) {
-            const size_t c = std::max(m, cap + cap / 2);
-            uint8_t *q = (uint8_t *)(owned ? realloc(p, c) : malloc(c));
+            size_t c = std::max(m, cap + cap / 2 + 1024);
+            T *q = (T *)realloc(p, c * sizeof(T));
             if (!q) return false;
-            if (!owned && n) memcpy(q, p, n);
             p = q;
             cap = c;
-            owned = true;
         }
         n = m;
         return true;
+    }
+    size_t size() const { return n; }
+    T *data() { return p; }
+    const T *data() const { return p; }
+    T &operator[](size_t i) { return p[i]; }
+    const T &operator[](size_t i) const { return p[i]; }
+    void swap(RawVec &o) { std::swap(p, o.p); std::swap(n, o.n); std::swap(cap, o.cap); }
+};
+
+// The window on the inflated byte stream: grown by the host-thread inflate, or (view) pointed at a batch
+// buffer that the reader owns -- the device-inflated batches are handed over without a copy.
+struct Bytes : RawVec<uint8_t> {
+    bool viewed = false;
+    ~Bytes() {
+        if (viewed) p = nullptr;
+    }
+    bool resize(size_t m) { return viewed && m > cap ? false : RawVec::resize(m); }   // (a view never grows)
+    void view(uint8_t *q, size_t m) {
+        if (!viewed) free(p);
+        p = q;
+        n = cap = m;
+        viewed = true;
     }
     void erase_front(size_t k) {
         if (k) memmove(p, p + k, n - k);
         n -= k;
     }
     void clear() { n = 0; }
-    bool owned = true;   // false: a view of a buffer someone else frees (view())
-    void view(uint8_t *q, size_t m) {
-        if (owned) free(p);
-        p = q;
-        n = cap = m;
-        owned = false;
+};
+
+// The BGZF block-header scan (SAM spec 4.1: the gzip magic with FEXTRA, xlen, the BC subfield's BSIZE, the
+// trailing ISIZE): the whole blocks of buf[p, n) appended to blks -- coff counted from buf, uoff from u --
+// and p, u advanced past them.  Stops in front of a block that is not complete yet.  Returns the error, or
+// null; at the end of the file (`eof`) bytes that hold no whole block are an error.
+const char *bgzf_scan(const uint8_t *buf, size_t n, bool eof, size_t &p, size_t &u, std::vector<svt_bgzf_block> &blks) {
+    while (p + 18 <= n) {
+        const uint8_t *h = buf + p;
+        if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) return "not a BGZF file (bad gzip header)";
+        const size_t xlen = rd16(h + 10);
+        if (p + 12 + xlen > n) break;
+        size_t bsize = 0;
+        for (size_t x = 0; x + 4 <= xlen;) {
+            const uint8_t *sf = h + 12 + x;
+            const size_t slen = rd16(sf + 2);
+            if (sf[0] == 66 && sf[1] == 67 && slen == 2) bsize = (size_t)rd16(sf + 4) + 1;
+            x += 4 + slen;
+        }
+        // (a BSIZE smaller than the block's own framing: the deflate length below would wrap)
+        if (!bsize || bsize < xlen + 20) return "BGZF block without BC subfield";
+        if (p + bsize > n) break;
+        blks.push_back(svt_bgzf_block{p + 12 + xlen, u, (uint32_t)(bsize - xlen - 20), rd32(h + bsize - 4)});   // coff, uoff, clen, ulen
+        u += blks.back().ulen;
+        p += bsize;
+    }
+    return eof && blks.empty() && n ? "truncated BGZF block at end of file" : nullptr;
+}
+
+// Raw inflate of one BGZF block with zlib, the stream reused from block to block.
+struct ZlibRaw {
+    z_stream zs;
+    bool ok;
+    ZlibRaw() {
+        memset(&zs, 0, sizeof zs);
+        ok = inflateInit2(&zs, -15) == Z_OK;
+    }
+    ZlibRaw(const ZlibRaw &) = delete;
+    ~ZlibRaw() {
+        if (ok) inflateEnd(&zs);
+    }
+    bool block(const uint8_t *in, size_t clen, uint8_t *out, size_t ulen) {
+        if (!ok) return false;
+        inflateReset(&zs);
+        zs.next_in = const_cast<uint8_t *>(in);
+        zs.avail_in = (uInt)clen;
+        zs.next_out = out;
+        zs.avail_out = (uInt)ulen;
+        return inflate(&zs, Z_FINISH) == Z_STREAM_END && zs.total_out == ulen;
     }
 };
 
+// The opened BAM and its inflated byte stream.  The file is closed when the reader goes, after the helper
+// thread that reads it has finished; no caller closes it or waits for that thread by hand.
 struct BgzfReader {
-    FILE *f = nullptr;
-    int threads = 1;
+    FILE *f = nullptr;             // null: the file did not open
+    int threads = 1;               // (clamped to >= 1)
     std::vector<uint8_t> comp;     // compressed bytes not yet consumed
     bool eof = false;
     std::string err;
@@ -129,7 +195,8 @@ struct BgzfReader {
     // output buffers (from inf->alloc: pinned host memory, so the copies to and from the device
     // run at full speed); the next batch is read and inflated by a helper thread while the
     // caller parses the current one
-    const svth_inflater *inf = nullptr;
+    svth_inflater cfg{};                   // (the caller's, copied)
+    const svth_inflater *inf = nullptr;    // &cfg, or null: host threads inflate
     static constexpr size_t HEAD = 64ull << 20;   // room in front of a batch for the previous one's tail
     struct Buf {
         uint8_t *p = nullptr;
@@ -163,9 +230,27 @@ struct BgzfReader {
     double t_read = 0, t_scan = 0, t_alloc_r = 0, t_alloc = 0, t_inflate = 0, t_wait = 0;
     static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
+    BgzfReader(const char *path, int threads_, const svth_inflater *inf_) : threads(threads_ < 1 ? 1 : threads_) {
+        if (inf_) {
+            cfg = *inf_;
+            inf = &cfg;
+        }
+        f = fopen(path, "rb");
+        struct stat st;
+        if (f) fsize = fstat(fileno(f), &st) == 0 ? (uint64_t)st.st_size : 0;
+    }
+    BgzfReader(const BgzfReader &) = delete;
+    BgzfReader &operator=(const BgzfReader &) = delete;
     ~BgzfReader() {
-        drop_pending();
+        drop_pending();   // (the helper thread reads f)
         for (Buf *b : {&cins[0], &cins[1], &outs[0], &outs[1]}) release(*b);
+        if (f) fclose(f);
+    }
+    // The message of a failed read: the reader's own when it has one (once the helper thread, which may be
+    // the one that set it, has finished), else m.
+    std::string error(const std::string &m) {
+        drop_pending();
+        return err.empty() ? m : err;
     }
     void drop_pending() {
         if (pending.valid()) (void)pending.get();
@@ -256,33 +341,11 @@ struct BgzfReader {
         for (;;) {
             if (!eof && !read_batch(b, n, want)) { c.err = err; return c; }
             const double ts = now();
-            while (p + 18 <= n) {
-                const uint8_t *h = b.p + p;
-                if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) { c.err = "not a BGZF file (bad gzip header)"; return c; }
-                const uint16_t xlen = rd16(h + 10);
-                if (p + 12 + xlen > n) break;
-                size_t bsize = 0;
-                for (size_t x = 0; x + 4 <= xlen;) {
-                    const uint8_t *sf = h + 12 + x;
-                    const uint16_t slen = rd16(sf + 2);
-                    if (sf[0] == 66 && sf[1] == 67 && slen == 2) bsize = (size_t)rd16(sf + 4) + 1;
-                    x += 4 + slen;
-                }
-                if (!bsize || bsize < (size_t)xlen + 20) { c.err = "BGZF block without BC subfield"; return c; }
-                if (p + bsize > n) break;
-                svt_bgzf_block k;
-                k.coff = p + 12 + xlen;
-                k.clen = (uint32_t)(bsize - xlen - 20);
-                k.uoff = u;
-                k.ulen = rd32(b.p + p + bsize - 4);
-                c.blks.push_back(k);
-                u += k.ulen;
-                p += bsize;
-            }
+            const char *e = bgzf_scan(b.p, n, eof, p, u, c.blks);
             t_scan += now() - ts;
+            if (e) { c.err = e; return c; }
             if (!c.blks.empty() || eof) break;   // (else a single block larger than what was read so far)
         }
-        if (c.blks.empty() && n) { c.err = "truncated BGZF block at end of file"; return c; }
         c.p = p;
         c.u = u;
         c.ok = true;
@@ -352,7 +415,9 @@ struct BgzfReader {
             at = 0;
         }
         const size_t CHUNK = 64u << 20;
-        for (;;) {
+        std::vector<svt_bgzf_block> blks;
+        size_t p = 0, u = 0;
+        while (blks.empty()) {
             if (!eof) {
                 size_t old = comp.size();
                 comp.resize(old + CHUNK);
@@ -360,70 +425,38 @@ struct BgzfReader {
                 comp.resize(old + got);
                 if (got < CHUNK) eof = true;
             }
-            struct Blk { size_t clen, ulen, cdata; };
-            std::vector<Blk> blks;
-            size_t p = 0;
-            while (p + 18 <= comp.size()) {
-                const uint8_t *h = comp.data() + p;
-                if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) { err = "not a BGZF file (bad gzip header)"; return false; }
-                uint16_t xlen = rd16(h + 10);
-                if (p + 12 + xlen > comp.size()) break;
-                size_t bsize = 0;
-                for (size_t x = 0; x + 4 <= xlen;) {
-                    const uint8_t *sf = h + 12 + x;
-                    uint16_t slen = rd16(sf + 2);
-                    if (sf[0] == 66 && sf[1] == 67 && slen == 2) bsize = (size_t)rd16(sf + 4) + 1;
-                    x += 4 + slen;
-                }
-                if (!bsize) { err = "BGZF block without BC subfield"; return false; }
-                if (p + bsize > comp.size()) break;
-                blks.push_back({bsize - xlen - 20, rd32(comp.data() + p + bsize - 4), p + 12 + xlen});
-                p += bsize;
-            }
-            if (blks.empty()) {
-                if (eof) {
-                    if (!comp.empty()) err = "truncated BGZF block at end of file";
-                    return false;
-                }
-                continue;   // a single block larger than what was read so far
-            }
-            std::vector<size_t> uoff(blks.size() + 1, 0);
-            for (size_t i = 0; i < blks.size(); i++) uoff[i + 1] = uoff[i] + blks[i].ulen;
-            const size_t base = out.size();
-            if (!out.resize(base + uoff.back())) { err = "out of host memory"; return false; }
-            std::atomic<int> bad{0};
-            const Inflater &inf = inflater();
-            parallel_for(threads, blks.size() * 4096, [&](size_t b0, size_t b1) {
-                if (inf.fast()) {
-                    void *d = inf.ld_alloc();
-                    if (!d) { bad = 1; return; }
-                    for (size_t i = b0 / 4096; i < b1 / 4096; i++) {
-                        size_t got = 0;
-                        int rc = inf.ld_dec(d, comp.data() + blks[i].cdata, blks[i].clen, out.data() + base + uoff[i],
-                                            blks[i].ulen, &got);
-                        if (rc != 0 || got != blks[i].ulen) bad = 1;
-                    }
-                    inf.ld_free(d);
-                    return;
-                }
-                z_stream zs;
-                memset(&zs, 0, sizeof zs);
-                if (inflateInit2(&zs, -15) != Z_OK) { bad = 1; return; }
-                for (size_t i = b0 / 4096; i < b1 / 4096; i++) {
-                    inflateReset(&zs);
-                    zs.next_in = comp.data() + blks[i].cdata;
-                    zs.avail_in = (uInt)blks[i].clen;
-                    zs.next_out = out.data() + base + uoff[i];
-                    zs.avail_out = (uInt)blks[i].ulen;
-                    int rc = inflate(&zs, Z_FINISH);
-                    if (rc != Z_STREAM_END || zs.total_out != blks[i].ulen) bad = 1;
-                }
-                inflateEnd(&zs);
-            });
-            if (bad) { err = "corrupt BGZF block (inflate failed)"; return false; }
-            comp.erase(comp.begin(), comp.begin() + (ptrdiff_t)p);
-            return true;
+            if (comp.empty()) return false;   // end of file
+            if (const char *e = bgzf_scan(comp.data(), comp.size(), eof, p, u, blks)) { err = e; return false; }
+            // (no block yet and not at the end: a single block larger than what was read so far)
         }
+        const size_t base = out.size();
+        if (!out.resize(base + u)) { err = "out of host memory"; return false; }
+        if (!inflate_host(blks, out.data() + base)) { err = "corrupt BGZF block (inflate failed)"; return false; }
+        comp.erase(comp.begin(), comp.begin() + (ptrdiff_t)p);
+        return true;
+    }
+
+    // Host threads: the blocks of comp raw-inflated to dst + uoff (libdeflate when present, else zlib).
+    bool inflate_host(const std::vector<svt_bgzf_block> &blks, uint8_t *dst) {
+        std::atomic<int> bad{0};
+        const Inflater &dec = inflater();
+        parallel_for(threads, blks.size() * 4096, [&](size_t b0, size_t b1) {
+            if (dec.fast()) {
+                void *d = dec.ld_alloc();
+                if (!d) { bad = 1; return; }
+                for (size_t i = b0 / 4096; i < b1 / 4096; i++) {
+                    const svt_bgzf_block &k = blks[i];
+                    size_t got = 0;
+                    if (dec.ld_dec(d, comp.data() + k.coff, k.clen, dst + k.uoff, k.ulen, &got) != 0 || got != k.ulen) bad = 1;
+                }
+                dec.ld_free(d);
+                return;
+            }
+            ZlibRaw z;
+            for (size_t i = b0 / 4096; i < b1 / 4096; i++)
+                if (!z.block(comp.data() + blks[i].coff, blks[i].clen, dst + blks[i].uoff, blks[i].ulen)) bad = 1;
+        });
+        return !bad;
     }
 };
 
@@ -473,40 +506,6 @@ struct BaiLinear {
     }
 };
 
-// Growable array without value-initialisation; large blocks grow by realloc (mremap on
-// glibc), so appending a chunk never re-copies or zero-fills what is already there.
-template <typename T>
-struct RawVec {
-    T *p = nullptr;
-    size_t n = 0, cap = 0;
-    RawVec() = default;
-    RawVec(const RawVec &) = delete;
-    RawVec &operator=(const RawVec &) = delete;
-    ~RawVec() { free(p); }
-    bool resize(size_t m) {
-        if (m > cap) {
-            size_t c = std::max(m, cap + cap / 2 + 1024);
-            T *q = (T *)realloc(p, c * sizeof(T));
-            if (!q) return false;
-            p = q;
-            cap = c;
-        }
-        n = m;
-        return true;
-    }
-    bool push_back(T v) {
-        if (!resize(n + 1)) return false;
-        p[n - 1] = v;
-        return true;
-    }
-    size_t size() const { return n; }
-    T *data() { return p; }
-    const T *data() const { return p; }
-    T &operator[](size_t i) { return p[i]; }
-    const T &operator[](size_t i) const { return p[i]; }
-    void swap(RawVec &o) { std::swap(p, o.p); std::swap(n, o.n); std::swap(cap, o.cap); }
-};
-
 }  // namespace
 
 struct svth_bam {
@@ -535,13 +534,22 @@ namespace {
 constexpr uint32_t OP_I = 1, INS_MIN = 50;   // the I ops that carry a sequence (include/svtrek_gpu.h: I >= 50)
 
 // A record's I >= 50 ops: their count and the sum of their lengths.
-inline void ins_census(const bamrec::View &v, uint32_t &cnt, uint64_t &bases) {
+inline void ins_census(const bamrec::View &v, uint64_t &cnt, uint64_t &bases) {
     cnt = 0;
     bases = 0;
     for (uint32_t j = 0; j < v.n; j++) {
         const uint32_t w = bamrec::rd32(v.cig + 4ull * j);
         if ((w & 0xfu) == OP_I && (w >> 4) >= INS_MIN) { cnt++; bases += w >> 4; }
     }
+}
+
+// Where a record's SEQ and aux fields start (r: the record after its block_size word), behind the name and the
+// stored CIGAR (the placeholder, when the CIGAR itself sits in a CG tag).  aux is null for l_seq < 0.
+struct SeqAux { const uint8_t *seq, *aux; int64_t l_seq; };
+inline SeqAux seq_aux(const uint8_t *r) {
+    const int64_t l_seq = (int32_t)rd32(r + 16);
+    const uint8_t *seq = r + 32 + r[8] + 4ull * rd16(r + 12);
+    return {seq, l_seq < 0 ? nullptr : seq + (size_t)(l_seq + 1) / 2 + (size_t)l_seq, l_seq};
 }
 
 // The lengths and bases of those ops (r: the record after its block_size word, bs: that word).  The
@@ -551,10 +559,9 @@ inline void ins_census(const bamrec::View &v, uint32_t &cnt, uint64_t &bases) {
 // a SEQ that runs past the record) keeps its CIGAR length with every base 4.
 inline void ins_extract(const bamrec::View &v, const uint8_t *r, uint32_t bs, uint32_t *len_out, uint8_t *base_out) {
     static const uint8_t NT4[16] = {4, 0, 1, 4, 2, 4, 4, 4, 3, 4, 4, 4, 4, 4, 4, 4};
-    const uint32_t l_qname = r[8], n_stored = bamrec::rd16(r + 12);
-    int64_t l_seq = (int32_t)bamrec::rd32(r + 16);
-    const uint8_t *seq = r + 32 + l_qname + 4ull * n_stored;
-    if (l_seq < 0 || seq + (size_t)(l_seq + 1) / 2 > r + bs) l_seq = 0;
+    const SeqAux sa = seq_aux(r);
+    const uint8_t *seq = sa.seq;
+    const int64_t l_seq = sa.l_seq < 0 || seq + (size_t)(sa.l_seq + 1) / 2 > r + bs ? 0 : sa.l_seq;
     uint64_t q = 0;
     for (uint32_t j = 0; j < v.n; j++) {
         const uint32_t w = bamrec::rd32(v.cig + 4ull * j), op = w & 0xfu, len = w >> 4;
@@ -576,10 +583,8 @@ inline void ins_extract(const bamrec::View &v, const uint8_t *r, uint32_t bs, ui
 // (or aux fields that cannot be walked).
 inline bool find_sa(const uint8_t *r, uint32_t bs, const uint8_t **beg, const uint8_t **vend) {
     const uint8_t *end = r + bs;
-    const uint32_t l_qname = r[8], n_stored = bamrec::rd16(r + 12);
-    const int64_t l_seq = (int32_t)bamrec::rd32(r + 16);
-    if (l_seq < 0) return false;
-    const uint8_t *p = r + 32 + l_qname + 4ull * n_stored + (size_t)(l_seq + 1) / 2 + (size_t)l_seq;
+    const uint8_t *p = seq_aux(r).aux;
+    if (!p) return false;
     while (p < end && end - p >= 3) {
         const char t0 = (char)p[0], t1 = (char)p[1], ty = (char)p[2];
         p += 3;
@@ -690,10 +695,385 @@ bool parse_sa(const uint8_t *p, const uint8_t *end, const std::unordered_map<std
     return true;
 }
 
+// The BAM header (SAM spec 4.2: magic, text, n_ref, the reference list) read through take(k): "make k more
+// bytes available at the cursor, hand them out and move past them" (null: there are no more).  Returns the
+// error, or an empty string; `suffix` ends the two messages about a header that stops early.
+template <typename Take>
+std::string parse_header(Take &&take, const char *suffix, int32_t &n_ref, std::vector<std::string> *names) {
+    const uint8_t *p = take(8);
+    if (!p || memcmp(p, "BAM\1", 4) != 0) return "not a BAM file";
+    const size_t l_text = rd32(p + 4);
+    if (!(p = take(l_text + 4))) return std::string("truncated BAM header") + suffix;
+    n_ref = (int32_t)rd32(p + l_text);
+    if (n_ref < 0) return "bad n_ref";
+    for (int32_t i = 0; i < n_ref; i++) {
+        const size_t ln = (p = take(4)) ? rd32(p) : 0;
+        if (!p || !(p = take(ln + 4))) return std::string("truncated reference list") + suffix;
+        if (names) names->emplace_back((const char *)p, ln ? ln - 1 : 0);
+    }
+    return {};
+}
+
+// One chunk of whole records in the inflated buffer: what the two passes over it share.
+struct Chunk {
+    const uint8_t *buf = nullptr;     // roff counts from here
+    std::vector<size_t> roff;         // each record, after its block_size word
+    std::vector<bamrec::View> views;
+    std::vector<size_t> slot;         // its index among the kept reads of the file ((size_t)-1: not kept)
+    std::vector<uint64_t> off;        // [nr + 1] its CIGAR's place in the chunk's share of the arena
+    size_t nr = 0, end = 0;           // the records taken; the buffer offset behind them
+    const uint8_t *rec(size_t i) const { return buf + roff[i]; }
+    uint32_t bs(size_t i) const { return rd32(buf + roff[i] - 4); }
+};
+
+// The reads of `v` in the order idx.
+template <typename T>
+bool permute(RawVec<T> &v, const std::vector<size_t> &idx) {
+    RawVec<T> w;
+    if (!w.resize(idx.size())) return false;
+    for (size_t k = 0; k < idx.size(); k++) w[k] = v[idx[k]];
+    v.swap(w);
+    return true;
+}
+
+// Rows of varying length -- row i is data[off[i], off[i + 1]) -- in the order idx.
+template <typename T>
+bool permute_rows(RawVec<uint64_t> &off, RawVec<T> &data, const std::vector<size_t> &idx) {
+    RawVec<uint64_t> off2;
+    RawVec<T> data2;
+    if (!off2.resize(idx.size() + 1) || !data2.resize(data.size())) return false;
+    uint64_t w = 0;
+    for (size_t k = 0; k < idx.size(); k++) {
+        const uint64_t o = off[idx[k]], m = off[idx[k] + 1] - o;
+        off2[k] = w;
+        if (m) memcpy(data2.data() + w, data.data() + o, sizeof(T) * m);
+        w += m;
+    }
+    off2[idx.size()] = w;
+    off.swap(off2);
+    data.swap(data2);
+    return true;
+}
+
+// svth_bam_read_seq's product: the inserted bases of the kept reads' I >= 50 ops, in (read, op) order.
+struct InsSeq {
+    svth_bam &b;
+    std::vector<uint64_t> ioff, iboff;   // [nr + 1] where the ops / the bases of each record of the chunk go
+    explicit InsSeq(svth_bam &b_) : b(b_) {}
+
+    // Before the parallel copy: the census of the chunk and room for its ops and bases; false: out of memory.
+    bool size(const Chunk &c, int threads) {
+        ioff.assign(c.nr + 1, 0);
+        iboff.assign(c.nr + 1, 0);
+        parallel_for(threads, c.nr, [&](size_t i0, size_t i1) {
+            for (size_t i = i0; i < i1; i++)
+                if (c.views[i].ok) ins_census(c.views[i], ioff[i + 1], iboff[i + 1]);
+        });
+        ioff[0] = b.ins_len.size();
+        iboff[0] = b.ins_bases.size();
+        for (size_t i = 0; i < c.nr; i++) {
+            ioff[i + 1] += ioff[i];
+            iboff[i + 1] += iboff[i];
+        }
+        return b.ins_cnt.resize(b.pos.size()) && b.ins_len.resize(ioff[c.nr]) && b.ins_bases.resize(iboff[c.nr]);
+    }
+    // Inside it, for a kept record.
+    void extract(const Chunk &c, size_t i) {
+        const uint64_t cnt = ioff[i + 1] - ioff[i];
+        b.ins_cnt[c.slot[i]] = (uint32_t)cnt;
+        if (cnt) ins_extract(c.views[i], c.rec(i), c.bs(i), b.ins_len.data() + ioff[i], b.ins_bases.data() + iboff[i]);
+    }
+    // The ops' offsets, and the bases, in the final (read, op) order: idx is the reads' reorder (empty: none).
+    bool finish(const std::vector<size_t> &idx) {
+        if (!idx.empty()) {   // per file-order read its first op and first base, then both in the reads' final order
+            const size_t n = idx.size();
+            RawVec<uint64_t> first, fbase;
+            if (!first.resize(n + 1) || !fbase.resize(n + 1)) return false;
+            first[0] = fbase[0] = 0;
+            for (size_t i = 0, k = 0; i < n; i++) {
+                first[i + 1] = first[i] + b.ins_cnt[i];
+                fbase[i + 1] = fbase[i];
+                for (; k < first[i + 1]; k++) fbase[i + 1] += b.ins_len[k];
+            }
+            if (!permute_rows(fbase, b.ins_bases, idx) || !permute_rows(first, b.ins_len, idx)) return false;
+        }
+        if (!b.ins_off.resize(b.ins_len.size() + 1)) return false;
+        b.ins_off[0] = 0;
+        for (size_t k = 0; k < b.ins_len.size(); k++) b.ins_off[k + 1] = b.ins_off[k] + b.ins_len[k];
+        b.has_seq = true;
+        return true;
+    }
+};
+
+// svth_bam_read_sa's product: the segment table of the kept reads that carry an SA:Z tag.
+struct SaTable {
+    svth_bam &b;
+    std::unordered_map<std::string, int32_t> tids;
+    // per record of the chunk its rows (the own segment first; empty: no SA tag, or a malformed one)
+    std::vector<std::vector<svt_junction_seg>> rows;
+    std::vector<uint8_t> bad;
+    explicit SaTable(svth_bam &b_) : b(b_) {}
+
+    void names() {
+        b.sa_off.assign(1, 0);
+        for (size_t t = 0; t < b.names.size(); t++) tids.emplace(b.names[t], (int32_t)t);   // (the first of equal names)
+    }
+    // Before the parallel copy.
+    void size(const Chunk &c) {
+        rows.assign(c.nr, {});
+        bad.assign(c.nr, 0);
+    }
+    // Inside it, for a kept record.
+    void extract(const Chunk &c, size_t i) {
+        const bamrec::View &v = c.views[i];
+        const uint8_t *sa0, *sa1;
+        if (!find_sa(c.rec(i), c.bs(i), &sa0, &sa1)) return;
+        SegLen g;
+        for (uint32_t j = 0; j < v.n; j++) {
+            const uint32_t w = rd32(v.cig + 4ull * j);
+            seg_op(g, w & 0xfu, w >> 4);
+        }
+        if (v.flag & 4u) g.rlen = 0;   // (bam_endpos: an unmapped record covers no reference base)
+        rows[i].resize(1);
+        if (!seg_make(g, v.tid, (v.flag >> 4) & 1u, (uint64_t)v.pos, &rows[i][0]) || !parse_sa(sa0, sa1, tids, rows[i])) {
+            rows[i].clear();
+            bad[i] = 1;
+        }
+    }
+    // Behind it: the chunk's rows appended to the table, in file order.
+    void collect(const Chunk &c) {
+        for (size_t i = 0; i < c.nr; i++) {
+            b.n_sa_malformed += bad[i];
+            if (rows[i].empty()) continue;
+            b.sa_read.push_back(c.slot[i]);
+            b.sa_seg.insert(b.sa_seg.end(), rows[i].begin(), rows[i].end());
+            b.sa_off.push_back(b.sa_seg.size());
+        }
+    }
+    // The table in the final read order, `read` holding final indices: idx is the reads' reorder (empty: none).
+    void finish(const std::vector<size_t> &idx) {
+        b.has_sa = true;
+        if (idx.empty()) return;
+        std::vector<uint64_t> inv(idx.size()), read, off(1, 0);
+        std::vector<svt_junction_seg> seg;
+        for (size_t k = 0; k < idx.size(); k++) inv[idx[k]] = k;
+        std::vector<size_t> ord(b.sa_read.size());
+        std::iota(ord.begin(), ord.end(), 0);
+        std::sort(ord.begin(), ord.end(), [&](size_t x, size_t y) { return inv[b.sa_read[x]] < inv[b.sa_read[y]]; });
+        for (size_t j : ord) {
+            read.push_back(inv[(size_t)b.sa_read[j]]);
+            seg.insert(seg.end(), b.sa_seg.begin() + (ptrdiff_t)b.sa_off[j], b.sa_seg.begin() + (ptrdiff_t)b.sa_off[j + 1]);
+            off.push_back(seg.size());
+        }
+        b.sa_read.swap(read);
+        b.sa_off.swap(off);
+        b.sa_seg.swap(seg);
+    }
+};
+
 constexpr int WANT_SEQ = 1, WANT_SA = 2;
 
+// One read of a BAM into a svth_bam, as stages.  A stage that fails leaves its message in err and returns
+// false; the pileup, the file and the buffers go with the Ingest.
+struct Ingest {
+    BgzfReader rd;
+    const int want;                  // WANT_* bits
+    const bool region;               // a read up to (tid1, end1); `done` once that is reached
+    const int32_t tid1;
+    const int64_t end1;
+    std::unique_ptr<svth_bam> b{new svth_bam()};
+    InsSeq ins{*b};
+    SaTable sa{*b};
+    Bytes buf;                       // inflated bytes, consumed up to `at`
+    size_t at = 0;
+    int32_t n_ref = 0;
+    RawVec<int32_t> tid_of;          // per kept read
+    uint64_t narena = 0;             // CIGAR words kept so far
+    bool done = false;
+    std::string err;
+
+    Ingest(const char *path, int threads, const svth_inflater *inf, int want_, bool region_, int32_t tid1_, int64_t end1_)
+        : rd(path, threads, inf), want(want_), region(region_), tid1(tid1_), end1(end1_) {}
+
+    bool fail(const char *m) { err = m; return false; }
+    bool need(size_t k) {
+        while (buf.size() - at < k)
+            if (!rd.next(buf, at)) return false;
+        return true;
+    }
+
+    bool header() {
+        err = parse_header([&](size_t k) -> const uint8_t * {
+            if (!need(k)) return nullptr;
+            at += k;
+            return buf.data() + at - k;
+        }, "", n_ref, &b->names);
+        if (err.empty() && (want & WANT_SA)) sa.names();
+        return err.empty();
+    }
+
+    // A region read continues at the BAI's linear-index offset of (tid0, beg0).
+    bool seek_region(const char *path, int32_t tid0, int64_t beg0) {
+        if (!region) return true;
+        BaiLinear bai;
+        if (!bai.load(std::string(path) + ".bai", err)) return false;
+        uint64_t voff = 0;
+        if (!bai.start(tid0, beg0, voff)) {   // no record at or after the region start
+            done = true;
+            return true;
+        }
+        if (!rd.seek(voff >> 16)) return fail("cannot seek in BAM");
+        buf.clear();
+        at = 0;
+        const size_t uo = (size_t)(voff & 0xffff);
+        if (uo && !need(uo)) return fail("BAI offset past the end of the BAM");
+        at += uo;
+        return true;
+    }
+
+    // The sequential boundary scan over the complete records in the buffer.  None (c.nr == 0): one record
+    // larger than the buffer, which was read on.
+    bool scan(Chunk &c) {
+        c.roff.clear();
+        size_t p = at;
+        while (buf.size() - p >= 4) {
+            const uint32_t bs = rd32(buf.data() + p);
+            if (bs < 32) return fail("corrupt BAM record (block_size < 32)");
+            if (buf.size() - p < 4 + (size_t)bs) break;
+            c.roff.push_back(p + 4);
+            p += 4 + bs;
+        }
+        if (c.roff.empty() && !need(4 + (size_t)rd32(buf.data() + at))) return fail("truncated BAM record");
+        c.buf = buf.data();
+        c.nr = c.roff.size();
+        c.end = p;
+        return true;
+    }
+
+    // Pass 1 (parallel): every record's CIGAR located; then the region cut: in a sorted file the first record
+    // past (tid1, end1) ends the read.
+    void view(Chunk &c) {
+        c.views.resize(c.nr);
+        parallel_for(rd.threads, c.nr, [&](size_t i0, size_t i1) {
+            for (size_t i = i0; i < i1; i++) c.views[i] = bamrec::view(c.rec(i), c.bs(i), n_ref);
+        });
+        if (!region) return;
+        for (size_t i = 0; i < c.nr; i++) {
+            const int32_t t = (int32_t)rd32(c.rec(i)), ps = (int32_t)rd32(c.rec(i) + 4);
+            if (t < 0 || t > tid1 || (t == tid1 && (int64_t)ps >= end1)) {
+                c.nr = i;
+                c.end = c.roff[i] - 4;
+                done = true;
+                break;
+            }
+        }
+    }
+
+    // Where every record of the chunk goes (prefix offsets), and room for it in the columns and products.
+    bool layout(Chunk &c) {
+        size_t k = b->pos.size();
+        c.off.assign(c.nr + 1, 0);
+        c.slot.assign(c.nr, 0);
+        for (size_t i = 0; i < c.nr; i++) {
+            const bamrec::View &v = c.views[i];
+            if (v.bad) return fail("corrupt BAM record");
+            if (v.cg) b->n_cg++;
+            c.off[i + 1] = c.off[i] + (v.ok ? v.n : 0);
+            c.slot[i] = v.ok ? k++ : (size_t)-1;
+        }
+        b->n_records += (int64_t)c.nr;
+        if (!b->pos.resize(k) || !b->endpos.resize(k) || !b->clip.resize(k) || !tid_of.resize(k) || !b->cig_off.resize(k) ||
+            !b->cigar.resize(narena + c.off[c.nr]))
+            return fail("out of host memory");
+        if ((want & WANT_SEQ) && !ins.size(c, rd.threads)) return fail("out of host memory");
+        if (want & WANT_SA) sa.size(c);
+        return true;
+    }
+
+    // Pass 2 (parallel): the kept records copied into the columnar arrays, the products extracted.
+    void copy(const Chunk &c) {
+        parallel_for(rd.threads, c.nr, [&](size_t i0, size_t i1) {
+            for (size_t i = i0; i < i1; i++) {
+                const bamrec::View &v = c.views[i];
+                if (!v.ok) continue;
+                const size_t k = c.slot[i];
+                if (want & WANT_SA) sa.extract(c, i);
+                if (v.n) memcpy(b->cigar.data() + narena + c.off[i], v.cig, 4ull * v.n);
+                b->pos[k] = v.pos;
+                b->endpos[k] = bamrec::endpos(v);   // htslib bam_endpos
+                b->clip[k] = (uint8_t)v.clip;
+                b->cig_off[k] = narena + c.off[i];
+                tid_of[k] = v.tid;
+                if (want & WANT_SEQ) ins.extract(c, i);
+            }
+        });
+    }
+
+    void commit(const Chunk &c) {
+        if (want & WANT_SA) sa.collect(c);
+        narena += c.off[c.nr];
+        at = c.end;
+    }
+
+    // The records, chunk by chunk; then the stage times (t_start: when the read began).
+    bool records(double t_start) {
+        Chunk c;
+        while (!done) {
+            if (buf.size() - at < 4 && !need(4)) break;   // clean EOF
+            if (!scan(c)) return false;
+            if (!c.nr) continue;
+            view(c);
+            if (!layout(c)) return false;
+            copy(c);
+            commit(c);
+        }
+        err = rd.error("");
+        if (!err.empty()) return false;
+        const double st[6] = {rd.t_read, rd.t_scan, rd.t_alloc_r + rd.t_alloc, rd.t_inflate, rd.t_wait, BgzfReader::now() - t_start};
+        memcpy(b->stage_s, st, sizeof st);
+        return true;
+    }
+
+    // The sortedness check, the one reorder -- computed once, handed to the columns and both products -- and
+    // the per-tid ranges.
+    bool finish() {
+        const size_t n = b->pos.size();
+        if (!b->cig_off.resize(n + 1)) return fail("out of host memory");
+        b->cig_off[n] = narena;
+        bool sorted = true;
+        for (size_t i = 1; i < n && sorted; i++)
+            sorted = tid_of[i] > tid_of[i - 1] || (tid_of[i] == tid_of[i - 1] && b->pos[i] >= b->pos[i - 1]);
+        std::vector<size_t> idx;   // the final order of the reads; empty: the file's own
+        if (!sorted) {
+            idx.resize(n);
+            std::iota(idx.begin(), idx.end(), 0);
+            std::stable_sort(idx.begin(), idx.end(), [&](size_t x, size_t y) {
+                return tid_of[x] != tid_of[y] ? tid_of[x] < tid_of[y] : b->pos[x] < b->pos[y];
+            });
+        }
+        if (!sorted && !(permute_rows(b->cig_off, b->cigar, idx) && permute(b->pos, idx) && permute(b->endpos, idx) &&
+                         permute(b->clip, idx)))
+            return fail("out of host memory");
+        b->tid_off.assign((size_t)n_ref + 1, 0);   // (a count per tid: the order of tid_of does not matter)
+        for (size_t k = 0; k < n; k++) b->tid_off[(size_t)tid_of[k] + 1]++;
+        for (int32_t t = 0; t < n_ref; t++) b->tid_off[(size_t)t + 1] += b->tid_off[(size_t)t];
+        if ((want & WANT_SEQ) && !ins.finish(idx)) return fail("out of host memory");
+        if (want & WANT_SA) sa.finish(idx);
+        return true;
+    }
+};
+
 svth_bam *bam_read_impl(const char *path, int threads, int32_t tid0, int64_t beg0, int32_t tid1, int64_t end1,
-                        const svth_inflater *inf, int want, char *err, size_t errcap);
+                        const svth_inflater *inf, int want, char *err, size_t errcap) {
+    const double t_start = BgzfReader::now();
+    Ingest in(path, threads, inf && inf->inflate ? inf : nullptr, want, tid0 >= 0, tid1, end1);
+    std::string m;
+    if (!in.rd.f) m = std::string("cannot open BAM: ") + path;
+    else if (in.header() && in.seek_region(path, tid0, beg0) && in.records(t_start) && in.finish()) return in.b.release();
+    else m = in.rd.error(in.err);
+    if (err && errcap) snprintf(err, errcap, "%s", m.c_str());
+    return nullptr;
+}
 
 }  // namespace
 
@@ -742,314 +1122,6 @@ int svth_bam_insseq(const svth_bam *b, svt_insseq_view *out) {
     return 1;
 }
 
-}  // extern "C"
-
-namespace {
-
-svth_bam *bam_read_impl(const char *path, int threads, int32_t tid0, int64_t beg0, int32_t tid1, int64_t end1,
-                        const svth_inflater *inf, int want, char *err, size_t errcap) {
-    const bool region = tid0 >= 0, want_seq = (want & WANT_SEQ) != 0, want_sa = (want & WANT_SA) != 0;
-    auto fail = [&](const std::string &m) -> svth_bam * {
-        if (err && errcap) snprintf(err, errcap, "%s", m.c_str());
-        return nullptr;
-    };
-    const double t_start = BgzfReader::now();
-    FILE *f = fopen(path, "rb");
-    if (!f) return fail(std::string("cannot open BAM: ") + path);
-    BgzfReader rd;
-    rd.f = f;
-    rd.threads = threads < 1 ? 1 : threads;
-    rd.inf = inf && inf->inflate ? inf : nullptr;
-    {
-        struct stat st;
-        rd.fsize = fstat(fileno(f), &st) == 0 ? (uint64_t)st.st_size : 0;
-    }
-    Bytes buf;
-    size_t at = 0;
-    auto need = [&](size_t k) -> bool {
-        while (buf.size() - at < k)
-            if (!rd.next(buf, at)) return false;
-        return true;
-    };
-    svth_bam *b = new svth_bam();
-    auto bail = [&](const std::string &m) {
-        rd.drop_pending();   // (the helper thread reads f)
-        fclose(f);
-        delete b;
-        return fail(rd.err.empty() ? m : rd.err);
-    };
-    // header
-    if (!need(8) || memcmp(buf.data() + at, "BAM\1", 4) != 0) return bail("not a BAM file");
-    const uint32_t l_text = rd32(buf.data() + at + 4);
-    at += 8;
-    if (!need((size_t)l_text + 4)) return bail("truncated BAM header");
-    at += l_text;
-    const int32_t n_ref = (int32_t)rd32(buf.data() + at);
-    at += 4;
-    if (n_ref < 0) return bail("bad n_ref");
-    for (int32_t i = 0; i < n_ref; i++) {
-        if (!need(4)) return bail("truncated reference list");
-        const uint32_t ln = rd32(buf.data() + at);
-        if (!need(4 + (size_t)ln + 4)) return bail("truncated reference list");
-        b->names.emplace_back((const char *)buf.data() + at + 4, ln ? ln - 1 : 0);
-        at += 4 + ln + 4;
-    }
-    // region: continue at the BAI's linear-index offset of (tid0, beg0)
-    bool done = false;
-    if (region) {
-        BaiLinear bai;
-        std::string e;
-        if (!bai.load(std::string(path) + ".bai", e)) return bail(e);
-        uint64_t voff = 0;
-        if (!bai.start(tid0, beg0, voff)) done = true;   // no record at or after the region start
-        else {
-            if (!rd.seek(voff >> 16)) return bail("cannot seek in BAM");
-            buf.clear();
-            at = 0;
-            const size_t uo = (size_t)(voff & 0xffff);
-            if (uo && !need(uo)) return bail("BAI offset past the end of the BAM");
-            at += uo;
-        }
-    }
-    // records, chunk by chunk
-    RawVec<int32_t> tid_of;
-    std::vector<uint8_t> rec_ok;
-    std::vector<uint16_t> flag;
-    uint64_t narena = 0;
-    std::vector<size_t> roff;
-    std::vector<uint32_t> rlen;
-    std::vector<bamrec::View> views;
-    std::vector<uint32_t> insn;          // want_seq: per record its I >= 50 ops ...
-    std::vector<uint64_t> insb;          //           ... and their bases
-    uint64_t n_ins = 0, n_insb = 0;
-    // want_sa: per record of a chunk its rows (the own segment first; empty: no SA tag, or a malformed one),
-    // then per table record in file order its kept-read index and rows
-    std::unordered_map<std::string, int32_t> tids;
-    std::vector<std::vector<svt_junction_seg>> sa_rows;
-    std::vector<uint8_t> sa_bad;
-    std::vector<uint64_t> sa_read, sa_off(1, 0);
-    std::vector<svt_junction_seg> sa_seg;
-    if (want_sa)
-        for (int32_t t = 0; t < n_ref; t++) tids.emplace(b->names[(size_t)t], t);   // (the first of equal names)
-    while (!done) {
-        if (buf.size() - at < 4 && !need(4)) break;   // clean EOF
-        // sequential boundary scan over the complete records in the buffer
-        roff.clear();
-        size_t p = at;
-        while (buf.size() - p >= 4) {
-            const uint32_t bs = rd32(buf.data() + p);
-            if (bs < 32) return bail("corrupt BAM record (block_size < 32)");
-            if (buf.size() - p < 4 + (size_t)bs) break;
-            roff.push_back(p + 4);
-            p += 4 + bs;
-        }
-        if (roff.empty()) {   // one record larger than the buffer: read on
-            if (!need(4 + (size_t)rd32(buf.data() + at))) return bail("truncated BAM record");
-            continue;
-        }
-        // pass 1 (parallel): locate every record's CIGAR
-        size_t nr = roff.size();
-        views.resize(nr);
-        parallel_for(rd.threads, nr, [&](size_t i0, size_t i1) {
-            for (size_t i = i0; i < i1; i++)
-                views[i] = bamrec::view(buf.data() + roff[i], rd32(buf.data() + roff[i] - 4), n_ref);
-        });
-        if (want_seq) {
-            insn.assign(nr, 0);
-            insb.assign(nr, 0);
-            parallel_for(rd.threads, nr, [&](size_t i0, size_t i1) {
-                for (size_t i = i0; i < i1; i++)
-                    if (views[i].ok && !views[i].bad) ins_census(views[i], insn[i], insb[i]);
-            });
-        }
-        if (region)   // sorted file: the first record past (tid1, end1) ends the read
-            for (size_t i = 0; i < nr; i++) {
-                const int32_t t = (int32_t)rd32(buf.data() + roff[i]), ps = (int32_t)rd32(buf.data() + roff[i] + 4);
-                if (t < 0 || t > tid1 || (t == tid1 && (int64_t)ps >= end1)) {
-                    nr = i;
-                    done = true;
-                    p = roff[i] - 4;
-                    break;
-                }
-            }
-        // prefix offsets, then pass 2 (parallel): copy into the columnar arrays
-        const size_t base = b->pos.size();
-        size_t kept = 0;
-        for (size_t i = 0; i < nr; i++) {
-            if (views[i].bad) return bail("corrupt BAM record");
-            if (views[i].ok) kept++;
-            if (views[i].cg) b->n_cg++;
-        }
-        b->n_records += (int64_t)nr;
-        std::vector<uint64_t> off(nr + 1, 0);
-        std::vector<size_t> slot(nr, 0);
-        for (size_t i = 0, k = base; i < nr; i++) {
-            off[i + 1] = off[i] + (views[i].ok ? views[i].n : 0);
-            slot[i] = views[i].ok ? k++ : (size_t)-1;
-        }
-        if (!b->pos.resize(base + kept) || !b->endpos.resize(base + kept) || !b->clip.resize(base + kept) ||
-            !tid_of.resize(base + kept) || !b->cig_off.resize(base + kept) || !b->cigar.resize(narena + off[nr]))
-            return bail("out of host memory");
-        std::vector<uint64_t> ioff, iboff;   // want_seq: where each record's ops / bases go
-        if (want_seq) {
-            ioff.assign(nr + 1, n_ins);
-            iboff.assign(nr + 1, n_insb);
-            for (size_t i = 0; i < nr; i++) {
-                ioff[i + 1] = ioff[i] + (views[i].ok ? insn[i] : 0);
-                iboff[i + 1] = iboff[i] + (views[i].ok ? insb[i] : 0);
-            }
-            if (!b->ins_cnt.resize(base + kept) || !b->ins_len.resize(ioff[nr]) || !b->ins_bases.resize(iboff[nr]))
-                return bail("out of host memory");
-            n_ins = ioff[nr];
-            n_insb = iboff[nr];
-        }
-        if (want_sa) {
-            sa_rows.assign(nr, {});
-            sa_bad.assign(nr, 0);
-        }
-        parallel_for(rd.threads, nr, [&](size_t i0, size_t i1) {
-            for (size_t i = i0; i < i1; i++) {
-                const bamrec::View &v = views[i];
-                if (!v.ok) continue;
-                const size_t k = slot[i];
-                const uint8_t *sa0, *sa1;
-                if (want_sa && find_sa(buf.data() + roff[i], rd32(buf.data() + roff[i] - 4), &sa0, &sa1)) {
-                    SegLen g;
-                    for (uint32_t j = 0; j < v.n; j++) {
-                        const uint32_t w = bamrec::rd32(v.cig + 4ull * j);
-                        seg_op(g, w & 0xfu, w >> 4);
-                    }
-                    if (v.flag & 4u) g.rlen = 0;   // (bam_endpos: an unmapped record covers no reference base)
-                    std::vector<svt_junction_seg> &rows = sa_rows[i];
-                    rows.resize(1);
-                    if (!seg_make(g, v.tid, (v.flag >> 4) & 1u, (uint64_t)v.pos, &rows[0]) || !parse_sa(sa0, sa1, tids, rows)) {
-                        rows.clear();
-                        sa_bad[i] = 1;
-                    }
-                }
-                uint32_t *dst = b->cigar.data() + narena + off[i];
-                if (v.n) memcpy(dst, v.cig, 4ull * v.n);
-                b->pos[k] = v.pos;
-                b->endpos[k] = bamrec::endpos(v);   // htslib bam_endpos
-                b->clip[k] = (uint8_t)v.clip;
-                b->cig_off[k] = narena + off[i];
-                tid_of[k] = v.tid;
-                if (want_seq) {
-                    b->ins_cnt[k] = insn[i];
-                    if (insn[i])
-                        ins_extract(v, buf.data() + roff[i], rd32(buf.data() + roff[i] - 4), b->ins_len.data() + ioff[i],
-                                    b->ins_bases.data() + iboff[i]);
-                }
-            }
-        });
-        if (want_sa)
-            for (size_t i = 0; i < nr; i++) {
-                b->n_sa_malformed += sa_bad[i];
-                if (sa_rows[i].empty()) continue;
-                sa_read.push_back(slot[i]);
-                sa_seg.insert(sa_seg.end(), sa_rows[i].begin(), sa_rows[i].end());
-                sa_off.push_back(sa_seg.size());
-            }
-        narena += off[nr];
-        at = p;
-    }
-    rd.drop_pending();
-    fclose(f);
-    if (!rd.err.empty()) { delete b; return fail(rd.err); }
-    {
-        const double st[6] = {rd.t_read, rd.t_scan, rd.t_alloc_r + rd.t_alloc, rd.t_inflate, rd.t_wait,
-                              BgzfReader::now() - t_start};
-        memcpy(b->stage_s, st, sizeof st);
-    }
-    const size_t n = b->pos.size();
-    if (!b->cig_off.push_back(narena)) { delete b; return fail("out of host memory"); }
-    // per-tid ranges; reorder only when the file was not coordinate-sorted
-    bool sorted = true;
-    for (size_t i = 1; i < n && sorted; i++)
-        sorted = tid_of[i] > tid_of[i - 1] || (tid_of[i] == tid_of[i - 1] && b->pos[i] >= b->pos[i - 1]);
-    std::vector<size_t> idx;
-    if (!sorted) {
-        idx.resize(n);
-        std::iota(idx.begin(), idx.end(), 0);
-        std::stable_sort(idx.begin(), idx.end(), [&](size_t x, size_t y) {
-            return tid_of[x] != tid_of[y] ? tid_of[x] < tid_of[y] : b->pos[x] < b->pos[y];
-        });
-        RawVec<int32_t> pos2, end2, tid2;
-        RawVec<uint8_t> clip2;
-        RawVec<uint64_t> off2;
-        RawVec<uint32_t> cig2;
-        if (!pos2.resize(n) || !end2.resize(n) || !tid2.resize(n) || !clip2.resize(n) || !off2.resize(n + 1) ||
-            !cig2.resize(narena)) { delete b; return fail("out of host memory"); }
-        uint64_t w = 0;
-        for (size_t k = 0; k < n; k++) {
-            const size_t i = idx[k];
-            pos2[k] = b->pos[i]; end2[k] = b->endpos[i]; clip2[k] = b->clip[i]; tid2[k] = tid_of[i];
-            const uint64_t o = b->cig_off[i], m = b->cig_off[i + 1] - o;
-            off2[k] = w;
-            if (m) memcpy(cig2.data() + w, b->cigar.data() + o, 4 * m);
-            w += m;
-        }
-        off2[n] = w;
-        b->pos.swap(pos2); b->endpos.swap(end2); b->clip.swap(clip2); b->cig_off.swap(off2); b->cigar.swap(cig2);
-        tid_of.swap(tid2);
-    }
-    b->tid_off.assign((size_t)n_ref + 1, 0);
-    for (size_t k = 0; k < n; k++) b->tid_off[(size_t)tid_of[k] + 1]++;
-    for (int32_t t = 0; t < n_ref; t++) b->tid_off[(size_t)t + 1] += b->tid_off[(size_t)t];
-    if (want_seq) {   // the ops' offsets, in the final (read, op) order
-        if (!b->ins_off.resize((size_t)n_ins + 1)) { delete b; return fail("out of host memory"); }
-        b->ins_off[0] = 0;
-        if (sorted) {
-            for (uint64_t k = 0; k < n_ins; k++) b->ins_off[k + 1] = b->ins_off[k] + b->ins_len[k];
-        } else {
-            // per file-order read its first op and first base, then the reads in sorted order
-            std::vector<uint64_t> first(n + 1, 0), fbase(n + 1, 0);
-            for (size_t i = 0, k = 0; i < n; i++) {
-                first[i + 1] = first[i] + b->ins_cnt[i];
-                fbase[i + 1] = fbase[i];
-                for (; k < first[i + 1]; k++) fbase[i + 1] += b->ins_len[k];
-            }
-            RawVec<uint8_t> bases2;
-            if (!bases2.resize((size_t)n_insb)) { delete b; return fail("out of host memory"); }
-            uint64_t k2 = 0, w = 0;
-            for (size_t r = 0; r < n; r++) {
-                const size_t i = idx[r];
-                for (uint64_t k = first[i]; k < first[i + 1]; k++, k2++) b->ins_off[k2 + 1] = b->ins_off[k2] + b->ins_len[k];
-                const uint64_t m = fbase[i + 1] - fbase[i];
-                if (m) memcpy(bases2.data() + w, b->ins_bases.data() + fbase[i], m);
-                w += m;
-            }
-            b->ins_bases.swap(bases2);
-        }
-        b->has_seq = true;
-    }
-    if (want_sa) {   // the table in the final read order: `read` holds sorted indices
-        const size_t m = sa_read.size();
-        std::vector<size_t> ord(m);
-        std::iota(ord.begin(), ord.end(), 0);
-        if (!sorted) {
-            std::vector<uint64_t> inv(n);
-            for (size_t k = 0; k < n; k++) inv[idx[k]] = k;
-            for (size_t j = 0; j < m; j++) sa_read[j] = inv[(size_t)sa_read[j]];
-            std::sort(ord.begin(), ord.end(), [&](size_t x, size_t y) { return sa_read[x] < sa_read[y]; });
-        }
-        b->sa_read.reserve(m);
-        b->sa_off.assign(1, 0);
-        b->sa_seg.reserve(sa_seg.size());
-        for (size_t j : ord) {
-            b->sa_read.push_back(sa_read[j]);
-            b->sa_seg.insert(b->sa_seg.end(), sa_seg.begin() + (ptrdiff_t)sa_off[j], sa_seg.begin() + (ptrdiff_t)sa_off[j + 1]);
-            b->sa_off.push_back(b->sa_seg.size());
-        }
-        b->has_sa = true;
-    }
-    return b;
-}
-
-}  // namespace
-
-extern "C" {
-
 int svth_bam_read_device(const char *path, int threads, const svth_dev_sink *sink, int32_t *n_targets, double *stage4,
                          char *err, size_t errcap) {
     auto fail = [&](const std::string &m) {
@@ -1058,64 +1130,32 @@ int svth_bam_read_device(const char *path, int threads, const svth_dev_sink *sin
     };
     if (!sink || !sink->begin || !sink->feed) return fail("no device sink");
     const double t_start = BgzfReader::now();
-    FILE *f = fopen(path, "rb");
-    if (!f) return fail(std::string("cannot open BAM: ") + path);
-    BgzfReader rd;
-    rd.f = f;
-    rd.threads = threads < 1 ? 1 : threads;
     // batches of whole BGZF blocks through read_next (its input buffers from the sink's allocator)
-    svth_inflater cfg{};
-    cfg.alloc = sink->alloc;
-    cfg.release = sink->release;
-    cfg.user = sink->user;
-    cfg.batch_bytes = sink->batch_bytes;
-    rd.inf = &cfg;
-    {
-        struct stat st;
-        rd.fsize = fstat(fileno(f), &st) == 0 ? (uint64_t)st.st_size : 0;
-    }
-    auto bail = [&](const std::string &m) {
-        rd.drop_pending();
-        fclose(f);
-        return fail(rd.err.empty() ? m : rd.err);
-    };
+    const svth_inflater cfg{nullptr, sink->alloc, sink->release, sink->user, sink->batch_bytes};
+    BgzfReader rd(path, threads, &cfg);
+    if (!rd.f) return fail(std::string("cannot open BAM: ") + path);
+    auto bail = [&](const std::string &m) { return fail(rd.error(m)); };
     BgzfReader::Comp c = rd.read_next();
     if (!c.ok) return bail(c.err);
     if (c.blks.empty()) return bail("not a BAM file (no BGZF blocks)");
     // the header (magic, text, references) on the host: inflate the first blocks until it is complete
     std::vector<uint8_t> h;
-    size_t bi = 0;
-    auto need = [&](size_t k) -> bool {
-        while (h.size() < k) {
-            if (bi >= c.blks.size()) return false;
+    size_t bi = 0, at = 0;
+    ZlibRaw z;
+    auto take = [&](size_t k) -> const uint8_t * {
+        while (h.size() < at + k) {
+            if (bi >= c.blks.size()) return nullptr;
             const svt_bgzf_block &b = c.blks[bi++];
             const size_t o = h.size();
             h.resize(o + b.ulen);
-            z_stream zs;
-            memset(&zs, 0, sizeof zs);
-            if (inflateInit2(&zs, -15) != Z_OK) return false;
-            zs.next_in = rd.cins[c.i].p + b.coff;
-            zs.avail_in = (uInt)b.clen;
-            zs.next_out = h.data() + o;
-            zs.avail_out = (uInt)b.ulen;
-            const int rc = inflate(&zs, Z_FINISH);
-            inflateEnd(&zs);
-            if (rc != Z_STREAM_END || zs.total_out != b.ulen) return false;
+            if (!z.block(rd.cins[c.i].p + b.coff, b.clen, h.data() + o, b.ulen)) return nullptr;
         }
-        return true;
+        at += k;
+        return h.data() + at - k;
     };
-    if (!need(8) || memcmp(h.data(), "BAM\1", 4) != 0) return bail("not a BAM file");
-    size_t at = 8 + (size_t)rd32(h.data() + 4);
-    if (!need(at + 4)) return bail("truncated BAM header (or longer than one batch)");
-    const int32_t n_ref = (int32_t)rd32(h.data() + at);
-    at += 4;
-    if (n_ref < 0) return bail("bad n_ref");
-    for (int32_t i = 0; i < n_ref; i++) {
-        if (!need(at + 4)) return bail("truncated reference list (or longer than one batch)");
-        const uint32_t ln = rd32(h.data() + at);
-        at += 4 + (size_t)ln + 4;
-        if (!need(at)) return bail("truncated reference list (or longer than one batch)");
-    }
+    int32_t n_ref = 0;
+    const std::string he = parse_header(take, " (or longer than one batch)", n_ref, nullptr);
+    if (!he.empty()) return bail(he);
     if (n_targets) *n_targets = n_ref;
     char e[512] = {0};
     if (sink->begin(sink->user, n_ref, e, sizeof e) != 0) return bail(e[0] ? e : "device sink: begin failed");
@@ -1136,9 +1176,7 @@ int svth_bam_read_device(const char *path, int threads, const svth_dev_sink *sin
         if (!c.ok) return bail(c.err);
         if (c.blks.empty()) break;
     }
-    rd.drop_pending();
-    fclose(f);
-    if (stage4) {
+    if (stage4) {   // (no batch is pending here: the helper thread has finished)
         stage4[0] = rd.t_read;
         stage4[1] = t_feed;
         stage4[2] = t_wait + rd.t_alloc_r;

@@ -2,7 +2,9 @@
 inflate + record parsing with T threads, CG-tag CIGARs, BAI region reads; vcf_audit.cpp:
 multithreaded VCF parse + batch formatting) and the oracle's threaded paths run under
 ASan+UBSan and under TSan (drivers in tests/san/, built by svtrek_amd.build.build_sanitizers);
-each instrumented run must exit cleanly and agree with the uninstrumented library."""
+each instrumented run must exit cleanly and agree with the uninstrumented library.  The reads here
+succeed: they cover the reader's stages (the one BGZF scan, header, chunks, the reorder-free finish);
+its error exits run under ASan+UBSan in tests/test_ingest_err_san.py."""
 import glob
 import os
 import random
